@@ -11,12 +11,18 @@ the only exchange is one all-gather of the per-env episode returns inside each t
 every env of the job: turbulence update, DM, WFS camera, slopes, reconstruction, reward, integrator command -- all on the
 device, inputs resident in HBM.
 
-Timing: W warm-up steps, then R timed regions of EXACTLY K steps each, every region bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; `ms_per_step` / `value` come from the MEDIAN region
-(R is chosen so that the regions add up to >= --min-seconds; their spread is reported).  Beside it, in the same JSON line:
-`roofline` (dominant kernel, HIP-event timed on the launch stream), `cpu_baseline` (the NumPy oracle on this host: one core,
-and one process per core), `ideal_detector` / `razor_camera` (the same workload with other cameras), `step_api` (the per-call
-Python API a trainer uses) and `configs` (BASELINE configs[2..4] per-GPU shards, driver-timed; N = 1 only).
+Timing: W warm-up steps, then ONE timed region of exactly K steps, bracketed by barrier + torch.cuda.synchronize() on both
+sides and reduced with MAX over the ranks; `ms_per_step` = region / K, `value` = env-steps of the job / region.  A plain run does
+only that (set up, warm up, time, optionally dump, print the line).
+
+--dump-outputs DIR: after the timed region, what its last step handed back (observation, reward, Strehl of every env of rank 0)
+and the episode returns accumulated over the timed steps, as DIR/<name>.npy in the env's dtype (float32 / float64).  Every
+seed is fixed, so the same arguments give the same inputs on every run.
+
+--full adds, in the same JSON line: `roofline` / `kernels` (HIP-event timed on the launch stream), `cpu_baseline` (the NumPy
+oracle on this host: one core, and one process per core), `ideal_detector` / `razor_camera` (the same workload with other
+cameras), `step_api` (the per-call Python API a trainer uses), `per_env_wind` and `configs` (BASELINE configs[2..4] per-GPU
+shards, driver-timed; N = 1 only).  Those legs time regions of min(K, 200) steps, repeated until --min-seconds.
 """
 from __future__ import annotations
 
@@ -57,6 +63,8 @@ CONFIGS = {
                         windDirection=[0.0, 72.0, 144.0], fractionalR0=[0.45 / 0.65, 0.1 / 0.65, 0.1 / 0.65],
                         altitude=[0.0, 1000.0, 5000.0], nModes=50)),
 }
+FULL_LEG_STEPS = 200           # --full: region length of the legs beside the headline (camera variants, per-env wind, profile)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: beyond this, a fixed sample of the envs is written
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32-input MFMA = the f32 vector rate
 # rocprofv3 --pmc passes of this command (scripts/pmc_collect.sh -> scripts/pmc_to_json.py), one file per camera setting, and of the
@@ -317,6 +325,22 @@ def start_episode(env, seed=17):
     return env.reset_soft()
 
 
+def dump_outputs(path, arrays, n_envs):
+    """--dump-outputs: every array (leading env dimension of length n_envs) as path/<name>.npy in its own float dtype.  Past
+    DUMP_MAX_BYTES, the same fixed, seeded sample of envs from each, and its indices as env_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        m = max(1, n_envs * DUMP_MAX_BYTES // (2 * total))       # half the cap: room for the index file
+        idx = np.sort(np.random.RandomState(0).choice(n_envs, m, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    for k, a in host.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def kernel_profile(env, run, n_local):
     """HIP-event pairs around every kernel launch of `run()` (aoenv_profile): {stage: {avg_us, launches}} and the dominant stage's
     roofline.  The events sit on the launch stream, so a stage's time is its kernels' device time plus their launch gaps."""
@@ -494,31 +518,40 @@ def config_headline(args, torch, dist, rank, world, local, cpu):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the headline: one region of exactly this many")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before it")
     ap.add_argument("--envs-per-gpu", type=int, default=None, help="default: 256 (C2) / the config's own per-GPU shard")
     ap.add_argument("--config", default="C2", type=str.upper, choices=["C2"] + sorted(CONFIGS),
                     help="the workload of the headline line: C2 (default) = BASELINE configs[1]; C3 / C4 / C5 = BASELINE configs[2..4] "
                          "as stated (with --gpus 8: 512 resp. 256 envs per GPU), C3M = the modulated Pyramid.  Same timer: K-step "
                          "regions, all-gather of the episode returns inside each")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--min-seconds", type=float, default=0.6, help="the timed regions of K steps are repeated until they add up to this")
+    ap.add_argument("--min-seconds", type=float, default=0.6, help="--full: the timed regions of its legs are repeated until they add up to this")
     ap.add_argument("--noise", nargs="?", const="razor", default="photon", choices=["off", "photon", "razor"],
                     help="WFS camera of the headline: photon (default) = photon (Poisson) noise only, the reference envs' default "
                          "(MAIN/OOPAOEnv/OOPAOEnv.py:379); razor = the Razor env's camera (photon + dark + read-out noise, QE, FWC, "
                          "10-bit ADC: OOPAOEnvRazor.py:243-250, 333); off = the ideal detector of the parity configuration")
-    ap.add_argument("--configs", default="C3,C3M,C4,C5", help="comma list of BASELINE configs timed beside the headline (N = 1 only); 'none' skips them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--configs", default="C3,C3M,C4,C5", help="--full: comma list of BASELINE configs timed beside the headline (N = 1 only); 'none' skips them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: headline + roofline only (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--dry-run-launch", action="store_true", help="print the rank launcher command of --gpus N and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline and per-kernel profile, CPU baseline, other cameras, step API, "
+                         "per-env wind, BASELINE configs (the --no-* / --configs / --min-seconds / --cpu-seconds options shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (C2 headline only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config != "C2":
+        raise SystemExit("--dump-outputs: only the C2 headline writes its outputs")
     maybe_spawn_ranks(args, sys.argv[1:])
     camera = {"photon": "papyrus", "razor": "razor", "off": "ideal"}[args.noise]
 
     rank_env, world_env = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     cpu = None
-    if not args.no_cpu_baseline and rank_env == 0 and world_env == 1 and args.config == "C2":
+    if args.full and not args.no_cpu_baseline and rank_env == 0 and world_env == 1 and args.config == "C2":
         cpu = cpu_baseline(camera, args.cpu_seconds, all_cores=not args.no_extras)   # before torch / HIP are loaded: the workers are forks
 
     import torch
@@ -539,41 +572,45 @@ def main():
     n_local = args.envs_per_gpu or 256
     n_total = n_local * world
     K, W = args.steps, args.warmup
+    Ke = min(K, FULL_LEG_STEPS)                     # --full legs: regions of Ke steps at frame indices W .. W + 10 Ke + 64
 
     env = BatchedAOEnv(n_envs=n_local, device=local, dtype=args.dtype, return_frame=True, env_index_offset=rank * n_local)
-    env.set_params(dict(GEOMETRY, nLoop=W + 10 * K + 64), wfs_type="shackhartmann", camera=camera)
+    env.set_params(dict(GEOMETRY, nLoop=W + K + (10 * Ke + 64 if args.full else 0)), wfs_type="shackhartmann", camera=camera)
     timer = Timer(torch, dist, world, env.device)
     start_episode(env)
     returns = torch.zeros(n_local, device=env.device, dtype=env.tdtype)
-    if world > 1:                                   # warm the communicator outside the timed regions
+    if world > 1:                                   # warm the communicator outside the timed region
         aodist.all_gather_returns(returns, n_total)
     env.run_integrator(0, W)                        # W untimed warm-up steps
     env.accumulate_returns(returns)                 # every step adds its reward on the device (episode return)
     gathered = {}
 
     def region(r):
-        env.run_integrator(W + (r % 8) * K, K)      # K closed-loop steps of every env: one library call, K x (1..3) launches
+        env.run_integrator(W, K)                    # K closed-loop steps of every env: one library call, K x (1..3) launches
         gathered["returns"] = aodist.all_gather_returns(returns, n_total)
 
-    times = timer.regions(region, args.min_seconds)
+    dt = timer.regions(region, 0.0, min_repeats=1, max_repeats=1)[0]
     env.accumulate_returns(None)
-    s = stats(times)
-    dt = s["median"]
     strehl = float(env._strehl.mean())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"obs": env._obs, "reward": env._reward, "strehl": env._strehl,
+                                         "episode_return": returns}, n_local)
 
-    # roofline leg: the same loop again with a hipEvent pair around every kernel launch
-    n_prof = min(max(K, 100), 2 * K + 64)
-    per_kernel, roof, step_bytes = kernel_profile(env, lambda: env.run_integrator(W + 8 * K, n_prof), n_local)
+    per_kernel, roof, step_bytes = None, None, algorithmic_bytes(env)[0]
     extras = {}
-    if not args.no_extras and world == 1:
+    if args.full:
+        # roofline leg: the same loop again with a hipEvent pair around every kernel launch
+        n_prof = min(max(Ke, 100), 2 * Ke + 64)
+        per_kernel, roof, step_bytes = kernel_profile(env, lambda: env.run_integrator(W, n_prof), n_local)
+    if args.full and not args.no_extras and world == 1:
         for cam2, key in (("ideal", "ideal_detector"), ("razor", "razor_camera"), ("papyrus", "photon_noise")):
             if cam2 == camera:
                 continue
             set_camera(env, cam2)
             env.run_integrator(W, 10)
-            t2 = timer.regions(lambda r: env.run_integrator(W + (r % 8) * K, K), args.min_seconds / 3)
+            t2 = timer.regions(lambda r: env.run_integrator(W + (r % 8) * Ke, Ke), args.min_seconds / 3)
             s2 = stats(t2)
-            extras[key] = {"value": n_total * K / s2["median"], "unit": "env-steps/s", "ms_per_step": 1e3 * s2["median"] / K,
+            extras[key] = {"value": n_total * Ke / s2["median"], "unit": "env-steps/s", "ms_per_step": 1e3 * s2["median"] / Ke,
                            "repeats": len(t2), "camera": CAMERA_NOTE[cam2]}
         set_camera(env, camera)
         # the per-call Python API a trainer's rollout loop uses (MAIN/PO4AO/mbrl.py:64-89): action = gain * obs in torch
@@ -607,9 +644,9 @@ def main():
         nl = env.param.nLayer
         env.set_wind_per_env(rs.uniform(5.0, 15.0, size=(n_local, nl)), rs.uniform(0.0, 360.0, size=(n_local, nl)), reset=True)
         env.run_integrator(W, 10)
-        t3 = timer.regions(lambda r: env.run_integrator(W + (r % 8) * K, K), args.min_seconds / 3)
+        t3 = timer.regions(lambda r: env.run_integrator(W + (r % 8) * Ke, Ke), args.min_seconds / 3)
         s3 = stats(t3)
-        extras["per_env_wind"] = {"value": n_total * K / s3["median"], "unit": "env-steps/s", "ms_per_step": 1e3 * s3["median"] / K,
+        extras["per_env_wind"] = {"value": n_total * Ke / s3["median"], "unit": "env-steps/s", "ms_per_step": 1e3 * s3["median"] / Ke,
                                   "repeats": len(t3), "note": "every env its own wind: 5-15 m/s, any direction (aoenv_set_wind_env); same camera as the headline"}
     if rank != 0:
         return
@@ -620,14 +657,13 @@ def main():
         "metric": "AO env-steps/sec (batched loops)", "value": n_total * K / dt, "unit": "env-steps/s",
         "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "repeats": len(times), "region_ms": {k: 1e3 * v for k, v in s.items()},
+        "timed_ms": 1e3 * dt,
         "config": {"workload": "8m / 20x20 Shack-Hartmann, 256 batched envs per GPU, integrator closed loop "
                                "(BASELINE.json configs[1])",
                    "envs_per_gpu": n_local, "envs_total": n_total, "resolution": env.R, "n_valid_act": env.nValidAct,
                    "n_signal": env.nSignal, "layers": env.param.nLayer, "controller": "leaky integrator, gain 0.5",
                    "camera": CAMERA_NOTE[camera], "noise": args.noise,
                    "parallelism": f"env-shards x{world}, all-gather of episode returns"},
-        "roofline": roof,
         "step_roofline": {"algorithmic_bytes_per_env_step": step_bytes,
                           "achieved_GBs": step_bytes * n_local / (dt / K) / 1e9,
                           "frac_of_hbm_peak": step_bytes * n_local / (dt / K) / 1e9 / HBM_PEAK_GBS},
@@ -635,17 +671,18 @@ def main():
                  "achieved_tflops": fl["total"] * n_local / (dt / K) / 1e12, "peak_tflops_f32": MFMA_F32_PEAK_TFLOPS,
                  "frac": fl["total"] * n_local / (dt / K) / 1e12 / MFMA_F32_PEAK_TFLOPS,
                  "pmc": None if pmc is None else pmc.get("mfma", {}).get("env_step")},
-        "kernels": per_kernel,
         "mean_strehl_last_step": strehl,
         "mean_episode_return": float(gathered["returns"].mean()),
     }
+    if args.full:
+        out.update(roofline=roof, kernels=per_kernel)
     out.update(extras)
     if cpu is not None:
         out["cpu_baseline"] = cpu
     env.close()
     del env
     torch.cuda.empty_cache()
-    if world == 1 and not args.no_extras and args.configs.lower() != "none":
+    if args.full and world == 1 and not args.no_extras and args.configs.lower() != "none":
         out["configs"] = {}
         for name in [c.strip().upper() for c in args.configs.split(",") if c.strip()]:
             if name not in CONFIGS:

@@ -19,7 +19,7 @@ for r in range(rounds):
         env = dict(os.environ)
         if path != "main":
             env["AOENV_LIB"] = os.path.join(REPO, path)
-        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline", "--min-seconds", "0.4",
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "8000", "--warmup", "5", "--full", "--no-extras", "--no-cpu-baseline", "--min-seconds", "0.4",
                "--noise", noise, "--config", config]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True)
         if out.returncode != 0:

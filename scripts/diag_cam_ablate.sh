@@ -18,7 +18,7 @@ if [ "$mode" = build ]; then
 else
   for m in "$@"; do
     echo "== ablate mask $m"
-    AOENV_LIB=build/ablate/libaoenv_$m.so python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --min-seconds 0.2 |
+    AOENV_LIB=build/ablate/libaoenv_$m.so python bench.py --steps 4000 --warmup 5 --full --no-extras --no-cpu-baseline --min-seconds 0.2 |
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('   step us', round(1e3*d['ms_per_step'],2), ' kernel us', round(d['kernels']['env_step']['avg_us'],2))"
   done
 fi

@@ -17,7 +17,7 @@ if [ "$mode" = build ]; then
   wait
 else
   for name in "$@"; do
-    AOENV_LIB=build/variants/libaoenv_$name.so python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --min-seconds 0.3 2>/dev/null |
+    AOENV_LIB=build/variants/libaoenv_$name.so python bench.py --steps 6000 --warmup 5 --full --no-extras --no-cpu-baseline --min-seconds 0.3 2>/dev/null |
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name: step us', round(1e3*d['ms_per_step'],2), ' kernel us', round(d['kernels']['env_step']['avg_us'],2))"
   done
 fi

@@ -6,7 +6,7 @@
 #   usage: scripts/pmc_collect.sh TAG [bench flags...]
 set -o pipefail
 TAG=${1:-r03}; shift
-BENCH="bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --min-seconds 0.2 $*"
+BENCH="bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --min-seconds 0.2 $*"
 OUT=$PWD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}

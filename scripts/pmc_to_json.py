@@ -114,7 +114,7 @@ for b in sorted({e["kernel"] for e in kernels.values()}):
     if cand:
         production[b] = max(cand, key=lambda k: kernels[k]["total_us"])
 over = [k for k, e in kernels.items() if e.get("hbm_frac_of_peak", 0) > 1.0]
-out = {"note": note or "rocprofv3 --pmc passes of `python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras` (scripts/pmc_collect.sh); "
+out = {"note": note or "rocprofv3 --pmc passes of `python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras` (scripts/pmc_collect.sh); "
        "entries keyed `kernel<template args>@grid`; counter values averaged per launch of the entry; durations from the kernel trace of "
        "the same command; hbm_bytes_per_launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950 FETCH_SIZE correction)",
        "n_envs": n_envs, "camera": camera, "kernels": kernels, "production": production, "entries_above_hbm_peak": over}

@@ -581,3 +581,32 @@ def test_phase_kernel_with_16_byte_accesses_is_bit_identical(coefs_image):
         assert all(torch.equal(p, q) for p, q in zip(x, y))
     assert np.array_equal(pa, pb) and np.array_equal(oa, ob) and np.array_equal(ta, tb) and np.array_equal(sa, sb)
     assert np.abs(pa).max() > 0
+
+
+def test_plain_bench_times_its_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: the headline line alone, K timed steps, and the last step's outputs as
+    float .npy files that a second run with the same arguments reproduces bit for bit."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                              "--envs-per-gpu", "32", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("obs", "reward", "strehl", "episode_return")})
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 30 and line["warmup"] == 5 and line["dtype"] == "f32"
+    assert abs(line["ms_per_step"] * 30 - line["timed_ms"]) < 1e-6 * line["timed_ms"]
+    assert abs(line["value"] - 32 * 30 / (line["timed_ms"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "kernels", "cpu_baseline", "configs", "step_api"} & set(line)       # those need --full
+    a, b = dumps
+    assert a["obs"].shape == (32, 21, 21) and a["reward"].shape == a["strehl"].shape == a["episode_return"].shape == (32,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    assert np.abs(a["obs"]).max() > 0

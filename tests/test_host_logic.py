@@ -198,6 +198,25 @@ def test_bench_cpu_baseline_runs_the_oracle_with_the_camera():
     assert out["cores"] == 1 and out["kind"] == "port" and out["value"] > 0 and "camera: papyrus" in out["sample"]
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float .npy per output; past the size cap, the same seeded sample of envs from every array."""
+    import torch
+    import bench
+    arrays = {"obs": torch.arange(64 * 3 * 3, dtype=torch.float32).reshape(64, 3, 3), "ret": torch.arange(64, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, 64)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == v.numpy().dtype and np.array_equal(got, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, 64)
+    files = {f: np.load(tmp_path / "s1" / f) for f in sorted(os.listdir(tmp_path / "s1"))}
+    assert sorted(files) == ["env_index.npy", "obs.npy", "ret.npy"] and sum(a.nbytes for a in files.values()) <= 1024
+    idx = files["env_index.npy"].astype(int)
+    assert np.array_equal(files["ret.npy"], idx) and np.array_equal(files["obs.npy"], arrays["obs"].numpy()[idx])
+    assert all(np.array_equal(a, np.load(tmp_path / "s2" / f)) for f, a in files.items())
+
+
 def test_atmosphere_clock_source_matches_the_oracle(tmp_path):
     """rlao_amd/csrc/common.hpp::clock_subpixel / taps_from_buff -- ONE source for the host clock (one wind per shard) and for the
     device clocks of per-env winds (k_ring_prepare_env) -- compiled for the host and stepped next to the oracle's updateLayer
