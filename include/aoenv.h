@@ -287,7 +287,16 @@ enum AoOption {
                                  nothing else in front of the step kernel (bit-identical results).  0: gather + draw in a launch of
                                  their own in front of the GEMM.  [Round-2 note: the same work one crossing ahead on a SECOND STREAM was
                                  slower -- with one 1024-lane workgroup per CU the side stream finds no free CU (5.59 -> 4.97 M env-steps/s)] */
-    AOENV_OPT_FAST_TRIG = 2  /* 1 (default): v_sin/v_cos after Cody-Waite reduction in the float32 SH kernel; 0: sincosf */
+    AOENV_OPT_FAST_TRIG = 2, /* 1 (default): v_sin/v_cos after Cody-Waite reduction in the float32 SH kernel; 0: sincosf */
+    AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
+                                 also keeps the shard off the fused step kernel; other bits are rejected */
+};
+/* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
+enum AoPath {
+    AOENV_PATH_PHASE_DWORD = 256,      /* float32 phase kernel with dword accesses instead of the 16-byte one (R % 4 == 0) */
+    AOENV_PATH_GENERIC = 512,          /* the Stockham Pyramid passes at nRes 528 / 288, the tiled 16-byte phase kernel instead of its
+                                          one-layer band form */
+    AOENV_PATH_PYR_ROUND_ROBIN = 1024  /* nRes 528 / 288 Pyramid column pass: blocks dealt round-robin over the XCDs */
 };
 int aoenv_set_option(AoEnv* env, int option, int value);
 

@@ -22,6 +22,9 @@ WFS_SH, WFS_PYRAMID = 0, 1
 
 (OPT_FAST_WFS, OPT_MFMA_GEMM, OPT_FAST_TRIG, OPT_STORE_ATM_OPD, OPT_FUSED_TAIL, OPT_FUSED_STEP, OPT_DEFER_RING, OPT_COEFS_IMAGE,
  OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD) = range(10)
+OPT_FORCE_PATH = 99
+# enum AoPath: bits of OPT_FORCE_PATH
+PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN = 256, 512, 1024
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
                 "gemm_recon", "recon_finish", "pyramid", "sh_tail", "env_step", "detector")
 

@@ -15,10 +15,6 @@
 #include "detector.hpp"
 #include "sh_device.hpp"
 
-#ifndef AO_ABL
-#define AO_ABL(bit) 0                                             // (timing ablations of the fused step kernel, scripts/diag_cam_ablate.sh)
-#endif
-
 namespace ao {
 
 typedef float f32x16s __attribute__((ext_vector_type(16)));
@@ -67,14 +63,9 @@ __device__ inline void camera_sh6_lane(f32x16s& pxv, bool ok, uint32_t px0, int 
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) v4[sl] = ok ? fmaxf(pxv[sl], 0.f) : 0.f;
             uint32_t o[4], o2[4], o3[4] = {0u, 0u, 0u, 0u};
-            if (AO_ABL(0)) {
-#pragma unroll
-                for (int z = 0; z < 4; ++z) { o[z] = (qid + z) * 2654435761u + det.frame_counter; o2[z] = o[z] * 40503u + z; o3[z] = o2[z] * 69069u + 1u; }
-            } else {
-                quad_bits(qid, e, det, kDrawPhoton, o);
-                quad_bits(qid, e, det, kDrawPhoton2, o2);
-                if (__any(fmaxf(fmaxf(v4[0], v4[1]), fmaxf(v4[2], v4[3])) >= palias::kCoarseStep)) quad_bits(qid, e, det, kDrawPhoton3, o3);
-            }
+            quad_bits(qid, e, det, kDrawPhoton, o);
+            quad_bits(qid, e, det, kDrawPhoton2, o2);
+            if (__any(fmaxf(fmaxf(v4[0], v4[1]), fmaxf(v4[2], v4[3])) >= palias::kCoarseStep)) quad_bits(qid, e, det, kDrawPhoton3, o3);
             float lam4[4], k4[4];
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) {
@@ -82,12 +73,7 @@ __device__ inline void camera_sh6_lane(f32x16s& pxv, bool ok, uint32_t px0, int 
                 over |= ov ? 1u << (4 * t + sl) : 0u;
                 lam4[sl] = ov ? 0.f : v4[sl];
             }
-            if (AO_ABL(1)) {
-#pragma unroll
-                for (int sl = 0; sl < 4; ++sl) k4[sl] = v4[sl];
-            } else {
-                poisson_alias4(lam4, o, o2, o3, tab, k4);
-            }
+            poisson_alias4(lam4, o, o2, o3, tab, k4);
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) pxv[sl] = v4[sl] >= lmax ? v4[sl] : k4[sl];
             camera_rotate(pxv);

@@ -190,7 +190,7 @@ template <typename T>
 struct KArgs {                 // kernel argument block of the phase kernels
     PhaseArgs pa;
     PhaseBuffers<T> pb;
-    int R, n_act, n_valid_act, tx, rp, ablate;
+    int R, n_act, n_valid_act, tx, rp;
     T atm_scale;   // lambda_atm / 2 pi
     T src_scale;   // 2 pi / lambda_src
 };
@@ -199,7 +199,7 @@ KArgs<T> make_phase_kargs(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int R,
                           double atm_wavelength, double src_wavelength);
 template <typename T>
 int launch_phase(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int n_env, int R, int n_act, int n_valid_act,
-                 double atm_wavelength, double src_wavelength, int use_mfma, hipStream_t st);
+                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st);
 
 template <typename T>
 struct ShConst {
@@ -326,8 +326,8 @@ struct PyrArgs {
     unsigned magic_seq;    // floor(2^32 / seq_per_block) + 1: i / seq_per_block for i < 2^16 without a division (set by the launchers)
     int phasor_mult;       // the pupil field is multiplied by exp(-i pi m (x + y) / N) on the padded grid: m = N + 1 (Pyramid with a
                            // centred mask, Pyramid.py:294), 1 (science PSF, Telescope.py:316), 0 (none)
-    int generic_fft;       // diagnostic (aoenv_set_option 99): bit 512 the Stockham passes also where pyr528_kernels.hip applies, bit 1024
-                           // its column blocks dealt round-robin over the XCDs
+    int force_path;        // AOENV_OPT_FORCE_PATH: AOENV_PATH_GENERIC the Stockham passes also where pyr528_kernels.hip applies,
+                           // AOENV_PATH_PYR_ROUND_ROBIN its column blocks dealt round-robin over the XCDs
 };
 // nRes = 528 / 288 in float32: the passes on the register-resident 24 x 22 / 16 x 18 transforms (pyr528_kernels.hip)
 int pyramid528_supported(const PyrArgs<float>& a);

@@ -159,7 +159,7 @@ struct AoEnv {
     bool use_fused_step = true;             // aoenv_set_option(AOENV_OPT_FUSED_STEP): the whole step in one kernel
     bool store_opd_atm = false;             // aoenv_set_option(AOENV_OPT_STORE_ATM_OPD): write atm.OPD every step
     bool atm_user_defined = false;          // aoenv_set_atm_opd() until the next step / new screens
-    int debug_ablate = 0;                   // aoenv_set_option(99): skip kernel sections (timing diagnosis only)
+    int force_path = 0;                     // aoenv_set_option(AOENV_OPT_FORCE_PATH): AoPath bits
     bool prof_on = false;
     struct ProfEv { int stage; hipEvent_t a, b; };
     std::vector<ProfEv> prof_ev;
@@ -490,7 +490,7 @@ int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int sto
     fill_phase_args<T>(env, pa, pb, update_atm, store_atm, store_phase);
     AO_PROF(env, PHASE, st);
     return launch_phase<T>(pa, pb, env->E, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength,
-                           (env->use_mfma ? 1 : 0) | (env->debug_ablate << 8), st);
+                           env->use_mfma, env->force_path, st);
 }
 
 // the WFS camera on the frame in HBM (detector.hpp); every measurement is a new frame of the noise streams
@@ -538,7 +538,7 @@ int run_wfs(AoEnv* env, hipStream_t st) {
         pa.centering = env->c.pyr_centering;
         pa.phasor_mult = env->c.pyr_centering ? env->c.pyr_n_res + 1 : 0;
         pa.n_env = env->E;
-        pa.generic_fft = env->debug_ablate & (512 | 1024);
+        pa.force_path = env->force_path;
         PyrSlopeArgs<T> sl{};
         sl.frame = env->as<T>(env->frame);
         sl.valid_idx = env->subap_idx;
@@ -623,10 +623,10 @@ int recon_product(AoEnv* env, int* splits, hipStream_t st) {
                                            env->nSig, s1, st));
                 // (32 and more column tiles of 64 actuators fill the chip for any shard: no split of the short K, one output slab instead of
                 //  K / 64 of them -- at the ELT size 11 MB written and read back by the epilogue instead of 43; the choice does not depend on E)
-                *splits = (cdiv(env->A, 64) >= 32 && !(env->debug_ablate & 8192)) ? 1 : gemm_splits(env->E, env->A, Kp);
+                *splits = cdiv(env->A, 64) >= 32 ? 1 : gemm_splits(env->E, env->A, Kp);
                 // a long chain read by many column tiles is summed once first (same order of the additions: same bits)
                 int xs = s1;
-                if (s1 > 1 && cdiv(env->A, 64) >= 8 && !(env->debug_ablate & 4096)) {
+                if (s1 > 1 && cdiv(env->A, 64) >= 8) {
                     AO_TRY(launch_sum_slabs(t, (size_t)env->E * Kp, s1, st));
                     xs = 1;
                 }
@@ -665,7 +665,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && env->debug_ablate == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && env->force_path == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -1917,7 +1917,11 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             if (value) AO_TRY(alloc_dm_rows(env));
             env->use_coefs_img = value != 0;
             return 0;
-        case 99: env->debug_ablate = value; return 0;
+        case AOENV_OPT_FORCE_PATH:
+            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN))
+                return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
+            env->force_path = value;
+            return 0;
         default: return fail("unknown option %d", option);
     }
 }

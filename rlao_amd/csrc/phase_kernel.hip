@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
                 }
                 const bool in = a.pb.pupil[q] != 0;
                 const T res = in ? (atm + dm) : (T)0;
-                if (a.pa.store_phase && (!(a.ablate & 8) || res == 12345.f)) a.pb.phase[pix0 + q] = res * a.src_scale;
+                if (a.pa.store_phase) a.pb.phase[pix0 + q] = res * a.src_scale;
                 if (in) {
                     const double da = (double)atm, dr = (double)res;
                     s_atm += da;
@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
     // wave w takes the tiles w, w + 4, ...; the A operands (the tile's 16 rows of gy) are the same for every column tile
     // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
     // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
-    if (!rows_given && !(a.ablate & 1)) {
+    if (!rows_given) {
         if (nAp <= 32) s1_tiles_mfma<8>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
         else s1_tiles_mfma<32>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
     }
@@ -289,7 +289,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) sup[tt][r] = 0.f;
 
-    if (a.pa.update_atm && !(a.ablate & 2)) {
+    if (a.pa.update_atm) {
         for (int l = 0; l < a.pa.n_layer; ++l) {
             const LayerTaps& tp = layer_taps(a.pa, l, e);
             const int S = a.pa.S_l[l], foot = a.pa.foot_l[l];       // the layer's own grid (fov != 0: it grows with the altitude)
@@ -352,7 +352,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
         for (int r = 0; r < 4; ++r) {
             const int xl = 16 * (2 * ly + tt) + lc, y = 4 * lq + r;
             const bool okp = xl < txe && y < tye;
-            const uint8_t t = (a.ablate & 64) ? 1 : a.pb.pupil[okp ? (size_t)(y0 + y) * R + (x0 + xl) : 0];
+            const uint8_t t = a.pb.pupil[okp ? (size_t)(y0 + y) * R + (x0 + xl) : 0];
             pup[tt][r] = okp && t != 0;
         }
     double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
@@ -361,7 +361,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
     constexpr int NQ = 8;
     f32x4 aq[NQ];
     const int nq = a.pb.ga_stride / 4;
-    if (rows_given && !(a.ablate & 4)) {
+    if (rows_given) {
         const int Rp = (R + 127) & ~127;
         const f32x4* asrc = reinterpret_cast<const f32x4*>(a.pb.s1a) + ((size_t)e * (Rp >> 4) + (y0 >> 4)) * nq * 64 + lx;
 #pragma unroll
@@ -375,7 +375,6 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
         // B[k = lane >> 4 + 4 s][j = lane & 15 -> column] = gx[x][k]: the operand table gives a lane its k steps as 16-byte loads
         const f32x4* bsrc = reinterpret_cast<const f32x4*>(a.pb.gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
         if (rows_given) {
-            if (!(a.ablate & 4)) {
             f32x4 bq[NQ];
 #pragma unroll
             for (int q4 = 0; q4 < NQ; ++q4) bq[q4] = bsrc[q4 < nq ? 64 * q4 : 0];
@@ -386,14 +385,14 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
                     for (int d = 0; d < 4; ++d)
                         if (16 * q4 + 4 * d < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[q4][d], bq[q4][d], dmv, 0, 0, 0);
                 }
-            }
-        } else if (!(a.ablate & 4))
-        for (int kb = 0; kb < nAp; kb += 32) {                    // 8 k steps = 2 loads per batch
-            const f32x4 b0 = bsrc[64 * (kb / 16)], b1 = bsrc[64 * (kb / 16 + 1 < nq ? kb / 16 + 1 : kb / 16)];
-            const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+        } else {
+            for (int kb = 0; kb < nAp; kb += 32) {                // 8 k steps = 2 loads per batch
+                const f32x4 b0 = bsrc[64 * (kb / 16)], b1 = bsrc[64 * (kb / 16 + 1 < nq ? kb / 16 + 1 : kb / 16)];
+                const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (kb + 4 * j < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[kb + 4 * j], bv[j], dmv, 0, 0, 0);
+                for (int j = 0; j < 8; ++j)
+                    if (kb + 4 * j < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[kb + 4 * j], bv[j], dmv, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -407,10 +406,10 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
                 } else {
                     atm = a.pb.opd_atm[pix0 + q];
                 }
-                const bool in = (a.ablate & 16) ? true : pup[tt][r];
+                const bool in = pup[tt][r];
                 const float res = in ? (atm + dmv[r]) : 0.f;
-                if (a.pa.store_phase && (!(a.ablate & 8) || res == 12345.f)) a.pb.phase[pix0 + q] = res * a.src_scale;
-                if (in && !(a.ablate & 32)) {
+                if (a.pa.store_phase) a.pb.phase[pix0 + q] = res * a.src_scale;
+                if (in) {
                     const double da = (double)atm, dr = (double)res;
                     s_atm += da;
                     q_atm += da * da;
@@ -492,7 +491,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     // wave w takes the tiles w, w + 4, ...; the A operands (the tile's 16 rows of gy) are the same for every column tile
     // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
     // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
-    if (!rows_given && !(a.ablate & 1)) {
+    if (!rows_given) {
         if (nAp <= 32) s1_tiles_mfma<8>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
         else s1_tiles_mfma<32>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
     }
@@ -503,7 +502,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     // ga_stride / 4 16-byte loads per lane (<= 8: n_act <= 128), all in flight together
     f32x4 aq[NQ];
     const int nq = a.pb.ga_stride / 4;
-    if (rows_given && !(a.ablate & 4)) {
+    if (rows_given) {
         const int Rp = (R + 127) & ~127;
         const f32x4* asrc = reinterpret_cast<const f32x4*>(a.pb.s1a) + ((size_t)e * (Rp >> 4) + (y0 >> 4)) * nq * 64 + lx;
 #pragma unroll
@@ -533,7 +532,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
         }
         return v;
     };
-    if (BAND && a.pa.update_atm && !(a.ablate & 2)) {
+    if (BAND && a.pa.update_atm) {
         const LayerTaps& tp = layer_taps(a.pa, 0, e);
         const int S = a.pa.S_l[0], foot = a.pa.foot_l[0];
         const float* map = static_cast<const float*>(a.pa.screen[0]) + (size_t)e * S * S;
@@ -558,7 +557,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) sup[tt][r] = 0.f;
 
-    if (a.pa.update_atm && !(a.ablate & 2)) {
+    if (a.pa.update_atm) {
         for (int l = 0; l < (BAND ? 1 : a.pa.n_layer); ++l) {
             const LayerTaps& tp = layer_taps(a.pa, l, e);
             if (!BAND) {
@@ -615,8 +614,8 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     for (int tt = 0; tt < 2; ++tt) {
         const int xl = 16 * (2 * ly + tt) + 4 * lq, y = lc;
         const bool okp = xl < txe && y < tye;
-        uint32_t t4 = 0x01010101u;
-        if (!(a.ablate & 64)) __builtin_memcpy(&t4, a.pb.pupil + (okp ? (size_t)(y0 + y) * R + (x0 + xl) : 0), 4);
+        uint32_t t4;
+        __builtin_memcpy(&t4, a.pb.pupil + (okp ? (size_t)(y0 + y) * R + (x0 + xl) : 0), 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) pup[tt][r] = okp && ((t4 >> (8 * r)) & 0xffu) != 0;
     }
@@ -630,7 +629,6 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
         // lane FOUR CONSECUTIVE pixels of ONE row: every global access below is a 16-byte one
         const f32x4* bsrc = reinterpret_cast<const f32x4*>(a.pb.gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
         if (rows_given) {
-            if (!(a.ablate & 4)) {
             f32x4 bq[NQ];
 #pragma unroll
             for (int q4 = 0; q4 < NQ; ++q4) bq[q4] = bsrc[q4 < nq ? 64 * q4 : 0];
@@ -641,14 +639,14 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
                     for (int d = 0; d < 4; ++d)
                         if (16 * q4 + 4 * d < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[q4][d], aq[q4][d], dmv, 0, 0, 0);
                 }
-            }
-        } else if (!(a.ablate & 4))
-        for (int kb = 0; kb < nAp; kb += 32) {                    // 8 k steps = 2 loads per batch
-            const f32x4 b0 = bsrc[64 * (kb / 16)], b1 = bsrc[64 * (kb / 16 + 1 < nq ? kb / 16 + 1 : kb / 16)];
-            const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+        } else {
+            for (int kb = 0; kb < nAp; kb += 32) {                // 8 k steps = 2 loads per batch
+                const f32x4 b0 = bsrc[64 * (kb / 16)], b1 = bsrc[64 * (kb / 16 + 1 < nq ? kb / 16 + 1 : kb / 16)];
+                const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (kb + 4 * j < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[j], ap[kb + 4 * j], dmv, 0, 0, 0);
+                for (int j = 0; j < 8; ++j)
+                    if (kb + 4 * j < nAp) dmv = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[j], ap[kb + 4 * j], dmv, 0, 0, 0);
+            }
         }
         if (xl < txe && lc < tye) {
             const size_t q = (size_t)(y0 + lc) * R + (x0 + xl);
@@ -657,10 +655,10 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (a.pa.update_atm) atm[r] = sup[tt][r] * a.atm_scale;
-                const bool in = (a.ablate & 16) ? true : pup[tt][r];
+                const bool in = pup[tt][r];
                 const float res = in ? (atm[r] + dmv[r]) : 0.f;
                 phi[r] = res * a.src_scale;
-                if (in && !(a.ablate & 32)) {
+                if (in) {
                     const double da = (double)atm[r], dr = (double)res;
                     s_atm += da;
                     q_atm += da * da;
@@ -669,7 +667,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
                 }
             }
             if (a.pa.update_atm && a.pa.store_atm) *reinterpret_cast<f32x4*>(a.pb.opd_atm + pix0 + q) = atm;
-            if (a.pa.store_phase && !(a.ablate & 8)) *reinterpret_cast<f32x4*>(a.pb.phase + pix0 + q) = phi;
+            if (a.pa.store_phase) *reinterpret_cast<f32x4*>(a.pb.phase + pix0 + q) = phi;
         }
     }
     }
@@ -694,9 +692,9 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 }
 
 template <typename T>
-int launch_phase_mfma(const KArgs<T>&, int, hipStream_t) { return -1; }
+int launch_phase_mfma(const KArgs<T>&, int, int, hipStream_t) { return -1; }
 template <>
-int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, hipStream_t st) {
+int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, int force_path, hipStream_t st) {
     const int nA = a.n_act, nAp = (nA + 3) & ~3, TX = kTXmax, MW = TX + 4;
     const size_t lds = sizeof(float) * ((a.pb.s1a ? 0 : (size_t)nA * nA + (size_t)kTY * (nAp + 1)) + (size_t)(kTY + 3) * MW);
     if (a.pb.gxa == nullptr || nA > 128) return -1;
@@ -705,10 +703,10 @@ int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, hipStream_t st) {
         AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_phase_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
     dim3 grid(cdiv(a.R, TX), cdiv(a.R, kTY), n_env);
-    if (a.R % 4 == 0 && !(a.ablate & 256)) {
+    if (a.R % 4 == 0 && !(force_path & AOENV_PATH_PHASE_DWORD)) {
         // one layer: its tile of the whole 16-row band in LDS (19 x (R + 4) floats) instead of one 19 x 132 tile per chunk
         const size_t lds_band = sizeof(float) * ((a.pb.s1a ? 0 : (size_t)nA * nA + (size_t)kTY * (nAp + 1)) + (size_t)(kTY + 3) * (a.R + 4));
-        const bool band = a.pa.n_layer == 1 && a.pa.update_atm && lds_band <= 160 * 1024 && !(a.ablate & 512);
+        const bool band = a.pa.n_layer == 1 && a.pa.update_atm && lds_band <= 160 * 1024 && !(force_path & AOENV_PATH_GENERIC);
         const size_t l4 = band ? lds_band : lds;
         const int nq = a.pb.ga_stride / 4;
         void (*kern)(const KArgs<float>);
@@ -850,7 +848,6 @@ KArgs<T> make_phase_kargs(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int R,
     a.n_valid_act = n_valid_act;
     a.tx = phase_tx(R, n_act, sizeof(T));
     a.rp = cdiv(R, kTXmax) * kTXmax;
-    a.ablate = 0;
     a.atm_scale = (T)(atm_wavelength / 2 / 3.14159265358979323846);
     a.src_scale = (T)(6.283185307179586476925286766559 / src_wavelength);
     return a;
@@ -860,14 +857,13 @@ template KArgs<double> make_phase_kargs<double>(const PhaseArgs&, const PhaseBuf
 
 template <typename T>
 int launch_phase(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int n_env, int R, int n_act, int n_valid_act,
-                 double atm_wavelength, double src_wavelength, int use_mfma, hipStream_t st) {
+                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st) {
     KArgs<T> a = make_phase_kargs<T>(pa, pb, R, n_act, n_valid_act, atm_wavelength, src_wavelength);
-    a.ablate = use_mfma >> 8;                      // diagnostic builds only (bench of kernel sections)
-    if ((use_mfma & 1) && sizeof(T) == 4 && pb.dm_opd == nullptr) {
+    if (use_mfma && sizeof(T) == 4 && pb.dm_opd == nullptr) {
         // the MFMA kernel tiles with TX = 128 whatever R is (phase_tiles() is the same count for R <= 128 and
         // for R a multiple of 128; otherwise fall through to the generic kernel)
         if (cdiv(R, kTXmax) == cdiv(R, a.tx)) {
-            const int rc = launch_phase_mfma<T>(a, n_env, st);
+            const int rc = launch_phase_mfma<T>(a, n_env, force_path, st);
             if (rc >= 0) return rc;
         }
     }
@@ -883,9 +879,9 @@ int launch_phase(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int n_env, int 
     return 0;
 }
 
-template int launch_phase<float>(const PhaseArgs&, const PhaseBuffers<float>&, int, int, int, int, double, double, int,
+template int launch_phase<float>(const PhaseArgs&, const PhaseBuffers<float>&, int, int, int, int, double, double, bool, int,
                                  hipStream_t);
-template int launch_phase<double>(const PhaseArgs&, const PhaseBuffers<double>&, int, int, int, int, double, double,
+template int launch_phase<double>(const PhaseArgs&, const PhaseBuffers<double>&, int, int, int, int, double, double, bool,
                                   int, hipStream_t);
 
 }  // namespace ao

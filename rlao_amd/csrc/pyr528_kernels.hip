@@ -27,32 +27,6 @@
 namespace ao {
 
 using f528::v2;
-// diagnostic build (-DAO_PYR_STAMPS, scripts/diag_pyr_stamps.py): s_memtime per wave at the phases of the column pass
-#ifdef AO_PYR_STAMPS
-__device__ unsigned long long g_pstamps[32 * 40 * 6 * 8];
-__device__ unsigned long long g_prt[32 * 40 * 3];               // s_memrealtime (100 MHz) at the start and the end of wave 0
-#define AO_PSTAMP(i) do { if ((threadIdx.x & 63) == 0 && blockIdx.y == 0 && blockIdx.z >= 500 && blockIdx.z < 532) \
-    g_pstamps[(((blockIdx.z - 500) * 40 + blockIdx.x) * 6 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define AO_PRT(i) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z >= 500 && blockIdx.z < 532) \
-    g_prt[((blockIdx.z - 500) * 40 + blockIdx.x) * 3 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define AO_PHW() do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z >= 500 && blockIdx.z < 532) \
-    g_prt[((blockIdx.z - 500) * 40 + blockIdx.x) * 3 + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492); } while (0)
-extern "C" int aoenv_debug_pstamps(unsigned long long* h_out) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_pstamps), sizeof(unsigned long long) * 32 * 40 * 6 * 8) == hipSuccess ? 0 : 1;
-}
-extern "C" int aoenv_debug_prt(unsigned long long* h_out) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_prt), sizeof(unsigned long long) * 32 * 40 * 3) == hipSuccess ? 0 : 1;
-}
-#else
-#define AO_PSTAMP(i) do { } while (0)
-#define AO_PRT(i) do { } while (0)
-#define AO_PHW() do { } while (0)
-#endif
-#ifdef AO_PYR_STAMPS
-}  // namespace ao
-extern "C" int aoenv_debug_pyr_occupancy(int* out3);
-namespace ao {
-#endif
 // Geometry of a factor pair: N = N1 x N2; "role A" lanes (sequence, n2 or m1 < N2) hold the N1-point factor, "role B" lanes
 // (sequence, k1 < N1) the N2-point factor.  N2 is even and N / 2 = N1 (N2 / 2): the fftshift is k2 -> k2 + N2 / 2.
 template <int N1_, int N2_>
@@ -77,7 +51,7 @@ using F288 = Fac<16, 18>;
 // the workgroups spread evenly over the 4 SIMDs) and pads the kernel's register allocation up to what that occupancy allows
 // (.amdhsa_next_free_vgpr 129 for 90-118 registers in use).  A workgroup of 3 or 6 waves does not spread evenly -- the column pass
 // puts 2, 2, 1, 1 waves on the SIMDs -- so a second workgroup needs a fourth slot on two of them, and with 136 registers per lane
-// allocated a SIMD holds three: one workgroup per CU instead of two (seen in the per-CU intervals of scripts/diag_pyr_stamps.py;
+// allocated a SIMD holds three: one workgroup per CU instead of two (seen in the per-CU intervals of a stamp build, DESIGN.md 4.3;
 // scripts/ubench/lds_occupancy.hip shows the LDS itself admits floor(160 / KB)).
 
 // w_N^(k1 n2), k1 < N1, n2 < N2, from the N-entry table of the env (k1 n2 < N), in two steps: the loads are issued at the top of a
@@ -224,9 +198,6 @@ __global__ void __launch_bounds__(F::LANES_C, 4) k_pyr528_cols(const PyrArgs<flo
     v2* ex = reinterpret_cast<v2*>(lds_raw);                      // [N2 * SF = N1 * SI = 16 N]
     v2* tws = ex + N2 * SF;                                       // [N1 * TWS]
     const int tid = threadIdx.x, c = tid & 15, j = tid >> 4, R = a.R, off = a.off;
-    AO_PSTAMP(0);
-    AO_PRT(0);
-    AO_PHW();
     TwsRegs<F, F::LANES_C> twr;
     tws_issue(twr, a.tw, tid);
     // blockIdx.x % 8 is the XCD (workgroups go round-robin over the 8 XCDs): XCD x takes the blocks PER_XCD x .. of every env (528: 4)
@@ -235,7 +206,7 @@ __global__ void __launch_bounds__(F::LANES_C, 4) k_pyr528_cols(const PyrArgs<flo
     // streaming, and misses.)
     const int e = blockIdx.z, th = blockIdx.y, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     int kx0;
-    if (a.generic_fft & 1024) {                                   // diagnostic: blocks dealt round-robin
+    if (a.force_path & AOENV_PATH_PYR_ROUND_ROBIN) {              // blocks dealt round-robin
         if ((int)blockIdx.x >= NBLK) return;
         kx0 = blockIdx.x * CB;
     } else if (slot < PER_XCD) {
@@ -277,9 +248,7 @@ __global__ void __launch_bounds__(F::LANES_C, 4) k_pyr528_cols(const PyrArgs<flo
 #pragma unroll
         for (int k1 = 0; k1 < N1; ++k1) ex[j * SF + k1 * CB + c] = v[k1];
     }
-    AO_PSTAMP(1);
     __syncthreads();
-    AO_PSTAMP(2);
     v2 g[N2];
     if (j < N1) {
         v2 m[N2];                                                 // (requested before the first barrier they were 50 us slower: 44 registers)
@@ -298,25 +267,19 @@ __global__ void __launch_bounds__(F::LANES_C, 4) k_pyr528_cols(const PyrArgs<flo
 #pragma unroll
         for (int m1 = 1; m1 < N2; ++m1) g[m1] = f528::cmul_tw<true>(g[m1], tws[j * F::TWS + m1]);
     }
-    AO_PSTAMP(3);
     __syncthreads();                                              // every lane has its forward values
-    AO_PSTAMP(4);
     if (j < N1) {
 #pragma unroll
         for (int m1 = 0; m1 < N2; ++m1) ex[j * SI + m1 * CB + c] = g[m1];
     }
     __syncthreads();
-    AO_PSTAMP(5);
     if (j < N2) {
 #pragma unroll
         for (int k1 = 0; k1 < N1; ++k1) v[k1] = ex[k1 * SI + j * CB + c];
         f528::dft_len<N1, true>(v);
-        AO_PSTAMP(6);
 #pragma unroll
         for (int m2 = 0; m2 < N1; ++m2) t2[oj + (unsigned)(N2 * N * m2)] = v[m2];
     }
-    AO_PSTAMP(7);
-    AO_PRT(1);
 }
 
 // ---- P3: grid = (cam / G, E): G camera rows = G nb rows of T2 per modulation point, in batches of SEQS sequences -------------------
@@ -421,23 +384,10 @@ __global__ void __launch_bounds__(F::lanes(SEQS), 4) k_pyr528_rows_inv(const Pyr
     }
 }
 
-#ifdef AO_PYR_STAMPS
-}  // namespace ao
-extern "C" int aoenv_debug_pyr_occupancy(int* out3) {            // resident workgroups per CU of the three passes (runtime's answer)
-    using namespace ao;
-    int r = 0;
-    r |= hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_pyr528_rows<F528, 8>, F528::lanes(8), F528::lds_rows(8)) != hipSuccess;
-    r |= hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_pyr528_cols<F528, false, 6, 12>, F528::LANES_C, F528::lds_cols()) != hipSuccess;
-    r |= hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[2], k_pyr528_rows_inv<F528, 8, 4>, F528::lanes(8), F528::lds_rows_inv(8)) != hipSuccess;
-    return r;
-}
-namespace ao {
-#endif
-
 // 0: this geometry is not covered (the caller runs the Stockham passes of pyr_kernels.hip)
 int pyramid528_supported(const PyrArgs<float>& a) {
     return (a.N == F528::N || a.N == F288::N) && a.R <= a.N && a.off >= 0 && a.off + a.R <= a.N && a.cam > 0 && a.N % a.cam == 0 &&
-           !(a.generic_fft & 512);
+           !(a.force_path & AOENV_PATH_GENERIC);
 }
 
 // (dynamic LDS beyond the 64 KiB a kernel may use without asking)
@@ -462,7 +412,7 @@ static int launch_fac(PyrArgs<float> a, int n_theta, int chunk, hipStream_t st) 
         a.seq_per_block = F::N2 * (n1_hi - n1_lo + 1);               // field columns per row that P1 evaluates
         a.magic_seq = fft_magic((unsigned)a.seq_per_block);
         hipLaunchKernelGGL((k_pyr528_rows<F, SEQS1>), dim3(cdiv(R, SEQS1), a.n_theta_chunk, a.n_env), dim3(F::lanes(SEQS1)), F::lds_rows(SEQS1), st, a);
-        const dim3 g2((a.generic_fft & 1024) ? cdiv(F::N / F::CB, 8) * 8 : 8 * slots, a.n_theta_chunk, a.n_env);
+        const dim3 g2((a.force_path & AOENV_PATH_PYR_ROUND_ROBIN) ? cdiv(F::N / F::CB, 8) * 8 : 8 * slots, a.n_theta_chunk, a.n_env);
         if (a.centering) {
             if (spec) AO_TRY(launch_lds(k_pyr528_cols<F, false, LO, CNT>, g2, F::LANES_C, F::lds_cols(), st, a));
             else AO_TRY(launch_lds(k_pyr528_cols<F, false, 0, F::N1>, g2, F::LANES_C, F::lds_cols(), st, a));

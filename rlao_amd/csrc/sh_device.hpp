@@ -3,10 +3,6 @@
 #pragma once
 #include "common.hpp"
 
-#ifndef AO_STAMP
-#define AO_STAMP(i) do { } while (0)
-#endif
-
 namespace ao {
 
 // Workgroup barrier for hand-offs through LDS only.  __syncthreads() is "s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier": it
@@ -241,7 +237,6 @@ __device__ inline void tail_from_slopes(const T* sl, T* img_s, double* red, cons
         }
     }
     lds_barrier();
-    AO_STAMP(19);
     // ---- o = -M2C t, integrator, image ------------------------------------------------------------------------------------
     // 4 lanes per group of 4 consecutive actuators: lane part p takes the modes q = p, p + 4, ... with 16-byte loads along
     // the actuator axis, all of them in flight at once (one memory round trip), then two shuffles fold the 4 partial sums.
@@ -295,13 +290,11 @@ __device__ inline void tail_from_slopes(const T* sl, T* img_s, double* red, cons
         }
     }
     lds_barrier();
-    AO_STAMP(20);
     T* ob = f.obs + (size_t)e * img;
     for (int q = tid; q < img; q += blockDim.x) ob[q] = img_s[q];
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_down(ss, off);
     if ((tid & (kWave - 1)) == 0) red[tid / kWave] = ss;
     lds_barrier();
-    AO_STAMP(21);
     if (tid == 0) {
         double tot = 0;
         for (int q = 0; q < (int)blockDim.x / kWave; ++q) tot += red[q];

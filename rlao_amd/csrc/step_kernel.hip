@@ -20,23 +20,7 @@
 //
 // Arithmetic is the same as in the separate kernels (phase_kernel.hip, sh_kernels.hip); only summation orders of the
 // centroid and of the telemetry differ (float32 / float64 rounding level).  No atomics: bitwise reproducible.
-// diagnostic ablation of the camera block (scripts/diag_cam_ablate.sh): -DAO_CAM_ABLATE=<bit mask>; wrong frames, timing only
-#ifdef AO_CAM_ABLATE
-#define AO_ABL(bit) (((AO_CAM_ABLATE) >> (bit)) & 1)
-#else
-#define AO_ABL(bit) 0
-#endif
 #include "common.hpp"
-
-// Diagnostic build only (-DAO_STEP_STAMPS): wave 0 of each workgroup stamps s_memtime at the stage boundaries.
-#ifdef AO_STEP_STAMPS
-namespace ao { __device__ unsigned long long g_stamps[1024 * 32]; __device__ unsigned long long g_wstamps[256 * 16 * 8]; }
-#define AO_WSTAMP(i) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) ::ao::g_wstamps[(blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define AO_STAMP(i) do { if (tid == 0 && e < 1024) ::ao::g_stamps[e * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define AO_STAMP(i) do { } while (0)
-#define AO_WSTAMP(i) do { } while (0)
-#endif
 
 #include "sh_device.hpp"
 #include "detector.hpp"
@@ -131,8 +115,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     const size_t pix0 = (size_t)e * R * R;
     const int n_sub = a.n_subap, n_valid = a.n_valid;
 
-    AO_STAMP(0);
-    AO_WSTAMP(0);
     // ---- prologue: every global load of the prologue is issued before the first barrier ------------------------------------
     // (the barriers are compiler fences for memory operations: a load written after one is issued after it)
     // A operands of the DM product, Gx[x][k = lane >> 4 + 4 step]: the lane's two column tiles are the same in every
@@ -165,7 +147,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     if (tid < n_sub * n_sub) slot_s[tid] = slot_v;
     for (int i = tid + 1024; i < n_sub * n_sub; i += 1024) slot_s[i] = a.slot_of[i];
     lds_barrier();
-    AO_STAMP(24);
     if (has_act) cimg[act_px] = act_c;
     float breg[2][KS];
 #pragma unroll
@@ -178,7 +159,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
 
     // ---- s1[y][ix] = sum_iy gy[y][iy] C[iy][ix] for every row, on the matrix cores: 8 x 2 tiles of 16 x 16, one per wave ---
     lds_barrier();                                             // cimg complete
-    AO_STAMP(25);
     {
         const int ix = 16 * ct + lc;
         float av[KS], bv[KS];
@@ -201,7 +181,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         }
     }
 
-    AO_STAMP(26);
     // ---- deferred ring scatter: map_full[outerMask] = X of a layer that crossed a pixel this step ----------------------------
     // The ring values are the fixed-order sum of the GEMM's split-K slabs, written through the torus origin.  This
     // workgroup is the only reader of this env's map in this launch, and its vector L1 holds no line of it yet (no load of
@@ -243,7 +222,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         }
     }
 
-    AO_STAMP(27);
     // ---- range of every layer's screen (the warp clips to it): read back, or recomputed here after a ring extrusion -------
     __shared__ float lohi[kMaxLayer][2];
     __shared__ float red_lo[16], red_hi[16];
@@ -300,8 +278,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         const int tye = min(PR, R - y0);
         const int yl = 16 * band + lc, y = y0 + yl;              // the lane's row
         const bool row_ok = yl < tye;
-        if (pass == 0) { AO_WSTAMP(1); lds_barrier(); AO_WSTAMP(2); }   // s1 and the screen ranges complete
-        AO_STAMP(1 + 6 * pass);
+        if (pass == 0) lds_barrier();                            // s1 and the screen ranges complete
         // pupil + WFS amplitude of the lane's 2 x 4 pixels (one table: amplitude, or -1 outside the pupil), long before use
         f32x4s apv[2];
 #pragma unroll
@@ -325,7 +302,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
             // another's arithmetic.  LDS operations of one wave execute in order: a compiler fence is all that is needed
             // between the tile writes and the reads of other lanes' data.
             asm volatile("" ::: "memory");
-            AO_STAMP(3 + 6 * pass);
             {
                 // tile element (r, c) = map[r0 + 16 band + r][c0 + 32 cg + c], staged as rows of WC4 float4
                 const int rw0 = r0 + 16 * band, cw0 = c0 + 32 * cg;
@@ -361,7 +337,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                 }
             }
             asm volatile("" ::: "memory");
-            AO_STAMP(4 + 6 * pass);
             const float wx0 = (float)tp.wx[0], wx1 = (float)tp.wx[1], wx2 = (float)tp.wx[2], wx3 = (float)tp.wx[3];
             const float wy0 = (float)tp.wy[0], wy1 = (float)tp.wy[1], wy2 = (float)tp.wy[2], wy3 = (float)tp.wy[3];
             const float lo = lohi[l][0], hi = lohi[l][1], wl = (float)tp.weight;
@@ -388,7 +363,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                 }
             }
         }
-        AO_STAMP(5 + 6 * pass);
 
         // ---- DM surface on the matrix cores, pupil, phase store, E0 -> LDS, telemetry sums -----------------------------
         const int iy = y / 6, by = y - 6 * iy;
@@ -436,8 +410,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
             }
         }
     }
-    AO_STAMP(13);
-    AO_WSTAMP(3);
     // telemetry: waves in a fixed order
     s_atm = wave_sum_f64(s_atm);
     q_atm = wave_sum_f64(q_atm);
@@ -450,8 +422,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         red[3][w] = q_res;
     }
     lds_barrier();                                             // E0 complete, red complete, cimg / s1 / layer tiles dead
-    AO_STAMP(14);
-    AO_WSTAMP(4);
     // the camera's tables on their way into LDS (no registers, nobody waits): they land while the spots are computed
     const bool cam_photons = a.det.active && a.det.photon_noise;
     if (cam_photons) alias_table_to_lds(a.pa.tab, a.pa.words, reinterpret_cast<uint32_t*>(lds + L.tab), w, 16, lane);
@@ -488,18 +458,14 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         li = kk / n_sub;
         lj = kk - li * n_sub;
     }
-    AO_STAMP(22);
     if (a.det.active) {
         // ---- self*self.cam: the camera on the lane's 12 pixels (detector.hpp, "Stream layout") --------------------------------
         // (camera_sh6.hpp: shared with the stand-alone camera kernel)
         f32x16s pxv = camera_pack(Ia, Ib);
-        AO_STAMP(23);
         if (cam_photons) {                                        // this wave's share of the tables has landed; then everybody's
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            AO_STAMP(6);
             lds_barrier();
         }
-        AO_STAMP(8);
         camera_sh6_lane(pxv, ok, (uint32_t)((li * 6) * R + lj * 6 + q3), R, (uint32_t)e, a.det, tab_s, a.pa.lmax);
         camera_unpack(pxv, Ia, Ib);
     }
@@ -513,7 +479,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
             mx = Ib[u] > mx ? Ib[u] : mx;
         }
     }
-    AO_STAMP(15);
     if (a.det.active && (a.det.dark_e > 0.f || a.det.readout_noise != 0.f)) {
         // the camera also reads out the pixels of the lenslets that are not valid (no light): dark + read-out noise, ADC
         const float rtab = recip_table_lane();
@@ -563,9 +528,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         mx = o > mx ? o : mx;
     }
     if (lane == 0) red_mx[w] = mx;
-    AO_WSTAMP(5);
     lds_barrier();
-    AO_STAMP(16);
     mx = red_mx[0];
 #pragma unroll
     for (int q = 1; q < 16; ++q) mx = red_mx[q] > mx ? red_mx[q] : mx;
@@ -601,7 +564,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         }
     }
     lds_barrier();
-    AO_STAMP(17);
 
     // ---- stage C ------------------------------------------------------------------------------------------------------------
     // Same arithmetic as tail_from_slopes (sh_device.hpp), with every operand that does not depend on the slopes already
@@ -638,7 +600,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         for (int j = 0; j < 13; ++j) cv[j] = f32x4s{0.f, 0.f, 0.f, 0.f};
     }
     lds_barrier();
-    AO_STAMP(19);
     double ss = 0.0;
     {
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -669,7 +630,6 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         }
     }
     lds_barrier();
-    AO_STAMP(20);
     {
         float* ob = a.fa.obs + (size_t)e * img;
         for (int q = tid; q < img; q += 1024) ob[q] = img_s[q];
@@ -677,25 +637,13 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     ss = wave_sum_f64(ss);
     if (lane == 0) red_tail[w] = ss;
     lds_barrier();
-    AO_STAMP(21);
     if (tid == 0) {
         double tot = 0;
         for (int q = 0; q < 16; ++q) tot += red_tail[q];
         if (a.fa.reward) a.fa.reward[e] = (float)(-sqrt(tot));
         if (a.fa.ret && a.fa.do_integrate) a.fa.ret[e] += (float)(-sqrt(tot));
     }
-    AO_STAMP(18);
-    AO_WSTAMP(6);
 }
-
-#ifdef AO_STEP_STAMPS
-extern "C" int aoenv_debug_wstamps(unsigned long long* h_out) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_wstamps), sizeof(unsigned long long) * 256 * 16 * 8) == hipSuccess ? 0 : 1;
-}
-extern "C" int aoenv_debug_stamps(unsigned long long* h_out, int n_env) {
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 32 * (size_t)n_env) == hipSuccess ? 0 : 1;
-}
-#endif
 
 int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes) {
     if (R % n_subap || R / n_subap != fast6::P) return 0;

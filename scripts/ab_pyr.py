@@ -1,5 +1,5 @@
 """In-process A/B of a config's measurement (or, with AB_MODE=step in the environment, of its closed-loop integrator step) under
-diagnostic options (aoenv_set_option 99), interleaved rounds:
+values of AOENV_OPT_FORCE_PATH (0 or a combination of AOENV_PATH_* bits, e.g. 512 = AOENV_PATH_GENERIC), interleaved rounds:
     python scripts/ab_pyr.py [C3|C3M|C4|C5] opt0 opt1 ..."""
 import os, statistics, sys
 import torch
@@ -16,7 +16,7 @@ bench.start_episode(env)
 res = {o: [] for o in opts}
 for rnd in range(4):
     for o in opts:
-        L.check(env._shard.lib.aoenv_set_option(env._shard.h, 99, o))
+        L.check(env._shard.lib.aoenv_set_option(env._shard.h, L.OPT_FORCE_PATH, o))
         step = os.environ.get("AB_MODE") == "step"
         env.measure()
         torch.cuda.synchronize()

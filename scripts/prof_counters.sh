@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3: kernel trace, then issue / wait / LDS / cache counter passes of one BASELINE config's shard (scripts/prof_config.py);
-# AOENV_DEBUG_OPTION in the environment selects a diagnostic path.   usage (via gpurun, repo root): bash scripts/prof_counters.sh C3 tag
+# AOENV_DEBUG_OPTION in the environment is a value of AOENV_OPT_FORCE_PATH (AOENV_PATH_* bits).   usage (repo root): bash scripts/prof_counters.sh C3 tag
 set -o pipefail
 C=$1; TAG=${2:-cnt}
 # KERNEL_RE in the environment keeps the counter files small (a config with a long calibration writes > 64 MiB otherwise)

@@ -238,6 +238,8 @@ def test_c_abi_reports_errors():
     assert b"expected" in lib.aoenv_last_error()
     assert lib.aoenv_upload(h, 999, bad.ctypes.data_as(C.c_void_p), bad.nbytes) != 0
     assert lib.aoenv_set_option(h, 12345, 1) != 0
+    assert lib.aoenv_set_option(h, L.OPT_FORCE_PATH, L.PATH_GENERIC | 1) != 0        # a bit that is not an AOENV_PATH_*
+    assert b"AOENV_PATH" in lib.aoenv_last_error()
     assert lib.aoenv_download(h, L.B_SIGNAL, bad.ctypes.data_as(C.c_void_p), 8, None) != 0
     idx = np.full(env._atm_tables.n_inner, 10 ** 6, dtype=np.int32)
     assert lib.aoenv_upload(h, L.C_INNER_IDX, idx.ctypes.data_as(C.c_void_p), idx.nbytes) != 0
@@ -555,7 +557,7 @@ def test_tensors_handed_out_by_step_survive_the_next_episode():
 @pytest.mark.parametrize("coefs_image", [0, 1])
 def test_phase_kernel_with_16_byte_accesses_is_bit_identical(coefs_image):
     """k_phase_mfma4 (lane = one row, four consecutive pixels: float4 tile loads, taps, pupil flags and phase stores) against
-    k_phase_mfma (dword accesses; forced through the diagnostic switch 99 = 256): the same taps in the same order and the same k order
+    k_phase_mfma (dword accesses; forced with AOENV_PATH_PHASE_DWORD): the same taps in the same order and the same k order
     of the DM product, so every output bit agrees -- three layers with winds that move the torus origins (float4s that straddle the
     wrap), both forms of the Gy C operand (computed in the kernel / handed over by k_dm_rows)."""
     import torch
@@ -570,7 +572,7 @@ def test_phase_kernel_with_16_byte_accesses_is_bit_identical(coefs_image):
         L.check(env._shard.lib.aoenv_set_option(env._shard.h, L.OPT_FUSED_STEP, 0))
         L.check(env._shard.lib.aoenv_set_option(env._shard.h, L.OPT_COEFS_IMAGE, coefs_image))
         if old:
-            L.check(env._shard.lib.aoenv_set_option(env._shard.h, 99, 256))
+            L.check(env._shard.lib.aoenv_set_option(env._shard.h, L.OPT_FORCE_PATH, L.PATH_PHASE_DWORD))
         rec = _run(env, 12, 5, gain=0.4)
         phase = env._shard.download(L.B_PHASE, (3, env.R, env.R))
         opd = env._shard.download(L.B_OPD_ATM, (3, env.R, env.R))

@@ -310,7 +310,7 @@ def test_c2_geometry_1000_envs_ragged_shard():
                                                             (29, 8, False, 0.0),
                                                             (20, 6, True, 0.0), (20, 6, False, 3.0), (5, 16, False, 2.0), (8, 12, True, 0.0)])
 def test_c3_pyramid_528_register_passes_match_the_stockham_passes(n_sub, ppx, centering, modulation):
-    """nRes = 528 in float32 runs the 24 x 22 register-resident transform (pyr528_kernels.hip); diagnostic option 99 bit 512
+    """nRes = 528 in float32 runs the 24 x 22 register-resident transform (pyr528_kernels.hip); AOENV_PATH_GENERIC
     puts the same shard back on the Stockham passes of pyr_kernels.hip (what float64 and every other length run, pinned to the
     reference by the golden replays).  Same field, same mask, different order of the float32 butterflies: frames agree to float32
     rounding of the brightest pixel.  Geometries: BASELINE configs[2] (R = 240: the specialised column pass, 4 camera rows per
@@ -331,7 +331,7 @@ def test_c3_pyramid_528_register_passes_match_the_stockham_passes(n_sub, ppx, ce
         env.dm.coefs = 0
         frames, signals = [], []
         for generic in (0, 512, 0, 1024):
-            L.check(env._shard.lib.aoenv_set_option(env._shard.h, 99, generic))
+            L.check(env._shard.lib.aoenv_set_option(env._shard.h, L.OPT_FORCE_PATH, generic))
             env.measure()
             frames.append(env._shard.download(L.B_FRAME, (4, env.cam_res, env.cam_res)).astype(np.float64))
             signals.append(env._shard.download(L.B_SIGNAL, (4, env.nSignal)).astype(np.float64))
