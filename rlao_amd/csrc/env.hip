@@ -29,6 +29,36 @@ struct LayerClock {
     double buff[2] = {0, 0};    // sub-pixel accumulator            OOPAO/Atmosphere.py:392-404
 };
 
+// Ring pipeline (float32 fused path, shared clock): the operand [Z | xi] of a layer's NEXT pixel crossing is put together while
+// the current crossing is being served -- xi by extra workgroups of the ring GEMM's launch (the stream position only moves at
+// crossings), Z by the fused step kernel right after it has written the ring (the screen does not change until the next
+// crossing) -- so a crossing step launches the GEMM and nothing else in front of the step kernel: k_ring_prepare (9 us, the
+// Gaussian draw) leaves the critical path.  [An earlier form ran prepare + GEMM one crossing ahead on a second stream: with one
+// 1024-lane workgroup resident on every CU the side-stream kernels found no free CU and time-sliced with the step kernel: slower.]
+struct RingAhead { bool valid = false; int sx = 0, sy = 0, buf = 0; };   // zx_pipe[buf][l] holds [Z | xi] for a crossing in direction (sx, sy); mt_alt the stream after it
+
+// One atmosphere layer of a shard (AoEnv::layer).
+struct Layer {
+    int N = 0, S = 0, nin = 0, nout = 0, K = 0;   // grid: fov != 0 puts a layer at altitude h on one of its own (OOPAO/Atmosphere.py:216-218)
+    size_t scr_off = 0;                     // element offset of the layer's [E][S^2] block in AoEnv::screen
+    void* ab = nullptr;                     // [nout][K] ring operators [A | B] (layers of a uniform shard share the ring tables)
+    int* inner_idx = nullptr;
+    int* outer_idx = nullptr;
+    bool have_ab = false, have_in = false, have_out = false;
+    double weight = 0;
+    LayerClock clk;                         // shared clock
+    int org[2] = {0, 0};                    // torus origin (oy, ox): logical (r, c) at ((r + oy) % S, (c + ox) % S)
+    uint32_t* mt_cur = nullptr;             // ring stream ([E][624] MT19937 states, [E] positions): committed copy ...
+    int* pos_cur = nullptr;
+    uint32_t* mt_alt = nullptr;             // ... and the one a look-ahead writes (swapped in when the look-ahead is consumed)
+    int* pos_alt = nullptr;
+    int ring_pending = 0;                   // > 0: split count of a ring extrusion whose scatter the next fused step kernel will do
+    const void* ring_src = nullptr;         // its slabs
+    RingAhead ahead;
+    bool gather_next = false;               // the next fused step kernel is to gather Z into zx_pipe[ahead.buf][l]
+    bool minmax_dirty = false;              // the min / max table is stale (ring extruded without the min / max pass)
+};
+
 }  // namespace ao
 
 using namespace ao;
@@ -37,22 +67,13 @@ struct AoEnv {
     AoCfg c{};
     int device = 0;
     size_t esz = 4;
-    int R = 0, N = 0, S = 0, A = 0, nAct = 0, E = 0, L = 0, nin = 0, nout = 0, K = 0, nSig = 0, nSub = 0, nVal = 0;
+    int R = 0, A = 0, nAct = 0, E = 0, L = 0, nSig = 0, nSub = 0, nVal = 0;
     int p = 0, n = 0, n_pupil = 0;
-    // per-layer screen grids (fov != 0: a layer at altitude h lives on a grid of its own, OOPAO/Atmosphere.py:216-218); N, S, nin,
-    // nout, K above are layer 0's (every layer's when `uniform`: the only case the fused step kernel takes)
-    int Nl[kMaxLayer] = {0}, Sl[kMaxLayer] = {0}, ninl[kMaxLayer] = {0}, noutl[kMaxLayer] = {0}, Kl[kMaxLayer] = {0};
-    size_t scr_off[kMaxLayer + 1] = {0};     // element offset of layer l's [E][S_l^2] block in `screen`
+    Layer layer[kMaxLayer];                  // layer[0].N / S are set with no atmosphere too (the phase kernels' footprint)
+    size_t scr_elems = 0;                    // elements of `screen`
     int Kmax = 0, noutmax = 0, Smax = 0;
-    bool uniform = true;
-    void* ab_l[kMaxLayer] = {nullptr};       // [nout_l][K_l] ring operators [A | B] of layer l
-    int* inner_idx_l[kMaxLayer] = {nullptr};
-    int* outer_idx_l[kMaxLayer] = {nullptr};
-    bool have_ab[kMaxLayer] = {false}, have_in[kMaxLayer] = {false}, have_out[kMaxLayer] = {false};
+    bool uniform = true;                     // every layer on one grid
     int last_zx_layer = 0;
-    LayerClock clk[kMaxLayer];
-    int org[kMaxLayer][2] = {{0, 0}};        // torus origin (oy, ox) of every layer: logical (r, c) at ((r + oy) % S, (c + ox) % S)
-    int ring_pending[kMaxLayer] = {0};       // > 0: split count of a ring extrusion whose scatter the next fused step kernel will do
     // per-env clocks (aoenv_set_wind_env): every env its own wind vector per layer; clocks, origins and taps live on the device
     bool per_env_wind = false;
     EnvClock* env_clk[2] = {nullptr, nullptr};   // [L][E] each: current / next (k_ring_prepare_env reads one, writes the other)
@@ -60,37 +81,16 @@ struct AoEnv {
     LayerTaps* env_taps = nullptr;           // [L][E] taps of the current step
     bool use_coefs_img = false;              // aoenv_set_option(AOENV_OPT_COEFS_IMAGE); always on above 1024 actuators
     bool defer_ring = true;                  // aoenv_set_option(AOENV_OPT_DEFER_RING)
-    bool minmax_dirty[kMaxLayer] = {false};  // the layer's min / max table is stale (ring extruded without the min / max pass)
     bool have[AOENV_C_COUNT] = {false};
     double units = 1.0;
     // device memory (element type = dtype unless noted)
-    void* screen[1] = {nullptr};            // [L][E][S*S], every screen a torus (see atm_kernels.hip)
+    void* screen = nullptr;                 // [L][E][S*S], every screen a torus (see atm_kernels.hip)
     void* minmax = nullptr;                 // [L][E][2]
-    uint32_t* mt_state = nullptr;           // [2][L][E][624]: per layer one committed copy and one the ring look-ahead writes
-    int* mt_pos = nullptr;                  // [2][L][E]
-    uint32_t* mt_cur[kMaxLayer] = {nullptr};   // committed MT19937 state of every layer's ring stream ...
-    int* pos_cur[kMaxLayer] = {nullptr};
-    uint32_t* mt_alt[kMaxLayer] = {nullptr};   // ... and the other copy (swapped in when a look-ahead is consumed)
-    int* pos_alt[kMaxLayer] = {nullptr};
-    // Ring pipeline (float32 fused path, shared clock): the operand [Z | xi] of a layer's NEXT pixel crossing is put together while
-    // the current crossing is being served -- xi by extra workgroups of the ring GEMM's launch (the stream position only moves at
-    // crossings), Z by the fused step kernel right after it has written the ring (the screen does not change until the next
-    // crossing) -- so a crossing step launches the GEMM and nothing else in front of the step kernel: k_ring_prepare (9 us, the
-    // Gaussian draw) leaves the critical path.  [An earlier form ran prepare + GEMM one crossing ahead on a second stream: with one
-    // 1024-lane workgroup resident on every CU the side-stream kernels found no free CU and time-sliced with the step kernel: slower.]
-    struct RingAhead { bool valid = false; int sx = 0, sy = 0, buf = 0; };   // zx_pipe[buf][l] holds [Z | xi] for a crossing in direction (sx, sy); mt_alt[l] the stream after it
-    RingAhead ahead[kMaxLayer];
-    bool gather_next[kMaxLayer] = {false};  // the next fused step kernel is to gather Z into zx_pipe[ahead.buf][l]
     void* zx_pipe = nullptr;                // [2][L][E][K]
     const void* last_zx = nullptr;          // operand of the last ring GEMM (AOENV_B_XI)
-    const void* ring_src[kMaxLayer] = {nullptr};   // slabs of the pending (deferred) ring of every layer
     bool use_lookahead = true;              // aoenv_set_option(AOENV_OPT_RING_LOOKAHEAD): the ring pipeline
     void* zx = nullptr;                     // [E][K]  [Z | xi]
     void* xbuf = nullptr;                   // [splits][E][nout] split-K slabs of the ring GEMM
-    void* ab = nullptr;                     // = ab_l[0] (fused path)
-    int* inner_idx = nullptr;               // = inner_idx_l[0]
-    int* outer_idx = nullptr;
-    double layer_weight[kMaxLayer] = {0};
     void* gx = nullptr;
     void* gy = nullptr;
     void* gxt = nullptr;                    // [nActPad4][Rpad128] transpose of gx, zero padded
@@ -165,9 +165,7 @@ struct AoEnv {
     std::vector<ProfEv> prof_ev;
 
     template <typename T> T* as(void* p_) const { return static_cast<T*>(p_); }
-    void* screen_ptr(int which, int l) const {
-        return static_cast<char*>(screen[which]) + scr_off[l] * esz;
-    }
+    void* screen_ptr(int l) const { return static_cast<char*>(screen) + layer[l].scr_off * esz; }
     void* minmax_ptr(int l) const { return static_cast<char*>(minmax) + (size_t)l * E * 2 * esz; }
     void* xbuf_ptr(int l) const { return static_cast<char*>(xbuf) + (size_t)l * kMaxSplits * E * noutmax * esz; }
     void* zx_pipe_ptr(int buf, int l) const { return static_cast<char*>(zx_pipe) + ((size_t)buf * L + l) * E * Kmax * esz; }
@@ -226,7 +224,6 @@ int upload_real(AoEnv* env, void* dst, const double* src, size_t n) {
 
 double sgn(double v) { return (v > 0) - (v < 0); }
 
-// Catmull-Rom tap weights of skimage's cubic_interpolation() for fractional offset x in [0, 1)
 void mt_seed(uint32_t seed, uint32_t* key) {          // numpy legacy mt19937_seed / init_genrand
     for (int pos = 0; pos < kMtN; ++pos) {
         key[pos] = seed;
@@ -266,34 +263,73 @@ int gemm_dispatch<double>(AoEnv*, const double* X, const double* W, double* C, i
     return launch_gemm_nt<double>(X, W, C, M, N, K, K, K, N, st);
 }
 
+// ---- the state changes of a layer's ring pipeline (Layer), each made in one place ---------------------------------------
 // The operand prepared for a layer's next crossing will not be used (the screens, the stream or the wind changed): nothing of it
 // was committed -- the stream copy it advanced is the alternate one -- so it is simply forgotten; the crossing draws in place.
-int drop_lookahead(AoEnv* env, int l, hipStream_t) {
-    env->ahead[l].valid = false;
-    env->gather_next[l] = false;
-    return 0;
+void forget_lookahead(Layer& y) { y.ahead.valid = false; y.gather_next = false; }
+
+// A deferred ring that is moot (the screens or the clocks it was computed for are gone): it is never scattered.
+void drop_ring(Layer& y) { y.ring_pending = 0; }
+
+// the shift of a crossing (sx, sy) on the shared clock: move the origin of the torus
+void move_origin(Layer& y, int sx, int sy) {
+    y.org[0] = ((y.org[0] - sy) % y.S + y.S) % y.S;
+    y.org[1] = ((y.org[1] - sx) % y.S + y.S) % y.S;
 }
-int drop_lookaheads(AoEnv* env, hipStream_t st) {
-    for (int l = 0; l < env->L; ++l) AO_TRY(drop_lookahead(env, l, st));
-    return 0;
+
+// The ring GEMM of a crossing of layer l ran on the operand zx and left `splits` split-K slabs in xbuf_ptr(l): the scatter is left
+// to the next fused step kernel, or to flush_ring.
+void defer_ring(AoEnv* env, int l, const void* zx, int splits) {
+    env->last_zx = zx;
+    env->last_zx_layer = l;
+    env->layer[l].ring_pending = splits;
+    env->layer[l].ring_src = env->xbuf_ptr(l);
 }
-int sync_lookaheads(AoEnv* env) { return drop_lookaheads(env, nullptr); }
+
+// The fused step kernel of this step takes the deferred rings, and gathers the Z of a look-ahead it was asked for (a look-ahead
+// whose ring is not pending has nothing to gather from: it is forgotten).
+void take_rings(AoEnv* env, StepArgs& a) {
+    for (int l = 0; l < env->L; ++l) {
+        Layer& y = env->layer[l];
+        a.ring_x[l] = y.ring_pending ? static_cast<const float*>(y.ring_src) : nullptr;
+        a.ring_splits[l] = y.ring_pending;
+        const bool g = y.gather_next && y.ring_pending && y.ahead.valid;
+        a.next_zx[l] = g ? static_cast<float*>(env->zx_pipe_ptr(y.ahead.buf, l)) : nullptr;
+        a.next_sx[l] = y.ahead.sx;
+        a.next_sy[l] = y.ahead.sy;
+        if (y.gather_next && !g) y.ahead.valid = false;
+        y.gather_next = false;
+    }
+}
+
+// ... and has written them, and recomputed and stored every layer's min / max
+void rings_written(AoEnv* env) {
+    for (int l = 0; l < env->L; ++l) { env->layer[l].ring_pending = 0; env->layer[l].minmax_dirty = false; }
+}
 
 // ---- add_row on the device (OOPAO/Atmosphere.py:301-311) for every env of the shard ---------------
-// lean = true: the ring is scattered without the min / max pass; the fused step kernel recomputes the range from the map
+// The pending ring of layer l, scattered now: through the shared origin (et = null; with_minmax: with the min / max pass), or per-env
+// clocks (et = their taps): only the envs that crossed, each through its own origin.
+template <typename T>
+int scatter_ring(AoEnv* env, int l, const LayerTaps* et, bool with_minmax, hipStream_t st) {
+    Layer& y = env->layer[l];
+    AO_PROF(env, SCATTER, st);
+    AO_TRY(launch_scatter_minmax<T>(env->as<T>(env->screen_ptr(l)), static_cast<const T*>(y.ring_src), y.outer_idx,
+                                    env->as<T>(env->minmax_ptr(l)), env->E, y.S, y.nout, y.ring_pending, y.org[0], y.org[1],
+                                    with_minmax ? 1 : 0, st, et));
+    y.ring_pending = 0;
+    return 0;
+}
+
+// A deferred ring of layer l, if any, scattered without the min / max pass (the fused step kernel recomputes the range from the
+// map); per-env clocks compute the range of the envs that crossed right away -- there is no per-env "dirty" flag on the host.
 template <typename T>
 int flush_ring(AoEnv* env, int l, hipStream_t st) {
-    if (!env->ring_pending[l]) return 0;
-    if (env->gather_next[l]) AO_TRY(drop_lookahead(env, l, st));   // (the step kernel that would have gathered the next Z is not coming)
-    AO_PROF(env, SCATTER, st);
-    // (per-env clocks: only the envs that crossed, each through its own origin, and their range right away -- there is no
-    //  per-env "dirty" flag on the host)
+    Layer& y = env->layer[l];
+    if (!y.ring_pending) return 0;
+    if (y.gather_next) forget_lookahead(y);                        // (the step kernel that would have gathered the next Z is not coming)
     const LayerTaps* et = env->per_env_wind ? env->env_taps + (size_t)l * env->E : nullptr;
-    AO_TRY(launch_scatter_minmax<T>(env->as<T>(env->screen_ptr(0, l)), static_cast<const T*>(env->ring_src[l]), env->outer_idx_l[l],
-                                    env->as<T>(env->minmax_ptr(l)), env->E, env->Sl[l], env->noutl[l], env->ring_pending[l],
-                                    env->org[l][0], env->org[l][1], et ? 1 : 0, st, et));
-    env->ring_pending[l] = 0;
-    return 0;
+    return scatter_ring<T>(env, l, et, et != nullptr, st);
 }
 template <typename T>
 int flush_rings(AoEnv* env, hipStream_t st) {
@@ -301,42 +337,33 @@ int flush_rings(AoEnv* env, hipStream_t st) {
     return 0;
 }
 
+// The ring GEMM X = [A | B] [Z | xi] of a crossing of layer l into xbuf_ptr(l).
+template <typename T>
+int ring_gemm(AoEnv* env, int l, const T* zx, int* splits, hipStream_t st) {
+    const Layer& y = env->layer[l];
+    AO_PROF(env, GEMM_RING, st);
+    return gemm_dispatch<T>(env, zx, env->as<T>(y.ab), env->as<T>(env->xbuf_ptr(l)), env->E, y.nout, y.K, splits, st);
+}
 
 // lean: no min / max pass (the fused step kernel recomputes the range from the map);  defer: not even the scatter -- the
 // fused step kernel of this step writes the ring itself (one launch less per crossing)
 template <typename T>
 int extrude(AoEnv* env, int l, int sx, int sy, bool lean, hipStream_t st, bool defer = false) {
-    AO_TRY(drop_lookahead(env, l, st));                            // computed from the screen and the stream as they were
+    Layer& y = env->layer[l];
+    forget_lookahead(y);                                           // computed from the screen and the stream as they were
     AO_TRY(flush_ring<T>(env, l, st));                             // an earlier extrusion of this layer in the same step
-    T* map = env->as<T>(env->screen_ptr(0, l));
     T* zx = env->as<T>(env->zx);
-    const int S = env->Sl[l];
-    const int oy = env->org[l][0], ox = env->org[l][1];
     {
         AO_PROF(env, SHIFT_GATHER, st);                           // Z gather + xi draw, one launch
-        AO_TRY(launch_ring_prepare<T>(map, zx, env->inner_idx_l[l], env->mt_cur[l], env->pos_cur[l], env->mt_cur[l], env->pos_cur[l], env->E, S,
-                                      env->ninl[l], env->noutl[l], env->Kl[l], sx, sy, oy, ox, st));
+        AO_TRY(launch_ring_prepare<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, env->E,
+                                      y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
     }
     int splits = 1;
-    {
-        AO_PROF(env, GEMM_RING, st);
-        AO_TRY(gemm_dispatch<T>(env, zx, env->as<T>(env->ab_l[l]), env->as<T>(env->xbuf_ptr(l)), env->E, env->noutl[l], env->Kl[l], &splits,
-                                st));
-    }
-    // the shift itself: move the origin of the torus
-    env->org[l][0] = ((oy - sy) % S + S) % S;
-    env->org[l][1] = ((ox - sx) % S + S) % S;
-    env->last_zx = zx;
-    env->last_zx_layer = l;
-    if (defer && lean) {
-        env->ring_pending[l] = splits;
-        env->ring_src[l] = env->xbuf_ptr(l);
-    } else {
-        AO_PROF(env, SCATTER, st);
-        AO_TRY(launch_scatter_minmax<T>(map, env->as<T>(env->xbuf_ptr(l)), env->outer_idx_l[l], env->as<T>(env->minmax_ptr(l)), env->E, S,
-                                        env->noutl[l], splits, env->org[l][0], env->org[l][1], lean ? 0 : 1, st));
-    }
-    env->minmax_dirty[l] = lean;
+    AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
+    move_origin(y, sx, sy);
+    defer_ring(env, l, zx, splits);
+    if (!(defer && lean)) AO_TRY(scatter_ring<T>(env, l, nullptr, !lean, st));
+    y.minmax_dirty = lean;
     return 0;
 }
 
@@ -345,9 +372,9 @@ template <typename T>
 int refresh_minmax(AoEnv* env, hipStream_t st) {
     AO_TRY(flush_rings<T>(env, st));
     for (int l = 0; l < env->L; ++l)
-        if (env->minmax_dirty[l]) {
-            AO_TRY(launch_minmax<T>(env->as<T>(env->screen_ptr(0, l)), env->as<T>(env->minmax_ptr(l)), env->E, env->Sl[l], st));
-            env->minmax_dirty[l] = false;
+        if (env->layer[l].minmax_dirty) {
+            AO_TRY(launch_minmax<T>(env->as<T>(env->screen_ptr(l)), env->as<T>(env->minmax_ptr(l)), env->E, env->layer[l].S, st));
+            env->layer[l].minmax_dirty = false;
         }
     return 0;
 }
@@ -370,47 +397,37 @@ bool next_crossing(const LayerClock& k0, int* sx, int* sy) {
     return false;
 }
 
-// A crossing of the float32 fused path through the ring pipeline (AoEnv::RingAhead): if the operand [Z | xi] of this crossing was
+// A crossing of the float32 fused path through the ring pipeline (RingAhead): if the operand [Z | xi] of this crossing was
 // put together ahead, commit its stream copy and launch the GEMM alone; else prepare it in place as extrude() does.  Either way
 // the GEMM's launch also draws the innovations of the NEXT crossing, and the step kernel of this step is asked to gather its Z.
 // The ring itself is left to that kernel (deferred scatter).  Bit-identical to extrude(): the same Z, the same xi, the same product.
 int extrude_pipelined(AoEnv* env, int l, int sx, int sy, hipStream_t st) {
-    AoEnv::RingAhead& ah = env->ahead[l];
-    const int S = env->Sl[l], oy = env->org[l][0], ox = env->org[l][1];
-    const int cur = ah.buf;
+    Layer& y = env->layer[l];
+    const int cur = y.ahead.buf;
     float* op = static_cast<float*>(env->zx_pipe_ptr(cur, l));
-    if (ah.valid && ah.sx == sx && ah.sy == sy) {
-        std::swap(env->mt_cur[l], env->mt_alt[l]);                 // the draw made ahead becomes the layer's stream
-        std::swap(env->pos_cur[l], env->pos_alt[l]);
+    if (y.ahead.valid && y.ahead.sx == sx && y.ahead.sy == sy) {
+        std::swap(y.mt_cur, y.mt_alt);                             // the draw made ahead becomes the layer's stream
+        std::swap(y.pos_cur, y.pos_alt);
     } else {
         AO_PROF(env, SHIFT_GATHER, st);
-        AO_TRY(launch_ring_prepare<float>(env->as<float>(env->screen_ptr(0, l)), op, env->inner_idx_l[l], env->mt_cur[l], env->pos_cur[l],
-                                          env->mt_cur[l], env->pos_cur[l], env->E, S, env->ninl[l], env->noutl[l], env->Kl[l], sx, sy, oy, ox, st));
+        AO_TRY(launch_ring_prepare<float>(env->as<float>(env->screen_ptr(l)), op, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur,
+                                          env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
     }
-    ah.valid = false;
-    env->gather_next[l] = false;
-    const int splits = gemm_splits(env->E, env->noutl[l], env->Kl[l]);
-    MtAhead m{env->mt_cur[l], env->pos_cur[l], env->mt_alt[l], env->pos_alt[l], static_cast<float*>(env->zx_pipe_ptr(1 - cur, l)),
-              env->Kl[l], env->ninl[l], env->noutl[l], env->E};
+    forget_lookahead(y);
+    const int splits = gemm_splits(env->E, y.nout, y.K);
+    MtAhead m{y.mt_cur, y.pos_cur, y.mt_alt, y.pos_alt, static_cast<float*>(env->zx_pipe_ptr(1 - cur, l)), y.K, y.nin, y.nout, env->E};
     {
         AO_PROF(env, GEMM_RING, st);
-        AO_TRY(launch_ring_gemm_draw_ahead(op, env->as<float>(env->ab_l[l]), static_cast<float*>(env->xbuf_ptr(l)), env->E, env->noutl[l], env->Kl[l],
-                                           splits, m, st));
+        AO_TRY(launch_ring_gemm_draw_ahead(op, env->as<float>(y.ab), static_cast<float*>(env->xbuf_ptr(l)), env->E, y.nout, y.K, splits, m,
+                                           st));
     }
-    env->last_zx = op;
-    env->last_zx_layer = l;
-    env->org[l][0] = ((oy - sy) % S + S) % S;                      // the shift itself: move the origin of the torus
-    env->org[l][1] = ((ox - sx) % S + S) % S;
-    env->ring_pending[l] = splits;
-    env->ring_src[l] = env->xbuf_ptr(l);
-    env->minmax_dirty[l] = true;
+    move_origin(y, sx, sy);
+    defer_ring(env, l, op, splits);
+    y.minmax_dirty = true;
     int nsx = 0, nsy = 0;
-    if (next_crossing(env->clk[l], &nsx, &nsy)) {                   // (the clock has been advanced for this step already)
-        ah.valid = true;
-        ah.sx = nsx;
-        ah.sy = nsy;
-        ah.buf = 1 - cur;
-        env->gather_next[l] = true;
+    if (next_crossing(y.clk, &nsx, &nsy)) {                        // (the clock has been advanced for this step already)
+        y.ahead = RingAhead{true, nsx, nsy, 1 - cur};
+        y.gather_next = true;
     }
     return 0;
 }
@@ -422,24 +439,18 @@ template <typename T>
 int advance_atmosphere_env(AoEnv* env, bool lean, hipStream_t st) {
     for (int l = 0; l < env->L; ++l) {
         AO_TRY(flush_ring<T>(env, l, st));
-        T* map = env->as<T>(env->screen_ptr(0, l));
+        const Layer& y = env->layer[l];
         T* zx = env->as<T>(env->zx);
         const size_t row = (size_t)l * env->E;
         {
             AO_PROF(env, SHIFT_GATHER, st);
-            AO_TRY(launch_ring_prepare_env<T>(map, zx, env->inner_idx_l[l], env->mt_cur[l], env->pos_cur[l], env->env_clk[env->clk_cur] + row,
-                                              env->env_clk[1 - env->clk_cur] + row, env->env_taps + row, env->layer_weight[l], env->E,
-                                              env->Sl[l], env->ninl[l], env->noutl[l], env->Kl[l], st));
+            AO_TRY(launch_ring_prepare_env<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur,
+                                              env->env_clk[env->clk_cur] + row, env->env_clk[1 - env->clk_cur] + row, env->env_taps + row,
+                                              y.weight, env->E, y.S, y.nin, y.nout, y.K, st));
         }
         int splits = 1;
-        {
-            AO_PROF(env, GEMM_RING, st);
-            AO_TRY(gemm_dispatch<T>(env, zx, env->as<T>(env->ab_l[l]), env->as<T>(env->xbuf_ptr(l)), env->E, env->noutl[l], env->Kl[l], &splits, st));
-        }
-        env->last_zx = zx;
-        env->last_zx_layer = l;
-        env->ring_pending[l] = splits;
-        env->ring_src[l] = env->xbuf_ptr(l);
+        AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
+        defer_ring(env, l, zx, splits);
         if (!(lean && env->defer_ring)) AO_TRY(flush_ring<T>(env, l, st));
     }
     env->clk_cur = 1 - env->clk_cur;
@@ -450,7 +461,7 @@ template <typename T>
 int advance_atmosphere(AoEnv* env, bool lean, hipStream_t st) {
     if (env->per_env_wind) return advance_atmosphere_env<T>(env, lean, st);
     for (int l = 0; l < env->L; ++l) {
-        LayerClock& k = env->clk[l];
+        LayerClock& k = env->layer[l].clk;
         if (k.ratio[0] == 0 && k.ratio[1] == 0) continue;
         const int ns[2] = {(int)std::fabs(k.ratio[0]), (int)std::fabs(k.ratio[1])};
         const int mn = ns[0] < ns[1] ? ns[0] : ns[1], mx = ns[0] > ns[1] ? ns[0] : ns[1];
@@ -460,7 +471,7 @@ int advance_atmosphere(AoEnv* env, bool lean, hipStream_t st) {
             AO_TRY(extrude<T>(env, l, ns[0] == mn ? 0 : s0, ns[1] == mn ? 0 : s1, lean, st));
         int b0, b1;
         if (clock_subpixel(k.ratio, k.buff, &b0, &b1)) {          // (the arithmetic the per-env device clocks share, common.hpp)
-            if (lean && env->defer_ring && env->use_lookahead && env->zx_pipe && !env->ring_pending[l]) {
+            if (lean && env->defer_ring && env->use_lookahead && env->zx_pipe && !env->layer[l].ring_pending) {
                 AO_TRY(extrude_pipelined(env, l, b0, b1, st));
             } else {
                 AO_TRY(extrude<T>(env, l, b0, b1, lean, st, lean && env->defer_ring));
@@ -673,24 +684,23 @@ template <typename T>
 void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_atm, int store_atm, int store_phase) {
     pa = PhaseArgs{};
     pa.n_layer = env->L;
-    pa.S = env->S;
-    pa.foot = (env->N / 2 - env->R / 2) + 1;
-    for (int l = 0; l < env->L; ++l) {                            // the R x R footprint of an on-axis source in layer l's grid
-        pa.S_l[l] = env->Sl[l];                                    // (OOPAO/Atmosphere.py:226-232: centre N_l // 2)
-        pa.foot_l[l] = (env->Nl[l] / 2 - env->R / 2) + 1;
-    }
+    pa.S = env->layer[0].S;
+    pa.foot = (env->layer[0].N / 2 - env->R / 2) + 1;
     pa.update_atm = (update_atm && env->L > 0 && !env->atm_user_defined) ? 1 : 0;
     pa.store_atm = store_atm;
     pa.store_phase = store_phase;
     for (int l = 0; l < env->L; ++l) {
-        pa.screen[l] = env->screen_ptr(0, l);
+        const Layer& y = env->layer[l];
+        pa.S_l[l] = y.S;                                           // the R x R footprint of an on-axis source in the layer's grid
+        pa.foot_l[l] = (y.N / 2 - env->R / 2) + 1;                 // (OOPAO/Atmosphere.py:226-232: centre N_l // 2)
+        pa.screen[l] = env->screen_ptr(l);
         pa.minmax[l] = env->minmax_ptr(l);
-        pa.minmax_dirty[l] = env->minmax_dirty[l] ? 1 : 0;
+        pa.minmax_dirty[l] = y.minmax_dirty ? 1 : 0;
         LayerTaps& t = pa.taps[l];
-        t.oy = env->org[l][0];
-        t.ox = env->org[l][1];
-        taps_from_buff(env->clk[l].buff, t);
-        t.weight = env->layer_weight[l];
+        t.oy = y.org[0];
+        t.ox = y.org[1];
+        taps_from_buff(y.clk.buff, t);
+        t.weight = y.weight;
     }
     pa.env_taps = env->per_env_wind ? env->env_taps : nullptr;
     pa.n_env = env->E;
@@ -748,23 +758,13 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     if (env->det.active) env->det.frame_counter += 1;              // every measurement is a new frame of the noise streams
     a.det = env->det;
     a.pa = env->alias();
-    for (int l = 0; l < env->L; ++l) {
-        a.ring_x[l] = env->ring_pending[l] ? static_cast<const float*>(env->ring_src[l]) : nullptr;
-        a.ring_splits[l] = env->ring_pending[l];
-    }
-    a.outer_idx = env->outer_idx;
-    a.n_outer = env->nout;
-    for (int l = 0; l < env->L; ++l) {
-        const bool g = env->gather_next[l] && env->ring_pending[l] && env->ahead[l].valid;
-        a.next_zx[l] = g ? static_cast<float*>(env->zx_pipe_ptr(env->ahead[l].buf, l)) : nullptr;
-        a.next_sx[l] = env->ahead[l].sx;
-        a.next_sy[l] = env->ahead[l].sy;
-        if (env->gather_next[l] && !g) env->ahead[l].valid = false;
-        env->gather_next[l] = false;
-    }
-    a.inner_idx = env->inner_idx;
-    a.n_inner = env->nin;
-    a.zx_ld = env->K;
+    take_rings(env, a);
+    const Layer& y0 = env->layer[0];                               // (every layer's grid and ring tables: fused_step_ok)
+    a.outer_idx = y0.outer_idx;
+    a.n_outer = y0.nout;
+    a.inner_idx = y0.inner_idx;
+    a.n_inner = y0.nin;
+    a.zx_ld = y0.K;
     a.n_modes = env->n_modes;
     a.n_subap = env->nSub;
     a.n_valid = env->nVal;
@@ -773,8 +773,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
         AO_PROF(env, ENV_STEP, st);
         AO_TRY(launch_env_step(a, st));
     }
-    for (int l = 0; l < env->L; ++l) env->minmax_dirty[l] = false;   // the kernel recomputed and stored them
-    for (int l = 0; l < env->L; ++l) env->ring_pending[l] = 0;        // ... and wrote the deferred rings
+    rings_written(env);
     return 0;
 }
 
@@ -838,7 +837,7 @@ struct BufInfo {
 int buf_info(AoEnv* env, int which, BufInfo* b) {
     const size_t z = env->esz, E = env->E, R2 = (size_t)env->R * env->R;
     switch (which) {
-        case AOENV_B_SCREEN: *b = {nullptr, env->scr_off[env->L] * z}; return 0;   // gathered per layer: [E][S_l^2] blocks, layer after layer
+        case AOENV_B_SCREEN: *b = {nullptr, env->scr_elems * z}; return 0;   // gathered per layer: [E][S_l^2] blocks, layer after layer
         case AOENV_B_OPD_ATM: *b = {env->opd_atm, E * R2 * z}; return 0;
         case AOENV_B_COEFS: *b = {env->coefs, E * env->A * z}; return 0;
         case AOENV_B_PHASE: *b = {env->phase, E * R2 * z}; return 0;
@@ -847,7 +846,7 @@ int buf_info(AoEnv* env, int which, BufInfo* b) {
         case AOENV_B_TOTAL: *b = {env->total, (size_t)env->c.n_loop * E * z}; return 0;
         case AOENV_B_RESIDUAL: *b = {env->residual, (size_t)env->c.n_loop * E * z}; return 0;
         case AOENV_B_WFS_MAX: *b = {env->wfs_max, E * z}; return 0;
-        case AOENV_B_XI: *b = {env->last_zx ? const_cast<void*>(env->last_zx) : env->zx, E * env->Kl[env->last_zx_layer] * z}; return 0;
+        case AOENV_B_XI: *b = {env->last_zx ? const_cast<void*>(env->last_zx) : env->zx, E * env->layer[env->last_zx_layer].K * z}; return 0;
         case AOENV_B_MT_STATE: *b = {nullptr, (size_t)env->L * E * (kMtN + 1) * 4}; return 0;     // packed on the host
         case AOENV_B_COUNTERS: *b = {nullptr, 16}; return 0;
         case AOENV_B_DM_PREV: *b = {env->dm_prev, E * env->A * z}; return 0;
@@ -878,17 +877,18 @@ struct DeviceGuard {
 // the ring tables of ONE layer: [A | B] (float64 [n_outer_l][n_inner_l + n_outer_l]) or the flat indices of its Z / X pixels
 static int upload_layer_table(AoEnv* env, int kind, int l, const void* h, size_t bytes) {
     if (l < 0 || l >= env->L) return fail("layer %d outside [0, %d)", l, env->L);
-    const int S = env->Sl[l], N = env->Nl[l];
+    Layer& y = env->layer[l];
+    const int S = y.S, N = y.N;
     auto need = [&](size_t n) { return bytes == n ? 0 : fail("ring table %d of layer %d: got %zu bytes, expected %zu", kind, l, bytes, n); };
     if (kind == AOENV_C_AB) {
-        AO_TRY(need((size_t)env->noutl[l] * env->Kl[l] * 8));
-        AO_TRY(sync_lookaheads(env));                              // a ring computed ahead used the old operators
-        AO_TRY(upload_real(env, env->ab_l[l], static_cast<const double*>(h), (size_t)env->noutl[l] * env->Kl[l]));
-        env->have_ab[l] = true;
+        AO_TRY(need((size_t)y.nout * y.K * 8));
+        for (int j = 0; j < env->L; ++j) forget_lookahead(env->layer[j]);   // a ring computed ahead used the old operators
+        AO_TRY(upload_real(env, y.ab, static_cast<const double*>(h), (size_t)y.nout * y.K));
+        y.have_ab = true;
         return 0;
     }
     if (kind != AOENV_C_INNER_IDX && kind != AOENV_C_OUTER_IDX) return fail("table %d is not a per-layer table", kind);
-    const int cnt = kind == AOENV_C_INNER_IDX ? env->ninl[l] : env->noutl[l];
+    const int cnt = kind == AOENV_C_INNER_IDX ? y.nin : y.nout;
     AO_TRY(need((size_t)cnt * 4));
     const int32_t* ix = static_cast<const int32_t*>(h);
     for (int i = 0; i < cnt; ++i)
@@ -898,8 +898,8 @@ static int upload_layer_table(AoEnv* env, int kind, int l, const void* h, size_t
             const int r = ix[i] / S, c = ix[i] % S;
             if (r < 1 || r > N || c < 1 || c > N) return fail("inner ring index %d is not interior", ix[i]);
         }
-    AO_HIP(hipMemcpy(kind == AOENV_C_INNER_IDX ? env->inner_idx_l[l] : env->outer_idx_l[l], h, (size_t)cnt * 4, hipMemcpyHostToDevice));
-    (kind == AOENV_C_INNER_IDX ? env->have_in[l] : env->have_out[l]) = true;
+    AO_HIP(hipMemcpy(kind == AOENV_C_INNER_IDX ? y.inner_idx : y.outer_idx, h, (size_t)cnt * 4, hipMemcpyHostToDevice));
+    (kind == AOENV_C_INNER_IDX ? y.have_in : y.have_out) = true;
     return 0;
 }
 
@@ -952,55 +952,52 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
     e->c = *cfg;
     e->device = device;
     e->esz = cfg->dtype == AOENV_F32 ? 4 : 8;
-    e->R = cfg->resolution; e->N = cfg->layer_res; e->S = cfg->layer_res + 2; e->A = cfg->n_valid_act;
-    e->nAct = cfg->n_act; e->E = cfg->n_env; e->L = cfg->n_layer; e->nin = cfg->n_inner; e->nout = cfg->n_outer;
-    e->K = cfg->n_inner + cfg->n_outer; e->nSig = cfg->n_signal; e->nSub = cfg->n_subap; e->nVal = cfg->n_valid_subap;
+    e->R = cfg->resolution; e->A = cfg->n_valid_act; e->nAct = cfg->n_act; e->E = cfg->n_env; e->L = cfg->n_layer;
+    e->nSig = cfg->n_signal; e->nSub = cfg->n_subap; e->nVal = cfg->n_valid_subap;
     e->p = e->R / e->nSub; e->n = 2 * e->p;
+    e->layer[0].N = cfg->layer_res;                                // (the phase kernels' footprint without an atmosphere)
+    e->layer[0].S = cfg->layer_res + 2;
     for (int l = 0; l < e->L; ++l) {
-        e->Nl[l] = cfg->layer_res_l[l] ? cfg->layer_res_l[l] : cfg->layer_res;
-        e->Sl[l] = e->Nl[l] + 2;
-        e->ninl[l] = 8 * e->Nl[l] - 16;
-        e->noutl[l] = 4 * e->Nl[l] + 4;
-        e->Kl[l] = e->ninl[l] + e->noutl[l];
-        e->scr_off[l + 1] = e->scr_off[l] + (size_t)e->E * e->Sl[l] * e->Sl[l];
-        e->Kmax = std::max(e->Kmax, e->Kl[l]);
-        e->noutmax = std::max(e->noutmax, e->noutl[l]);
-        e->Smax = std::max(e->Smax, e->Sl[l]);
-        if (e->Nl[l] != e->Nl[0]) e->uniform = false;
-    }
-    if (e->L > 0) {                                                // "layer 0" scalars: the grid of every layer when uniform
-        e->N = e->Nl[0]; e->S = e->Sl[0]; e->nin = e->ninl[0]; e->nout = e->noutl[0]; e->K = e->Kl[0];
+        Layer& y = e->layer[l];
+        y.N = cfg->layer_res_l[l] ? cfg->layer_res_l[l] : cfg->layer_res;
+        y.S = y.N + 2;
+        y.nin = 8 * y.N - 16;
+        y.nout = 4 * y.N + 4;
+        y.K = y.nin + y.nout;
+        y.scr_off = e->scr_elems;
+        e->scr_elems += (size_t)e->E * y.S * y.S;
+        e->Kmax = std::max(e->Kmax, y.K);
+        e->noutmax = std::max(e->noutmax, y.nout);
+        e->Smax = std::max(e->Smax, y.S);
+        if (y.N != e->layer[0].N) e->uniform = false;
     }
     const size_t z = e->esz, E = e->E, R2 = (size_t)e->R * e->R;
     int rc = 0;
     auto A_ = [&](void** p, size_t bytes) { if (!rc) rc = dmalloc(e, p, bytes); };
     if (e->L > 0) {
-        A_(&e->screen[0], e->scr_off[e->L] * z);
+        A_(&e->screen, e->scr_elems * z);
         A_(&e->minmax, (size_t)e->L * E * 2 * z);
-        A_((void**)&e->mt_state, (size_t)2 * e->L * E * kMtN * 4);
-        A_((void**)&e->mt_pos, (size_t)2 * e->L * E * 4);
         if (cfg->dtype == AOENV_F32) {                              // ring pipeline (fused float32 path)
             A_(&e->zx_pipe, (size_t)2 * e->L * E * e->Kmax * z);
         }
         A_(&e->zx, E * e->Kmax * z);
         A_(&e->xbuf, (size_t)e->L * kMaxSplits * E * e->noutmax * z);
-        for (int l = 0; l < e->L; ++l) {                           // layers on the same grid share one set of tables
-            int same = -1;
-            for (int j = 0; j < l; ++j)
-                if (e->Nl[j] == e->Nl[l]) { same = j; break; }
-            if (same >= 0 && e->uniform) {                         // (non-uniform shards: operators per layer -- r0 / L0 scale them alike, but
-                e->ab_l[l] = e->ab_l[same];                        //  the reference computes them per layer too when fov != 0)
-                e->inner_idx_l[l] = e->inner_idx_l[same];
-                e->outer_idx_l[l] = e->outer_idx_l[same];
+        for (int l = 0; l < e->L; ++l) {
+            Layer& y = e->layer[l];
+            A_((void**)&y.mt_cur, E * kMtN * 4);
+            A_((void**)&y.pos_cur, E * 4);
+            A_((void**)&y.mt_alt, E * kMtN * 4);
+            A_((void**)&y.pos_alt, E * 4);
+            if (l > 0 && e->uniform) {                             // layers on one grid share one set of tables (non-uniform shards:
+                y.ab = e->layer[0].ab;                             //  operators per layer -- r0 / L0 scale them alike, but the
+                y.inner_idx = e->layer[0].inner_idx;               //  reference computes them per layer too when fov != 0)
+                y.outer_idx = e->layer[0].outer_idx;
                 continue;
             }
-            A_(&e->ab_l[l], (size_t)e->noutl[l] * e->Kl[l] * z);
-            A_((void**)&e->inner_idx_l[l], (size_t)e->ninl[l] * 4);
-            A_((void**)&e->outer_idx_l[l], (size_t)e->noutl[l] * 4);
+            A_(&y.ab, (size_t)y.nout * y.K * z);
+            A_((void**)&y.inner_idx, (size_t)y.nin * 4);
+            A_((void**)&y.outer_idx, (size_t)y.nout * 4);
         }
-        e->ab = e->ab_l[0];
-        e->inner_idx = e->inner_idx_l[0];
-        e->outer_idx = e->outer_idx_l[0];
     }
     A_(&e->gx, (size_t)e->R * e->nAct * z);
     A_(&e->gy, (size_t)e->R * e->nAct * z);
@@ -1059,12 +1056,6 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
             rc = fail("aoenv_create: upload of the photon-noise tables failed");
     }
     if (rc) { aoenv_destroy(e); return rc; }
-    for (int l = 0; l < e->L; ++l) {
-        e->mt_cur[l] = e->mt_state + (size_t)l * E * kMtN;
-        e->mt_alt[l] = e->mt_state + (size_t)(e->L + l) * E * kMtN;
-        e->pos_cur[l] = e->mt_pos + (size_t)l * E;
-        e->pos_alt[l] = e->mt_pos + (size_t)(e->L + l) * E;
-    }
     // DFT twiddles w^k = exp(-2 pi i k / n) and the centring phasor exp(-i pi (n+1)/n x) at x = a + lo
     // (OOPAO/ShackHartmann.py:208-209), in float64 then converted
     if (cfg->wfs_type == AOENV_WFS_SH) {
@@ -1134,14 +1125,13 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             if (!env->uniform) return fail("the layers of this shard have grids of their own: upload the ring tables per layer (aoenv_upload_layer)");
             AO_TRY(upload_layer_table(env, kind, 0, h, bytes));
             for (int l = 1; l < env->L; ++l) {
-                if (kind == AOENV_C_AB) env->have_ab[l] = true;
-                else if (kind == AOENV_C_INNER_IDX) env->have_in[l] = true;
-                else env->have_out[l] = true;
+                Layer& y = env->layer[l];
+                (kind == AOENV_C_AB ? y.have_ab : kind == AOENV_C_INNER_IDX ? y.have_in : y.have_out) = true;
             }
             break;
         case AOENV_C_LAYER_WEIGHT:
             AO_TRY(need((size_t)env->L * 8));
-            for (int l = 0; l < env->L; ++l) env->layer_weight[l] = d[l];
+            for (int l = 0; l < env->L; ++l) env->layer[l].weight = d[l];
             break;
         case AOENV_C_DM_GX:
         case AOENV_C_DM_GY:
@@ -1287,7 +1277,7 @@ static int push_env_clocks(AoEnv* env, const std::vector<EnvClock>& clk) {
             t.oy = c.org[0];
             t.ox = c.org[1];
             taps_from_buff(c.buff, t);
-            t.weight = env->layer_weight[l];
+            t.weight = env->layer[l].weight;
         }
     AO_HIP(hipMemcpy(env->env_clk[env->clk_cur], clk.data(), n * sizeof(EnvClock), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(env->env_taps, taps.data(), n * sizeof(LayerTaps), hipMemcpyHostToDevice));
@@ -1307,7 +1297,7 @@ int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* 
     for (size_t i = 0; i < 2 * n; ++i)
         if (!(std::fabs(h_ratio[i]) < 1.0)) return fail("per-env wind: |ratio| = %g px/frame, must be < 1 (an env extrudes at most one ring per step)", std::fabs(h_ratio[i]));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    AO_TRY(drop_lookaheads(env, st));
+    for (int l = 0; l < env->L; ++l) forget_lookahead(env->layer[l]);
     AO_TRY(AO_DISPATCH(env, flush_rings, env, st));                // a deferred ring of the clocks as they were
     AO_HIP(hipStreamSynchronize(st));
     AO_TRY(alloc_env_clocks(env));
@@ -1319,10 +1309,11 @@ int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* 
         for (int l = 0; l < env->L; ++l)
             for (int e = 0; e < env->E; ++e) {
                 EnvClock& c = clk[(size_t)l * env->E + e];
-                c.buff[0] = env->clk[l].buff[0];
-                c.buff[1] = env->clk[l].buff[1];
-                c.org[0] = env->org[l][0];
-                c.org[1] = env->org[l][1];
+                const Layer& y = env->layer[l];
+                c.buff[0] = y.clk.buff[0];
+                c.buff[1] = y.clk.buff[1];
+                c.org[0] = y.org[0];
+                c.org[1] = y.org[1];
             }
     }
     for (size_t i = 0; i < n; ++i) {
@@ -1365,7 +1356,7 @@ int aoenv_set_clock_env(AoEnv* env, const double* h_clock) {
             clk[i].buff[d] = h_clock[4 * i + 2 + d];
         }
     }
-    for (int l = 0; l < env->L; ++l) env->ring_pending[l] = 0;
+    for (int l = 0; l < env->L; ++l) drop_ring(env->layer[l]);     // (aoenv_set_wind_env scatters it first instead)
     return push_env_clocks(env, clk);
 }
 
@@ -1379,6 +1370,22 @@ static int reset_env_clocks(AoEnv* env, bool reset_buff) {
         if (reset_buff) c.buff[0] = c.buff[1] = 0;
     }
     return push_env_clocks(env, clk);
+}
+
+// The screens are replaced (new screens, an uploaded state): every torus restarts at origin 0; a deferred ring and a look-ahead of
+// the old screens are moot; the min / max tables are stale.  reset_buff: the sub-pixel accumulators of the clocks restart too
+// (notDoneOnce, OOPAO/Atmosphere.py:586, 359-364), else they are kept.
+static int screens_replaced(AoEnv* env, bool reset_buff) {
+    for (int l = 0; l < env->L; ++l) {
+        Layer& y = env->layer[l];
+        y.org[0] = y.org[1] = 0;
+        drop_ring(y);
+        forget_lookahead(y);
+        y.minmax_dirty = true;
+        if (reset_buff) y.clk.buff[0] = y.clk.buff[1] = 0;
+    }
+    env->atm_user_defined = false;
+    return reset_env_clocks(env, reset_buff);
 }
 
 int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff) {
@@ -1397,9 +1404,10 @@ int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff) {
         return aoenv_set_wind_env(env, r.data(), reset_buff, nullptr);
     }
     for (int l = 0; l < env->L; ++l) {
-        env->clk[l].ratio[0] = h_ratio[2 * l];
-        env->clk[l].ratio[1] = h_ratio[2 * l + 1];
-        if (reset_buff) env->clk[l].buff[0] = env->clk[l].buff[1] = 0;
+        LayerClock& k = env->layer[l].clk;
+        k.ratio[0] = h_ratio[2 * l];
+        k.ratio[1] = h_ratio[2 * l + 1];
+        if (reset_buff) k.buff[0] = k.buff[1] = 0;
     }
     return 0;
 }
@@ -1413,35 +1421,25 @@ static int require_step_constants(AoEnv* env, bool atmosphere) {
     if (atmosphere && env->L > 0) {
         if (!env->have[AOENV_C_LAYER_WEIGHT]) return fail("atmosphere table %d has not been uploaded", (int)AOENV_C_LAYER_WEIGHT);
         for (int l = 0; l < env->L; ++l)
-            if (!env->have_ab[l] || !env->have_in[l] || !env->have_out[l]) return fail("the ring tables of layer %d have not been uploaded", l);
+            if (!env->layer[l].have_ab || !env->layer[l].have_in || !env->layer[l].have_out) return fail("the ring tables of layer %d have not been uploaded", l);
     }
     return 0;
 }
 
-// ring RandomState seeding, first ring X = A.Z + B.xi, accumulators, atm.OPD: the part of generateNewPhaseScreen
-// after the new interior is in mapShift (OOPAO/Atmosphere.py:579-592)
+// ring RandomState seeding, first ring X = A.Z + B.xi, atm.OPD: the part of generateNewPhaseScreen after the new interior is in
+// mapShift (OOPAO/Atmosphere.py:579-592); the callers have reset the tori and the accumulators (screens_replaced)
 static int finish_new_screens(AoEnv* env, const uint32_t* h_ring_seeds, hipStream_t st) {
     const int E = env->E, L = env->L;
-    for (int l = 0; l < L; ++l) env->ring_pending[l] = 0;          // a deferred ring of the old screens is moot
-    AO_TRY(sync_lookaheads(env));
     std::vector<uint32_t> keys((size_t)E * kMtN);
     std::vector<int> pos((size_t)E, kMtN);
     for (int l = 0; l < L; ++l) {
         for (int e = 0; e < E; ++e) mt_seed(h_ring_seeds[(size_t)e * L + l], &keys[(size_t)e * kMtN]);
-        AO_HIP(hipMemcpy(env->mt_cur[l], keys.data(), keys.size() * 4, hipMemcpyHostToDevice));
-        AO_HIP(hipMemcpy(env->pos_cur[l], pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+        AO_HIP(hipMemcpy(env->layer[l].mt_cur, keys.data(), keys.size() * 4, hipMemcpyHostToDevice));
+        AO_HIP(hipMemcpy(env->layer[l].pos_cur, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
     }
     AO_HIP(hipStreamSynchronize(st));
-    AO_TRY(reset_env_clocks(env, true));                           // per-env clocks: accumulators and origins of every env to zero
-    const bool pe = env->per_env_wind;
-    env->per_env_wind = false;                                     // the first ring is one extrusion of the whole shard, origin 0
-    for (int l = 0; l < L; ++l) {
-        env->clk[l].buff[0] = env->clk[l].buff[1] = 0;            // notDoneOnce (OOPAO/Atmosphere.py:586, 359-364)
-        const int rc = AO_DISPATCH(env, extrude, env, l, 0, 0, false, st);   // (the callers reset the torus origin with the new interior)
-        if (rc) { env->per_env_wind = pe; return rc; }
-    }
-    env->per_env_wind = pe;
-    env->atm_user_defined = false;
+    for (int l = 0; l < L; ++l)                                    // the first ring: one extrusion of the whole shard at origin 0
+        AO_TRY(AO_DISPATCH(env, extrude, env, l, 0, 0, false, st));
     AO_TRY(AO_DISPATCH(env, run_phase, env, 1, 1, st));            // fill_phase_support + set_OPD + atm*tel
     return 0;
 }
@@ -1457,15 +1455,15 @@ int aoenv_new_screens(AoEnv* env, const double* h_screens, const uint32_t* h_rin
     if (!h_screens) {
         if (env->per_env_wind) return fail("per-env clocks: the interior cannot be kept (every env has moved its own origin): hand the screens over");
         for (int l = 0; l < L; ++l)
-            if (env->org[l][0] || env->org[l][1]) return fail("keeping the interior is only possible before the first shift");
+            if (env->layer[l].org[0] || env->layer[l].org[1]) return fail("keeping the interior is only possible before the first shift");
     }
-    for (int l = 0; l < L; ++l) env->org[l][0] = env->org[l][1] = 0;
+    AO_TRY(screens_replaced(env, true));
     if (h_screens) {
         // mapShift[~outerMask] = phase  (OOPAO/Atmosphere.py:585); the ring is drawn below
         std::vector<char> host;
         size_t layer_base = 0;                                     // (layers with grids of their own: layer-major blocks)
         for (int l = 0; l < L; ++l) {
-            const int N = env->Nl[l], S = env->Sl[l];
+            const int N = env->layer[l].N, S = env->layer[l].S;
             host.assign((size_t)E * S * S * env->esz, 0);
             for (int e = 0; e < E; ++e) {
                 const double* src = env->uniform ? h_screens + ((size_t)e * L + l) * N * N : h_screens + layer_base + (size_t)e * N * N;
@@ -1476,7 +1474,7 @@ int aoenv_new_screens(AoEnv* env, const double* h_screens, const uint32_t* h_rin
                         else reinterpret_cast<double*>(host.data())[o] = src[(size_t)r * N + c];
                     }
             }
-            AO_HIP(hipMemcpy(env->screen_ptr(0, l), host.data(), host.size(), hipMemcpyHostToDevice));
+            AO_HIP(hipMemcpy(env->screen_ptr(l), host.data(), host.size(), hipMemcpyHostToDevice));
             layer_base += (size_t)E * N * N;
         }
     }
@@ -1511,7 +1509,7 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
     hipStream_t st = static_cast<hipStream_t>(stream);
     AO_HIP(hipStreamSynchronize(st));
     const int E = env->E, L = env->L;
-    for (int l = 0; l < L; ++l) env->org[l][0] = env->org[l][1] = 0;
+    AO_TRY(screens_replaced(env, true));
     const double pi = 3.14159265358979323846;
     TmpFree tmp;
     int N_built = -1, EC = 1;
@@ -1523,7 +1521,7 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
     std::vector<uint32_t> keys;
     std::vector<int> pos;
     for (int l = 0; l < L; ++l) {
-        const int N = env->Nl[l], S = env->Sl[l];
+        const int N = env->layer[l].N, S = env->layer[l].S;
         const size_t N2 = (size_t)N * N;
         if (N != N_built) {                                        // tables of this grid size (every layer's when fov = 0)
             // frequency-grid amplitude sqrt(PSD) del_f (phaseStats.py:209-222) and the 3 x 4 sub-harmonic terms (:277-309)
@@ -1579,7 +1577,7 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
             AO_HIP(hipMemcpyAsync(d_pos, pos.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
             AO_TRY(launch_mt_normal<double>(d_mt, d_pos, d_nrm, ne, (int)(2 * N2), 0, (int)(2 * N2), st));
             sa.n_env = ne;
-            char* map = static_cast<char*>(env->screen_ptr(0, l)) + (size_t)e0 * S * S * env->esz;
+            char* map = static_cast<char*>(env->screen_ptr(l)) + (size_t)e0 * S * S * env->esz;
             if (env->esz == 4) AO_TRY(launch_screen<float>(sa, reinterpret_cast<float*>(map), S, st));
             else AO_TRY(launch_screen<double>(sa, reinterpret_cast<double*>(map), S, st));
             AO_HIP(hipStreamSynchronize(st));                      // keys / pos are reused by the next chunk
@@ -1782,14 +1780,15 @@ int aoenv_download(AoEnv* env, int which, void* h_dst, size_t bytes, void* strea
         std::vector<EnvClock> clk_h;
         if (env->per_env_wind) AO_TRY(pull_env_clocks(env, clk_h));
         for (int l = 0; l < env->L; ++l) {
-            const int S = env->Sl[l];
+            const Layer& y = env->layer[l];
+            const int S = y.S;
             const size_t per = (size_t)env->E * S * S * z;
             tmp.resize(per);
-            AO_HIP(hipMemcpy(tmp.data(), env->screen_ptr(0, l), per, hipMemcpyDeviceToHost));
-            char* dst = static_cast<char*>(h_dst) + env->scr_off[l] * z;
+            AO_HIP(hipMemcpy(tmp.data(), env->screen_ptr(l), per, hipMemcpyDeviceToHost));
+            char* dst = static_cast<char*>(h_dst) + y.scr_off * z;
             for (int e = 0; e < env->E; ++e) {
-                const int oy = env->per_env_wind ? clk_h[(size_t)l * env->E + e].org[0] : env->org[l][0];
-                const int ox = env->per_env_wind ? clk_h[(size_t)l * env->E + e].org[1] : env->org[l][1];
+                const int* org = env->per_env_wind ? clk_h[(size_t)l * env->E + e].org : y.org;
+                const int oy = org[0], ox = org[1];
                 for (int r = 0; r < S; ++r) {
                     const char* srow = tmp.data() + ((size_t)e * S * S + (size_t)((r + oy) % S) * S) * z;
                     char* drow = dst + ((size_t)e * S * S + (size_t)r * S) * z;
@@ -1805,8 +1804,8 @@ int aoenv_download(AoEnv* env, int which, void* h_dst, size_t bytes, void* strea
         std::vector<uint32_t> st_(n * kMtN);
         std::vector<int> pos(n);
         for (int l = 0; l < env->L; ++l) {                         // the committed copy of every layer (a look-ahead writes the other)
-            AO_HIP(hipMemcpy(&st_[(size_t)l * env->E * kMtN], env->mt_cur[l], (size_t)env->E * kMtN * 4, hipMemcpyDeviceToHost));
-            AO_HIP(hipMemcpy(&pos[(size_t)l * env->E], env->pos_cur[l], (size_t)env->E * 4, hipMemcpyDeviceToHost));
+            AO_HIP(hipMemcpy(&st_[(size_t)l * env->E * kMtN], env->layer[l].mt_cur, (size_t)env->E * kMtN * 4, hipMemcpyDeviceToHost));
+            AO_HIP(hipMemcpy(&pos[(size_t)l * env->E], env->layer[l].pos_cur, (size_t)env->E * 4, hipMemcpyDeviceToHost));
         }
         uint32_t* out = static_cast<uint32_t*>(h_dst);
         for (size_t i = 0; i < n; ++i) {
@@ -1839,16 +1838,13 @@ int aoenv_upload_state(AoEnv* env, int which, const void* h_src, size_t bytes, v
     AO_HIP(hipStreamSynchronize(st));
     if (which == AOENV_B_SCREEN) {
         // logical layer.mapShift of every env: the tori restart at origin 0; the clip range is re-derived by its next consumer
-        AO_TRY(sync_lookaheads(env));
+        AO_TRY(screens_replaced(env, false));                      // (the clocks' accumulators are kept)
         for (int l = 0; l < env->L; ++l) {
-            const size_t per = (size_t)env->E * env->Sl[l] * env->Sl[l] * env->esz;
-            AO_HIP(hipMemcpy(env->screen_ptr(0, l), static_cast<const char*>(h_src) + env->scr_off[l] * env->esz, per, hipMemcpyHostToDevice));
-            env->org[l][0] = env->org[l][1] = 0;
-            env->ring_pending[l] = 0;
-            env->minmax_dirty[l] = true;
+            const Layer& y = env->layer[l];
+            const size_t per = (size_t)env->E * y.S * y.S * env->esz;
+            AO_HIP(hipMemcpy(env->screen_ptr(l), static_cast<const char*>(h_src) + y.scr_off * env->esz, per, hipMemcpyHostToDevice));
         }
-        env->atm_user_defined = false;
-        return reset_env_clocks(env, false);                       // per-env clocks: origins to zero, accumulators kept
+        return 0;
     }
     if (which == AOENV_B_MT_STATE) {
         const size_t n = (size_t)env->L * env->E;
@@ -1860,10 +1856,10 @@ int aoenv_upload_state(AoEnv* env, int which, const void* h_src, size_t bytes, v
             pos[i] = (int)in[i * (kMtN + 1) + kMtN];
             if (pos[i] < 0 || pos[i] > kMtN || pos[i] % 4) return fail("MT19937 position %d is not a multiple of 4 in [0, 624]", pos[i]);
         }
-        AO_TRY(sync_lookaheads(env));
         for (int l = 0; l < env->L; ++l) {
-            AO_HIP(hipMemcpy(env->mt_cur[l], &st_[(size_t)l * env->E * kMtN], (size_t)env->E * kMtN * 4, hipMemcpyHostToDevice));
-            AO_HIP(hipMemcpy(env->pos_cur[l], &pos[(size_t)l * env->E], (size_t)env->E * 4, hipMemcpyHostToDevice));
+            forget_lookahead(env->layer[l]);
+            AO_HIP(hipMemcpy(env->layer[l].mt_cur, &st_[(size_t)l * env->E * kMtN], (size_t)env->E * kMtN * 4, hipMemcpyHostToDevice));
+            AO_HIP(hipMemcpy(env->layer[l].pos_cur, &pos[(size_t)l * env->E], (size_t)env->E * 4, hipMemcpyHostToDevice));
         }
         return 0;
     }
@@ -1879,7 +1875,7 @@ int aoenv_upload_state(AoEnv* env, int which, const void* h_src, size_t bytes, v
 int aoenv_get_buff(AoEnv* env, double* h_buff) {
     if (!env || !h_buff) return fail("null argument");
     if (env->per_env_wind) return fail("the shard runs per-env clocks (aoenv_set_wind_env): use aoenv_get_clock_env");
-    for (int l = 0; l < env->L; ++l) { h_buff[2 * l] = env->clk[l].buff[0]; h_buff[2 * l + 1] = env->clk[l].buff[1]; }
+    for (int l = 0; l < env->L; ++l) { h_buff[2 * l] = env->layer[l].clk.buff[0]; h_buff[2 * l + 1] = env->layer[l].clk.buff[1]; }
     return 0;
 }
 
@@ -1888,7 +1884,7 @@ int aoenv_set_buff(AoEnv* env, const double* h_buff) {
     if (env->per_env_wind) return fail("the shard runs per-env clocks (aoenv_set_wind_env): use aoenv_set_clock_env");
     for (int l = 0; l < env->L; ++l) {
         if (std::fabs(h_buff[2 * l]) >= 1 || std::fabs(h_buff[2 * l + 1]) >= 1) return fail("|buff| must be < 1");
-        env->clk[l].buff[0] = h_buff[2 * l]; env->clk[l].buff[1] = h_buff[2 * l + 1];
+        env->layer[l].clk.buff[0] = h_buff[2 * l]; env->layer[l].clk.buff[1] = h_buff[2 * l + 1];
     }
     return 0;
 }
@@ -1910,7 +1906,8 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
         case AOENV_OPT_DEFER_RING: env->defer_ring = value != 0; return 0;
         case AOENV_OPT_FACTORED_RECON: env->use_factored_recon = value != 0; return 0;
         case AOENV_OPT_RING_LOOKAHEAD:
-            if (!value) AO_TRY(sync_lookaheads(env));
+            if (!value)
+                for (int l = 0; l < env->L; ++l) forget_lookahead(env->layer[l]);
             env->use_lookahead = value != 0;
             return 0;
         case AOENV_OPT_COEFS_IMAGE:
