@@ -179,6 +179,31 @@ int aoenv_new_screens(AoEnv* env, const double* h_screens, const uint32_t* h_rin
 int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds, double r0,
                              double L0, double pixel_size, void* stream);
 
+/* Replaces: atm.generateNewPhaseScreen(seed) (OOPAO/Atmosphere.py:560-592) plus the trainers' episode prologue (dm.coefs = 0,
+ * dm_prev = 0: MAIN/PO4AO/mbrl.py:49-52, OOPAOEnv_VPG.py:120-121) for SOME envs of the shard: the restart of single loops that a
+ * batched RL environment needs (a diverged loop, staggered episodes, autoreset).
+ *   h_env_idx [n_idx] int32: the envs to restart, each in [0, n_env), none twice, in any order;
+ *   h_screen_seeds / h_ring_seeds [n_idx][n_layer] uint32: row c belongs to env h_env_idx[c]; as for aoenv_new_screens_device;
+ *   r0, L0, pixel_size: as for aoenv_new_screens_device.
+ * For every listed env, and only for those: new layer screens drawn on the device (the generator and streams of
+ * aoenv_new_screens_device), ring RandomStates reseeded, the first ring X = A.Z + B.xi drawn, the clock restarted (accumulator and
+ * torus origin 0, the wind ratio kept), min / max refreshed, dm.coefs and dm_prev zeroed; atm.OPD and the residual phase are then
+ * re-derived from the screens (a user-defined OPD of aoenv_set_atm_opd ends here, as with new screens).  Afterwards a listed env is
+ * indistinguishable, bit for bit, from the same env of a shard of the same size that was reset as a whole with those seeds and had
+ * its commands zeroed; screens, streams, clocks, commands and telemetry of every other env stay bit for bit as they were.
+ * The shard switches to per-env clocks FOR GOOD, exactly as aoenv_set_wind_env does (a shared origin cannot describe one env
+ * restarted at origin 0): from the shared clock every env starts at the shared origin and accumulator with the shard's wind, which
+ * must be < 1 pixel per frame; a deferred ring is scattered and a ring look-ahead forgotten first.  From then on the shard pays the
+ * cost of per-env clocks on every step (the ring kernels run on every step: about 26 % at the 8 m Shack-Hartmann geometry,
+ * DESIGN.md section 4.2).  The screen generation and the ring operands are work for n_idx envs, driven by a device index list;
+ * the ring product itself runs once per layer over the whole shard, so that it sums in the order of the full reset.
+ * n_idx == 0 succeeds and does nothing (the clocks stay as they are).  Refused, with nothing changed: null pointers, n_idx < 0,
+ * an index outside [0, n_env), a duplicate index, n_layer == 0, missing ring tables, non-positive r0 / L0 / pixel_size, a shared
+ * wind of a pixel per frame or more, and shards with layers on grids of their own (AoCfg.layer_res_l), which have no per-env
+ * clocks.  Host synchronisation as in aoenv_new_screens_device (the stream is waited for once, before the clocks are switched). */
+int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint32_t* h_screen_seeds,
+                     const uint32_t* h_ring_seeds, double r0, double L0, double pixel_size, void* stream);
+
 /* Replaces: atm.update(OPD) with a user-defined OPD (OOPAO/Atmosphere.py:421-425) and
  * tel.OPD = ... in the WFS calibration (OOPAO/ShackHartmann.py:296-297).  h_opd [n_env][R*R] float64
  * (no pupil applied); only meaningful while n_layer == 0 or until the next aoenv_step. */

@@ -179,6 +179,112 @@ int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Partial reset (aoenv_reset_envs): the same work for the envs of a device index list only.  Workgroup c of a launch serves env
+// env_idx[c]; every listed env is at origin 0 with an empty accumulator (k_reset_env_rows), so the first ring is the extrusion
+// (sx, sy) = (0, 0) of the full reset, kernel for kernel: the same gather, the same draw, the same sum of the slabs.
+// ---------------------------------------------------------------------------------------------------
+// RandomState(seed): init_genrand of MT19937 (NumPy's legacy seeding), one lane per stream; stream c is seeded with seeds[c * stride]
+// and stored in row env_idx[c] (env_idx null: row c) with its position at the end of the block (the first draw twists)
+__global__ void __launch_bounds__(64) k_mt_seed(const uint32_t* __restrict__ seeds, int stride, const int* __restrict__ env_idx,
+                                                uint32_t* __restrict__ mt_state, int* __restrict__ mt_pos, int n) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n) return;
+    const int row = env_idx ? env_idx[c] : c;
+    uint32_t seed = seeds[(size_t)c * stride];
+    uint32_t* key = mt_state + (size_t)row * kMtN;
+    for (int pos = 0; pos < kMtN; ++pos) {
+        key[pos] = seed;
+        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)pos + 1u;
+    }
+    mt_pos[row] = kMtN;
+}
+
+int launch_mt_seed(const uint32_t* seeds, int stride, const int* env_idx, uint32_t* mt_state, int* mt_pos, int n, hipStream_t st) {
+    hipLaunchKernelGGL(k_mt_seed, dim3(cdiv(n, 64)), dim3(64), 0, st, seeds, stride, env_idx, mt_state, mt_pos, n);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+
+// the state rows of the listed envs back to the start of an episode: dm.coefs and dm_prev zero; per layer the clock's accumulator
+// and origin zero (the wind ratio is kept) and the taps that follow from them, no ring to scatter
+template <typename T>
+__global__ void __launch_bounds__(256) k_reset_env_rows(const int* __restrict__ env_idx, T* __restrict__ coefs, T* __restrict__ dm_prev,
+                                                        int n_valid_act, EnvClock* __restrict__ clk, LayerTaps* __restrict__ taps,
+                                                        int n_layer, int n_env) {
+    const int e = env_idx[blockIdx.x];
+    for (int k = threadIdx.x; k < n_valid_act; k += blockDim.x) {
+        coefs[(size_t)e * n_valid_act + k] = (T)0;
+        dm_prev[(size_t)e * n_valid_act + k] = (T)0;
+    }
+    if ((int)threadIdx.x < n_layer) {
+        const size_t i = (size_t)threadIdx.x * n_env + e;
+        EnvClock c = clk[i];
+        c.buff[0] = c.buff[1] = 0.0;
+        c.org[0] = c.org[1] = 0;
+        clk[i] = c;
+        LayerTaps t = taps[i];                                     // (keeps the layer's weight)
+        t.oy = t.ox = 0;
+        taps_from_buff(c.buff, t);
+        t.ring = 0;
+        taps[i] = t;
+    }
+}
+
+template <typename T>
+int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, int n_valid_act, EnvClock* clk, LayerTaps* taps,
+                          int n_layer, int n_env, hipStream_t st) {
+    hipLaunchKernelGGL(k_reset_env_rows<T>, dim3(n_idx), dim3(256), 0, st, env_idx, coefs, dm_prev, n_valid_act, clk, taps, n_layer, n_env);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+
+// k_ring_prepare of the listed envs at origin 0, no shift: Z of the new interior, xi from the stream just seeded (in place)
+template <typename T>
+__global__ void __launch_bounds__(256) k_ring_prepare_idx(const T* __restrict__ map, T* __restrict__ zx, const int* __restrict__ inner_idx,
+                                                          uint32_t* mt_state, int* mt_pos, const int* __restrict__ env_idx, int S,
+                                                          int n_inner, int n_outer, int K) {
+    const int e = env_idx[blockIdx.y];
+    if (blockIdx.x == 0) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, 0, 0, 0, 0, e, threadIdx.x, 256);
+    else mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, e);
+}
+
+template <typename T>
+int launch_ring_prepare_idx(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const int* env_idx, int n_idx,
+                            int S, int n_inner, int n_outer, int K, hipStream_t st) {
+    if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
+    hipLaunchKernelGGL(k_ring_prepare_idx<T>, dim3(2, n_idx), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, env_idx, S, n_inner,
+                       n_outer, K);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+
+// k_scatter_minmax of the listed envs at origin 0, with the min / max pass; X is the product over the WHOLE shard (slab = n_env * n_outer)
+template <typename T>
+__global__ void __launch_bounds__(1024) k_scatter_minmax_idx(T* __restrict__ new_map, const T* __restrict__ X,
+                                                             const int* __restrict__ outer_idx, T* __restrict__ minmax,
+                                                             const int* __restrict__ env_idx, int S, int n_outer, int splits, size_t slab) {
+    const int e = env_idx[blockIdx.x];
+    T* map = new_map + (size_t)e * S * S;
+    const T* x = X + (size_t)e * n_outer;
+    for (int k = threadIdx.x; k < n_outer; k += blockDim.x) {
+        T v = x[k];
+        for (int z = 1; z < splits; ++z) v += x[(size_t)z * slab + k];       // split-K slabs, fixed order
+        map[outer_idx[k]] = v;
+    }
+    __syncthreads();
+    block_minmax<T>(map, minmax, S, e);
+}
+
+template <typename T>
+int launch_scatter_minmax_idx(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n_idx, int n_env, int S,
+                              int n_outer, int splits, hipStream_t st) {
+    hipLaunchKernelGGL(k_scatter_minmax_idx<T>, dim3(n_idx), dim3(1024), 0, st, new_map, X, outer_idx, minmax, env_idx, S, n_outer, splits,
+                       (size_t)n_env * n_outer);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+
 #define INST(T)                                                                                                    \
     template int launch_ring_prepare<T>(const T*, T*, const int*, const uint32_t*, const int*, uint32_t*, int*, int, int, int, \
                                         int, int, int, int, int, int, hipStream_t);                                \
@@ -187,7 +293,10 @@ int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st) {
                                           hipStream_t, const LayerTaps*);                                          \
     template int launch_ring_prepare_env<T>(const T*, T*, const int*, uint32_t*, int*, const EnvClock*, EnvClock*, LayerTaps*, \
                                             double, int, int, int, int, int, hipStream_t);                                                          \
-    template int launch_minmax<T>(const T*, T*, int, int, hipStream_t);
+    template int launch_minmax<T>(const T*, T*, int, int, hipStream_t);                                            \
+    template int launch_reset_env_rows<T>(const int*, int, T*, T*, int, EnvClock*, LayerTaps*, int, int, hipStream_t); \
+    template int launch_ring_prepare_idx<T>(const T*, T*, const int*, uint32_t*, int*, const int*, int, int, int, int, int, hipStream_t); \
+    template int launch_scatter_minmax_idx<T>(T*, const T*, const int*, T*, const int*, int, int, int, int, int, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

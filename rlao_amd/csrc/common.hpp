@@ -134,6 +134,17 @@ int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t*
                             hipStream_t st);
 template <typename T>
 int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st);
+// partial reset (aoenv_reset_envs): the index-list forms, workgroup c of a launch serves env env_idx[c] (device list, n_idx entries)
+int launch_mt_seed(const uint32_t* seeds, int stride, const int* env_idx, uint32_t* mt_state, int* mt_pos, int n, hipStream_t st);
+template <typename T>
+int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, int n_valid_act, EnvClock* clk, LayerTaps* taps,
+                          int n_layer, int n_env, hipStream_t st);
+template <typename T>
+int launch_ring_prepare_idx(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const int* env_idx, int n_idx,
+                            int S, int n_inner, int n_outer, int K, hipStream_t st);
+template <typename T>
+int launch_scatter_minmax_idx(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n_idx, int n_env, int S,
+                              int n_outer, int splits, hipStream_t st);
 int gemm_splits(int M, int N, int K);
 // the draw of a layer's next innovations, run beside the ring GEMM (k_ring_gemm_draw_ahead)
 struct MtAhead {
@@ -362,8 +373,9 @@ struct ScreenArgs {
     int N, n_env, seq_per_block;
     double delta;            // layer pixel size [m]
 };
-// writes layer.phase (rad @ 500 nm) of n_env envs into the interior of their (N+2)^2 mapShift
+// writes layer.phase (rad @ 500 nm) of n_env envs into the interior of their (N+2)^2 mapShift: generated env c goes to map c of
+// `map`, or -- env_idx (a device list of n_env entries) given -- to map env_idx[c] (aoenv_reset_envs)
 template <typename T>
-int launch_screen(const ScreenArgs& base, T* map, int S, hipStream_t st);
+int launch_screen(const ScreenArgs& base, T* map, int S, hipStream_t st, const int* env_idx = nullptr);
 
 }  // namespace ao

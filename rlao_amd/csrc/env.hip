@@ -1499,6 +1499,65 @@ double vk_psd(double f, double r0, double L0) {
 }
 }  // namespace
 
+namespace {
+// Tables and scratch of the device screen generator for one grid size N and up to n_env envs at a time (chunks of `ec`)
+struct ScreenGen {
+    ScreenArgs sa{};
+    uint32_t* mt = nullptr;                        // [ec][624] the layers' own RandomState(seed + layer) ...
+    int* pos = nullptr;                            // [ec]
+    int ec = 1;
+};
+int make_screen_gen(TmpFree& tmp, int N, int n_env, double r0, double L0, double pixel_size, ScreenGen* g) {
+    const double pi = 3.14159265358979323846;
+    const size_t N2 = (size_t)N * N;
+    // frequency-grid amplitude sqrt(PSD) del_f (phaseStats.py:209-222) and the 3 x 4 sub-harmonic terms (:277-309)
+    std::vector<double> amp(N2), sub(36), tw(2 * (size_t)N);
+    const double del_f = 1.0 / (N * pixel_size);
+    for (int y = 0; y < N; ++y)
+        for (int x = 0; x < N; ++x) {
+            const double fx = (x - N / 2.0) * del_f, fy = (y - N / 2.0) * del_f;
+            amp[(size_t)y * N + x] = std::sqrt(vk_psd(std::sqrt(fx * fx + fy * fy), r0, L0)) * del_f;
+        }
+    amp[(size_t)(N / 2) * N + N / 2] = 0;
+    const double D = N * pixel_size;
+    for (int p = 1; p <= 3; ++p) {
+        const double df = 1.0 / (std::pow(3.0, p) * D);
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j) {
+                const double fx = (j - 1) * df, fy = (i - 1) * df;
+                double* t = &sub[3 * (4 * (p - 1) + 2 * i + j)];
+                t[0] = (i == 1 && j == 1) ? 0.0 : std::sqrt(vk_psd(std::sqrt(fx * fx + fy * fy), r0, L0)) * df;
+                t[1] = fx;
+                t[2] = fy;
+            }
+    }
+    for (int k = 0; k < N; ++k) { tw[2 * k] = std::cos(2 * pi * k / N); tw[2 * k + 1] = -std::sin(2 * pi * k / N); }
+    ScreenArgs& sa = g->sa;
+    sa = ScreenArgs{};
+    AO_TRY(make_fft_plan(N, &sa.plan));
+    sa.N = N;
+    sa.delta = pixel_size;
+    const size_t per_env = 40 * N2;                                // normals + complex scratch + real screen, float64
+    const int EC = g->ec = (int)std::min<size_t>((size_t)n_env, std::max<size_t>(1, ((size_t)1 << 30) / per_env));
+    double *d_amp = nullptr, *d_sub = nullptr, *d_tw = nullptr, *d_nrm = nullptr, *d_hi = nullptr;
+    void* d_scr = nullptr;
+    AO_TRY(tmp.get((void**)&d_amp, N2 * 8));
+    AO_TRY(tmp.get((void**)&d_sub, 36 * 8));
+    AO_TRY(tmp.get((void**)&d_tw, 2 * (size_t)N * 8));
+    AO_TRY(tmp.get((void**)&d_nrm, (size_t)EC * 2 * N2 * 8));
+    AO_TRY(tmp.get(&d_scr, (size_t)EC * N2 * 16));
+    AO_TRY(tmp.get((void**)&d_hi, (size_t)EC * N2 * 8));
+    AO_TRY(tmp.get((void**)&g->mt, (size_t)EC * kMtN * 4));
+    AO_TRY(tmp.get((void**)&g->pos, (size_t)EC * 4));
+    AO_HIP(hipMemcpy(d_amp, amp.data(), N2 * 8, hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(d_sub, sub.data(), 36 * 8, hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
+    sa.amp = d_amp; sa.sub = d_sub; sa.tw = d_tw; sa.nrm = d_nrm; sa.hi = d_hi;
+    sa.scratch = reinterpret_cast<cx<double>*>(d_scr);
+    return 0;
+}
+}  // namespace
+
 int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds, double r0,
                              double L0, double pixel_size, void* stream) {
     AO_CHECK_ENV(env);
@@ -1510,80 +1569,132 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
     AO_HIP(hipStreamSynchronize(st));
     const int E = env->E, L = env->L;
     AO_TRY(screens_replaced(env, true));
-    const double pi = 3.14159265358979323846;
     TmpFree tmp;
-    int N_built = -1, EC = 1;
-    ScreenArgs sa{};
-    double *d_amp = nullptr, *d_sub = nullptr, *d_tw = nullptr, *d_nrm = nullptr, *d_hi = nullptr;
-    void* d_scr = nullptr;
-    uint32_t* d_mt = nullptr;
-    int* d_pos = nullptr;
+    int N_built = -1;
+    ScreenGen g;
     std::vector<uint32_t> keys;
     std::vector<int> pos;
     for (int l = 0; l < L; ++l) {
         const int N = env->layer[l].N, S = env->layer[l].S;
         const size_t N2 = (size_t)N * N;
         if (N != N_built) {                                        // tables of this grid size (every layer's when fov = 0)
-            // frequency-grid amplitude sqrt(PSD) del_f (phaseStats.py:209-222) and the 3 x 4 sub-harmonic terms (:277-309)
-            std::vector<double> amp(N2), sub(36), tw(2 * (size_t)N);
-            const double del_f = 1.0 / (N * pixel_size);
-            for (int y = 0; y < N; ++y)
-                for (int x = 0; x < N; ++x) {
-                    const double fx = (x - N / 2.0) * del_f, fy = (y - N / 2.0) * del_f;
-                    amp[(size_t)y * N + x] = std::sqrt(vk_psd(std::sqrt(fx * fx + fy * fy), r0, L0)) * del_f;
-                }
-            amp[(size_t)(N / 2) * N + N / 2] = 0;
-            const double D = N * pixel_size;
-            for (int p = 1; p <= 3; ++p) {
-                const double df = 1.0 / (std::pow(3.0, p) * D);
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j) {
-                        const double fx = (j - 1) * df, fy = (i - 1) * df;
-                        double* t = &sub[3 * (4 * (p - 1) + 2 * i + j)];
-                        t[0] = (i == 1 && j == 1) ? 0.0 : std::sqrt(vk_psd(std::sqrt(fx * fx + fy * fy), r0, L0)) * df;
-                        t[1] = fx;
-                        t[2] = fy;
-                    }
-            }
-            for (int k = 0; k < N; ++k) { tw[2 * k] = std::cos(2 * pi * k / N); tw[2 * k + 1] = -std::sin(2 * pi * k / N); }
-            sa = ScreenArgs{};
-            AO_TRY(make_fft_plan(N, &sa.plan));
-            sa.N = N;
-            sa.delta = pixel_size;
-            const size_t per_env = 40 * N2;                        // normals + complex scratch + real screen, float64
-            EC = (int)std::min<size_t>((size_t)E, std::max<size_t>(1, ((size_t)1 << 30) / per_env));
-            AO_TRY(tmp.get((void**)&d_amp, N2 * 8));
-            AO_TRY(tmp.get((void**)&d_sub, 36 * 8));
-            AO_TRY(tmp.get((void**)&d_tw, 2 * (size_t)N * 8));
-            AO_TRY(tmp.get((void**)&d_nrm, (size_t)EC * 2 * N2 * 8));
-            AO_TRY(tmp.get(&d_scr, (size_t)EC * N2 * 16));
-            AO_TRY(tmp.get((void**)&d_hi, (size_t)EC * N2 * 8));
-            AO_TRY(tmp.get((void**)&d_mt, (size_t)EC * kMtN * 4));
-            AO_TRY(tmp.get((void**)&d_pos, (size_t)EC * 4));
-            AO_HIP(hipMemcpy(d_amp, amp.data(), N2 * 8, hipMemcpyHostToDevice));
-            AO_HIP(hipMemcpy(d_sub, sub.data(), 36 * 8, hipMemcpyHostToDevice));
-            AO_HIP(hipMemcpy(d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
-            sa.amp = d_amp; sa.sub = d_sub; sa.tw = d_tw; sa.nrm = d_nrm; sa.hi = d_hi;
-            sa.scratch = reinterpret_cast<cx<double>*>(d_scr);
-            keys.assign((size_t)EC * kMtN, 0u);
-            pos.assign((size_t)EC, kMtN);
+            AO_TRY(make_screen_gen(tmp, N, E, r0, L0, pixel_size, &g));
+            keys.assign((size_t)g.ec * kMtN, 0u);
+            pos.assign((size_t)g.ec, kMtN);
             N_built = N;
         }
+        const int EC = g.ec;
         for (int e0 = 0; e0 < E; e0 += EC) {
             const int ne = std::min(EC, E - e0);
             // the layer's own RandomState(seed + layer) draws normal(size=(N, N)) twice (real, imaginary parts)
             for (int e = 0; e < ne; ++e) mt_seed(h_screen_seeds[(size_t)(e0 + e) * L + l], &keys[(size_t)e * kMtN]);
-            AO_HIP(hipMemcpyAsync(d_mt, keys.data(), (size_t)ne * kMtN * 4, hipMemcpyHostToDevice, st));
-            AO_HIP(hipMemcpyAsync(d_pos, pos.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
-            AO_TRY(launch_mt_normal<double>(d_mt, d_pos, d_nrm, ne, (int)(2 * N2), 0, (int)(2 * N2), st));
-            sa.n_env = ne;
+            AO_HIP(hipMemcpyAsync(g.mt, keys.data(), (size_t)ne * kMtN * 4, hipMemcpyHostToDevice, st));
+            AO_HIP(hipMemcpyAsync(g.pos, pos.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
+            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), ne, (int)(2 * N2), 0, (int)(2 * N2), st));
+            g.sa.n_env = ne;
             char* map = static_cast<char*>(env->screen_ptr(l)) + (size_t)e0 * S * S * env->esz;
-            if (env->esz == 4) AO_TRY(launch_screen<float>(sa, reinterpret_cast<float*>(map), S, st));
-            else AO_TRY(launch_screen<double>(sa, reinterpret_cast<double*>(map), S, st));
+            if (env->esz == 4) AO_TRY(launch_screen<float>(g.sa, reinterpret_cast<float*>(map), S, st));
+            else AO_TRY(launch_screen<double>(g.sa, reinterpret_cast<double*>(map), S, st));
             AO_HIP(hipStreamSynchronize(st));                      // keys / pos are reused by the next chunk
         }
     }
     return finish_new_screens(env, h_ring_seeds, st);
+}
+
+extern "C++" {
+// the part of aoenv_reset_envs behind the validation and the switch to per-env clocks, everything on the stream: the listed envs'
+// rows cleared, their screens drawn, their ring streams seeded, their first ring extruded -- every launch over the device list
+// d_idx (n entries) except the ring GEMM, which runs over the whole shard as on a per-env-clock step: its split count and the order
+// of its sums are then those of the full reset whatever the list (the rows of the other envs are computed and never used).
+template <typename T>
+static int reset_listed_envs(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const uint32_t* d_ring_seeds,
+                             double r0, double L0, double pixel_size, TmpFree& tmp, hipStream_t st) {
+    const int E = env->E, L = env->L;
+    AO_TRY(launch_reset_env_rows<T>(d_idx, n, env->as<T>(env->coefs), env->as<T>(env->dm_prev), env->A, env->env_clk[env->clk_cur],
+                                    env->env_taps, L, E, st));
+    AO_TRY(refresh_dense_dm<T>(env, st));
+    const int N = env->layer[0].N, S = env->layer[0].S;           // (one grid: layers on grids of their own are refused)
+    const size_t N2 = (size_t)N * N;
+    ScreenGen g;
+    AO_TRY(make_screen_gen(tmp, N, n, r0, L0, pixel_size, &g));
+    for (int l = 0; l < L; ++l)
+        for (int c0 = 0; c0 < n; c0 += g.ec) {                    // (the scratch is reused in stream order: no host wait in between)
+            const int nc = std::min(g.ec, n - c0);
+            AO_TRY(launch_mt_seed(d_screen_seeds + (size_t)c0 * L + l, L, nullptr, g.mt, g.pos, nc, st));
+            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), nc, (int)(2 * N2), 0, (int)(2 * N2), st));
+            g.sa.n_env = nc;
+            AO_TRY(launch_screen<T>(g.sa, env->as<T>(env->screen_ptr(l)), S, st, d_idx + c0));
+        }
+    T* zx = env->as<T>(env->zx);
+    for (int l = 0; l < L; ++l) {
+        Layer& y = env->layer[l];
+        AO_TRY(launch_mt_seed(d_ring_seeds + l, L, d_idx, y.mt_cur, y.pos_cur, n, st));
+        AO_TRY(launch_ring_prepare_idx<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, d_idx, n, y.S, y.nin,
+                                          y.nout, y.K, st));
+        int splits = 1;
+        AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
+        env->last_zx = zx;
+        env->last_zx_layer = l;
+        AO_TRY(launch_scatter_minmax_idx<T>(env->as<T>(env->screen_ptr(l)), env->as<T>(env->xbuf_ptr(l)), y.outer_idx,
+                                            env->as<T>(env->minmax_ptr(l)), d_idx, n, E, y.S, y.nout, splits, st));
+    }
+    env->atm_user_defined = false;
+    return run_phase<T>(env, 1, 1, st);                            // atm.OPD and the residual phase from the screens as they are now
+}
+}  // extern "C++"
+
+int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds,
+                     double r0, double L0, double pixel_size, void* stream) {
+    AO_CHECK_ENV(env);
+    if (n_idx < 0) return fail("aoenv_reset_envs: n_idx = %d", n_idx);
+    if (n_idx == 0) return 0;
+    if (!h_env_idx || !h_screen_seeds || !h_ring_seeds) return fail("aoenv_reset_envs: null index list / seeds");
+    if (env->L == 0) return fail("no atmosphere in this shard");
+    if (!env->uniform)
+        return fail("aoenv_reset_envs: layers on grids of their own (AoCfg.layer_res_l: fov != 0 with altitude layers) have no per-env clocks; "
+                    "reset the whole shard (aoenv_new_screens_device)");
+    AO_TRY(require_step_constants(env, true));
+    if (!(r0 > 0) || !(L0 > 0) || !(pixel_size > 0)) return fail("r0, L0 and the pixel size must be positive");
+    const int E = env->E, L = env->L;
+    std::vector<char> seen((size_t)E, 0);
+    for (int c = 0; c < n_idx; ++c) {
+        const int e = h_env_idx[c];
+        if (e < 0 || e >= E) return fail("aoenv_reset_envs: env index %d outside [0, n_env=%d)", e, E);
+        if (seen[e]) return fail("aoenv_reset_envs: env index %d is listed twice", e);
+        seen[e] = 1;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!env->per_env_wind) {
+        // One env restarted at origin 0 cannot share an origin with the others: per-env clocks from here on, every env where the shard
+        // is (origin, accumulator) with the shard's wind.  aoenv_set_wind_env forgets the look-aheads and scatters a pending ring first.
+        std::vector<double> r((size_t)L * E * 2);
+        for (int l = 0; l < L; ++l) {
+            const LayerClock& k = env->layer[l].clk;
+            if (!(std::fabs(k.ratio[0]) < 1.0) || !(std::fabs(k.ratio[1]) < 1.0))
+                return fail("aoenv_reset_envs: the shard's wind is %g px/frame in layer %d; per-env clocks take < 1", std::max(std::fabs(k.ratio[0]), std::fabs(k.ratio[1])), l);
+            for (int e = 0; e < E; ++e) {
+                r[2 * ((size_t)l * E + e)] = k.ratio[0];
+                r[2 * ((size_t)l * E + e) + 1] = k.ratio[1];
+            }
+        }
+        AO_TRY(aoenv_set_wind_env(env, r.data(), 0, stream));
+    } else {
+        for (int l = 0; l < L; ++l) forget_lookahead(env->layer[l]);
+        AO_TRY(AO_DISPATCH(env, flush_rings, env, st));            // a deferred ring of the clocks as they were
+        AO_HIP(hipStreamSynchronize(st));
+    }
+    // the list and the seeds in one upload: [n_idx] indices, [n_idx][L] screen seeds, [n_idx][L] ring seeds
+    TmpFree tmp;
+    const size_t ns = (size_t)n_idx * L;
+    std::vector<uint32_t> pack((size_t)n_idx + 2 * ns);
+    memcpy(pack.data(), h_env_idx, (size_t)n_idx * 4);
+    memcpy(pack.data() + n_idx, h_screen_seeds, ns * 4);
+    memcpy(pack.data() + n_idx + ns, h_ring_seeds, ns * 4);
+    uint32_t* d_pack = nullptr;
+    AO_TRY(tmp.get((void**)&d_pack, pack.size() * 4));
+    AO_HIP(hipMemcpy(d_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
+    const int* d_idx = reinterpret_cast<const int*>(d_pack);
+    return AO_DISPATCH(env, reset_listed_envs, env, d_idx, n_idx, d_pack + n_idx, d_pack + n_idx + ns, r0, L0, pixel_size, tmp, st);
 }
 
 int aoenv_set_atm_opd(AoEnv* env, const double* h_opd, void* stream) {

@@ -69,9 +69,10 @@ __global__ void __launch_bounds__(256) k_screen_cols(const ScreenArgs a) {
     }
 }
 
-// sub-harmonics + mean removal + sum, one workgroup per env; writes layer.phase into the interior of mapShift
+// sub-harmonics + mean removal + sum, one workgroup per env; writes layer.phase into the interior of mapShift.  env_idx: the
+// destination map of generated env e is chosen through the list (partial reset: the scratch is compact, the screens are not)
 template <typename T>
-__global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* __restrict__ map, int S) {
+__global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* __restrict__ map, int S, const int* __restrict__ env_idx) {
     __shared__ double red[16];
     __shared__ double cr[12], ci[12];
     const int N = a.N, e = blockIdx.x;
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* _
     double mean = 0;
     for (int w = 0; w < (int)blockDim.x / kWave; ++w) mean += red[w];
     mean /= (double)N * N;
-    T* m = map + (size_t)e * S * S;
+    T* m = map + (size_t)(env_idx ? env_idx[e] : e) * S * S;
     for (int q = threadIdx.x; q < N * N; q += blockDim.x) {
         const int y = q / N, x = q - y * N;
         const double xc = (x - N / 2.0) * a.delta, yc = (y - N / 2.0) * a.delta;
@@ -122,7 +123,7 @@ __global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* _
 }
 
 template <typename T>
-int launch_screen(const ScreenArgs& base, T* map, int S, hipStream_t st) {
+int launch_screen(const ScreenArgs& base, T* map, int S, hipStream_t st, const int* env_idx) {
     ScreenArgs a = base;
     const int N = a.N;
     const int NP = a.plan.np;
@@ -137,12 +138,12 @@ int launch_screen(const ScreenArgs& base, T* map, int S, hipStream_t st) {
     }
     hipLaunchKernelGGL(k_screen_rows, dim3(cdiv(N, rb), a.n_env), dim3(256), lds, st, a);
     hipLaunchKernelGGL(k_screen_cols, dim3(cdiv(N, rb), a.n_env), dim3(256), lds, st, a);
-    hipLaunchKernelGGL(k_screen_finish<T>, dim3(a.n_env), dim3(1024), 0, st, a, map, S);
+    hipLaunchKernelGGL(k_screen_finish<T>, dim3(a.n_env), dim3(1024), 0, st, a, map, S, env_idx);
     AO_HIP(hipGetLastError());
     return 0;
 }
 
-template int launch_screen<float>(const ScreenArgs&, float*, int, hipStream_t);
-template int launch_screen<double>(const ScreenArgs&, double*, int, hipStream_t);
+template int launch_screen<float>(const ScreenArgs&, float*, int, hipStream_t, const int*);
+template int launch_screen<double>(const ScreenArgs&, double*, int, hipStream_t, const int*);
 
 }  // namespace ao

@@ -35,6 +35,38 @@ def _torch():
     return torch
 
 
+def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
+    """The envs a partial reset names, as a sorted unique ``int32`` array.  ``env_ids``: a 1-D integer sequence / array / tensor
+    (each id in ``[0, n_envs)``, none twice, any order) or a boolean mask of length ``n_envs``.  Raises ``ValueError`` for an input
+    that is not 1-D, ids out of range, duplicates, a mask of the wrong length or a non-integer dtype.  ``return_order``: also the
+    ids in the caller's order (a mask: ascending), to pair per-env arguments and results with them.  Pure host code."""
+    n_envs = int(n_envs)
+    if hasattr(env_ids, "detach"):                                  # a torch tensor, wherever it lives
+        env_ids = env_ids.detach().cpu().numpy()
+    elif isinstance(env_ids, range):
+        env_ids = list(env_ids)
+    a = np.asarray(env_ids)
+    if a.ndim != 1:
+        raise ValueError(f"env_ids must be 1-D, got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if a.shape[0] != n_envs:
+            raise ValueError(f"a boolean env mask must have length n_envs={n_envs}, got {a.shape[0]}")
+        given = np.flatnonzero(a).astype(np.int32)
+    elif a.size == 0:
+        given = np.zeros(0, dtype=np.int32)
+    else:
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"env_ids must be integers or a boolean mask, got dtype {a.dtype}")
+        if a.min() < 0 or a.max() >= n_envs:
+            bad = a[(a < 0) | (a >= n_envs)][0]
+            raise ValueError(f"env id {int(bad)} outside [0, n_envs={n_envs})")
+        given = a.astype(np.int32)
+    ids = np.unique(given)
+    if ids.size != given.size:
+        raise ValueError("env_ids lists an env twice")
+    return (ids, given) if return_order else ids
+
+
 class Shard:
     """One AoEnv handle of libaoenv (a shard of independent loops on one GPU)."""
 
@@ -95,6 +127,14 @@ class Shard:
         k = np.ascontiguousarray(ring_seeds, dtype=np.uint32)
         L.check(self.lib.aoenv_new_screens_device(self.h, a.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p),
                                                   float(r0), float(L0), float(pixel_size), C.c_void_p(stream)))
+
+    def reset_envs(self, env_idx, screen_seeds, ring_seeds, r0, L0, pixel_size, stream=0):
+        """aoenv_reset_envs: seeds [len(env_idx)][n_layer], row c for env env_idx[c]."""
+        i = np.ascontiguousarray(env_idx, dtype=np.int32)
+        a = np.ascontiguousarray(screen_seeds, dtype=np.uint32)
+        k = np.ascontiguousarray(ring_seeds, dtype=np.uint32)
+        L.check(self.lib.aoenv_reset_envs(self.h, i.ctypes.data_as(C.c_void_p), int(i.size), a.ctypes.data_as(C.c_void_p),
+                                          k.ctypes.data_as(C.c_void_p), float(r0), float(L0), float(pixel_size), C.c_void_p(stream)))
 
     def set_atm_opd(self, opd, stream=0):
         a = None if opd is None else np.ascontiguousarray(opd, dtype=np.float64)
@@ -757,6 +797,51 @@ class BatchedAOEnv:
     def measure(self):
         """tel*dm*wfs: one WFS measurement of (atmosphere + DM), no turbulence update."""
         self._shard.measure(self._stream())
+
+    def reset_envs(self, env_ids, seed=None):
+        """A new episode for SOME envs (``aoenv_reset_envs``): what ``generate_new_phase_screen(seed); dm.coefs = 0; dm_prev = 0;
+        measure(); reset_soft()`` does for the whole batch, for the listed envs only -- a diverged loop restarted on its own,
+        staggered episodes, autoreset.  Every other env's screens, streams, clocks and commands stay as they are.
+
+        ``env_ids``: 1-D integer sequence / tensor or a boolean mask of length ``n_envs`` (``normalize_env_ids``).  ``seed``: an int
+        -- env e gets the seed ``generate_new_phase_screen(seed)`` would give it, ``env_seeds(seed)[e]`` (layer l: screen seed + l,
+        ring seed + 1000 l); or an array with one seed per listed env, in the order of ``env_ids`` (a mask: ascending); None: the
+        wall clock, as ``generate_new_phase_screen`` does.  Returns the ``reset_soft()`` observations of the listed envs,
+        ``[k, nAct, nAct]`` in the order of ``env_ids``, as a new tensor (``output='numpy'``: the one env's array); the same rows are
+        put into the env's retained last observation (``get_state``).  Tensors handed out earlier are not written to: the
+        observation a caller holds for the other envs stays valid.
+
+        The shard runs per-env clocks from here on (see ``set_wind_per_env``; per-env winds set earlier are kept).  The
+        measurement behind the returned observation is ONE ``measure()`` of the whole shard: it consumes one camera frame number
+        for every env.  With a noisy camera the untouched envs therefore continue like a twin that called ``measure()`` at this
+        point, not like one that did not; with the ideal camera there is no difference."""
+        import time as _t
+        torch = _torch()
+        ids, given = normalize_env_ids(env_ids, self.n_envs, return_order=True)
+        k, A_ = int(ids.size), self.nActuator
+        if k == 0:
+            return torch.empty((0, A_, A_), device=self.device, dtype=self.tdtype)
+        if seed is None:
+            t = _t.localtime()
+            seed = t.tm_hour * 3600 + t.tm_min * 60 + t.tm_sec
+        if np.ndim(seed) == 0:
+            seeds = np.asarray(self.env_seeds(int(seed)))[given]
+        else:
+            seeds = np.asarray(seed)
+            if seeds.shape != (k,) or not np.issubdtype(seeds.dtype, np.integer):
+                raise ValueError(f"seed must be an int or {k} integers, one per listed env")
+        p, at = self.param, self._atm_tables
+        scr = np.array([[(int(s) + l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32).reshape(k, p.nLayer)
+        ring = np.array([[(int(s) + 1000 * l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32).reshape(k, p.nLayer)
+        self._shard.reset_envs(given, scr, ring, p.r0, p.L0, at.layer_D / at.N, self._stream())
+        self._per_env_clock = True
+        self.measure()
+        scratch = torch.empty_like(self._obs)
+        L.check(self._shard.lib.aoenv_reset_soft(self._shard.h, C.c_void_p(scratch.data_ptr()), C.c_void_p(self._stream())))
+        sel = torch.as_tensor(given.astype(np.int64), device=self.device)
+        rows = scratch.index_select(0, sel)
+        self._obs = self._obs.index_copy(0, sel, rows)              # (out of place: the old tensor may be in a caller's hands)
+        return self._out(rows)
 
     # -- the reference surface ------------------------------------------------------------------------------
     def _out(self, t):

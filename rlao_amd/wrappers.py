@@ -12,6 +12,28 @@ def _torch():
     return torch
 
 
+def _env_rows(env, env_ids):
+    """The listed envs in the caller's order (``normalize_env_ids`` checks them), as a host int64 array."""
+    from .env import normalize_env_ids
+    return normalize_env_ids(env_ids, getattr(env, "n_envs", 1), return_order=True)[1].astype("int64")
+
+
+def _with_rows_cleared(buffered, rows):
+    """Copies of the buffered actions with the rows of the listed envs zeroed (the buffered tensors are the caller's own)."""
+    out = []
+    for a in buffered:
+        if hasattr(a, "clone"):
+            a = a.clone()
+            if a.dim() == 3:
+                a[_torch().as_tensor(rows, device=a.device)] = 0
+            elif len(rows):
+                a.zero_()
+        else:                                                       # the single-env NumPy flavour: one image
+            a = a * 0 if len(rows) else a.copy()
+        out.append(a)
+    return out
+
+
 class TorchWrapper:
     def __init__(self, env):
         self._env = env
@@ -34,6 +56,9 @@ class TorchWrapper:
 
     def reset_soft(self):
         return _torch().as_tensor(self._env.reset_soft(), dtype=_torch().float32)
+
+    def reset_envs(self, env_ids, seed=None):
+        return _torch().as_tensor(self._env.reset_envs(env_ids, seed), dtype=_torch().float32)
 
 
 class TimeDelayEnv:
@@ -67,6 +92,13 @@ class TimeDelayEnv:
     def reset_soft(self):
         obs = self._env.reset_soft()
         self._fill()
+        return obs
+
+    def reset_envs(self, env_ids, seed=None):
+        """A new episode for the listed envs (``BatchedAOEnv.reset_envs``): their rows of the delayed actions are cleared too."""
+        rows = _env_rows(self._env, env_ids)
+        obs = self._env.reset_envs(env_ids, seed)
+        self.action_buffer = _with_rows_cleared(self.action_buffer, rows)
         return obs
 
     def step(self, i, action):
@@ -176,6 +208,27 @@ class HistoryEnv:
         self.t = 0
         self._push(obs)
         return self._out(), {}
+
+    def reset_envs(self, env_ids, seed=None):
+        """``reset()`` for the listed envs only (``BatchedAOEnv.reset_envs``): new turbulence, flat DM and one measurement for them;
+        their history rows restart as ``reset()`` starts the whole batch -- empty but for the new observation in the newest slot -- and
+        their rows of the delayed actions are cleared.  The other envs' histories, and the frame counter, go on.  Returns the windows
+        of the listed envs ``[k, n_history, nAct, nAct]`` in the order of ``env_ids``: a fresh tensor (a NumPy array for the single-env
+        flavour), not a view of the ring buffer."""
+        torch = _torch()
+        h = self._hist
+        rows = _env_rows(self._env, env_ids)
+        obs = torch.as_tensor(self._env.reset_envs(env_ids, seed), dtype=torch.float32, device=h.buf.device)
+        if obs.dim() == 2:
+            obs = obs.unsqueeze(0)
+        sel = torch.as_tensor(rows, device=h.buf.device)
+        h.buf[sel] = 0
+        if len(rows):
+            h.buf[sel, h.p] = obs
+            h.buf[sel, h.p + h.H] = obs
+        self.action_buffer = _with_rows_cleared(self.action_buffer, rows)
+        win = h.window()[sel]                                       # (advanced indexing: a copy)
+        return win.cpu().numpy() if self.single else win
 
     def _push(self, obs):
         torch = _torch()
