@@ -11,25 +11,27 @@ __global__ void __launch_bounds__(256) k_mt_normal(uint32_t* __restrict__ mt_sta
     mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, blockIdx.x);
 }
 
-// One launch for the two independent halves of the ring operand [Z | xi] of env blockIdx.y:
-// blockIdx.x == 0 gathers Z, blockIdx.x == 1 draws the n_outer innovations xi of the layer's MT19937 stream.
+// One launch for the two independent halves of the ring operand [Z | xi] of an env: blockIdx.x == 0 gathers Z, blockIdx.x == 1 draws
+// the n_outer innovations xi of the layer's MT19937 stream.  The env is blockIdx.y, or env_idx[blockIdx.y] of a device index list
+// (the partial reset, aoenv_reset_envs); null list: row c is env c, as everywhere a list is taken.
 template <typename T>
 __global__ void __launch_bounds__(256) k_ring_prepare(const T* __restrict__ map, T* __restrict__ zx,
                                                       const int* __restrict__ inner_idx, const uint32_t* mt_state,
                                                       const int* mt_pos, uint32_t* mt_state_out, int* mt_pos_out, int S,
-                                                      int n_inner, int n_outer, int K, int sx, int sy, int oy, int ox) {
-    const int e = blockIdx.y;
+                                                      int n_inner, int n_outer, int K, int sx, int sy, int oy, int ox,
+                                                      const int* __restrict__ env_idx) {
+    const int e = env_idx ? env_idx[blockIdx.y] : blockIdx.y;
     if (blockIdx.x == 0) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, sx, sy, oy, ox, e, threadIdx.x, 256);
     else mt_normal_body<T>(mt_state, mt_pos, mt_state_out, mt_pos_out, zx, K, n_inner, n_outer, e);
 }
 
 template <typename T>
 int launch_ring_prepare(const T* map, T* zx, const int* inner_idx, const uint32_t* mt_state, const int* mt_pos,
-                        uint32_t* mt_state_out, int* mt_pos_out, int n_env, int S, int n_inner, int n_outer, int K, int sx, int sy,
-                        int oy, int ox, hipStream_t st) {
+                        uint32_t* mt_state_out, int* mt_pos_out, const int* env_idx, int n, int S, int n_inner, int n_outer, int K,
+                        int sx, int sy, int oy, int ox, hipStream_t st) {
     if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
-    hipLaunchKernelGGL(k_ring_prepare<T>, dim3(2, n_env), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, mt_state_out,
-                       mt_pos_out, S, n_inner, n_outer, K, sx, sy, oy, ox);
+    hipLaunchKernelGGL(k_ring_prepare<T>, dim3(2, n), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, mt_state_out,
+                       mt_pos_out, S, n_inner, n_outer, K, sx, sy, oy, ox, env_idx);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -92,7 +94,8 @@ int launch_mt_normal(uint32_t* mt_state, int* mt_pos, T* zx, int n_env, int K, i
 // ---------------------------------------------------------------------------------------------------
 // add_row, part 3: map_full[outerMask] = X through the NEW origin (+ min / max of the whole new map, which the
 // sub-pixel warp clips its output to: skimage clip=True; with_minmax = 0 leaves that to the consumer -- the fused
-// step kernel recomputes it from the map it reads anyway).  One workgroup per env.
+// step kernel recomputes it from the map it reads anyway).  One workgroup per env: env blockIdx.x, or env_idx[blockIdx.x] of a
+// device index list (the partial reset); X is always the product over the WHOLE shard (slab = n_env * n_outer).
 // ---------------------------------------------------------------------------------------------------
 template <typename T>
 __device__ inline void block_minmax(const T* __restrict__ map, T* __restrict__ minmax, int S, int e) {
@@ -137,8 +140,9 @@ template <typename T>
 __global__ void __launch_bounds__(1024) k_scatter_minmax(T* __restrict__ new_map, const T* __restrict__ X,
                                                          const int* __restrict__ outer_idx, T* __restrict__ minmax,
                                                          int S, int n_outer, int splits, size_t slab, int oy, int ox,
-                                                         int with_minmax, const LayerTaps* __restrict__ env_taps) {
-    const int e = blockIdx.x;
+                                                         int with_minmax, const LayerTaps* __restrict__ env_taps,
+                                                         const int* __restrict__ env_idx) {
+    const int e = env_idx ? env_idx[blockIdx.x] : blockIdx.x;
     if (env_taps) {                                                // per-env clocks: only the envs that crossed, through their origin
         if (!env_taps[e].ring) return;
         oy = env_taps[e].oy;
@@ -158,10 +162,10 @@ __global__ void __launch_bounds__(1024) k_scatter_minmax(T* __restrict__ new_map
 }
 
 template <typename T>
-int launch_scatter_minmax(T* new_map, const T* X, const int* outer_idx, T* minmax, int n_env, int S, int n_outer,
-                          int splits, int oy, int ox, int with_minmax, hipStream_t st, const LayerTaps* env_taps) {
-    hipLaunchKernelGGL(k_scatter_minmax<T>, dim3(n_env), dim3(with_minmax ? 1024 : 512), 0, st, new_map, X, outer_idx, minmax, S,
-                       n_outer, splits, (size_t)n_env * n_outer, oy, ox, with_minmax, env_taps);
+int launch_scatter_minmax(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n, int n_env, int S,
+                          int n_outer, int splits, int oy, int ox, int with_minmax, hipStream_t st, const LayerTaps* env_taps) {
+    hipLaunchKernelGGL(k_scatter_minmax<T>, dim3(n), dim3(with_minmax ? 1024 : 512), 0, st, new_map, X, outer_idx, minmax, S,
+                       n_outer, splits, (size_t)n_env * n_outer, oy, ox, with_minmax, env_taps, env_idx);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -180,9 +184,9 @@ int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Partial reset (aoenv_reset_envs): the same work for the envs of a device index list only.  Workgroup c of a launch serves env
-// env_idx[c]; every listed env is at origin 0 with an empty accumulator (k_reset_env_rows), so the first ring is the extrusion
-// (sx, sy) = (0, 0) of the full reset, kernel for kernel: the same gather, the same draw, the same sum of the slabs.
+// Episode reset.  The full reset (null index list) and the partial one (aoenv_reset_envs: a device index list, workgroup c of a
+// launch serves env env_idx[c]) run the same launches: k_mt_seed, the screen generator, k_ring_prepare and k_scatter_minmax at
+// origin 0.  What only the partial reset needs is k_reset_env_rows.
 // ---------------------------------------------------------------------------------------------------
 // RandomState(seed): init_genrand of MT19937 (NumPy's legacy seeding), one lane per stream; stream c is seeded with seeds[c * stride]
 // and stored in row env_idx[c] (env_idx null: row c) with its position at the end of the block (the first draw twists)
@@ -239,64 +243,16 @@ int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, i
     return 0;
 }
 
-// k_ring_prepare of the listed envs at origin 0, no shift: Z of the new interior, xi from the stream just seeded (in place)
-template <typename T>
-__global__ void __launch_bounds__(256) k_ring_prepare_idx(const T* __restrict__ map, T* __restrict__ zx, const int* __restrict__ inner_idx,
-                                                          uint32_t* mt_state, int* mt_pos, const int* __restrict__ env_idx, int S,
-                                                          int n_inner, int n_outer, int K) {
-    const int e = env_idx[blockIdx.y];
-    if (blockIdx.x == 0) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, 0, 0, 0, 0, e, threadIdx.x, 256);
-    else mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, e);
-}
-
-template <typename T>
-int launch_ring_prepare_idx(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const int* env_idx, int n_idx,
-                            int S, int n_inner, int n_outer, int K, hipStream_t st) {
-    if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
-    hipLaunchKernelGGL(k_ring_prepare_idx<T>, dim3(2, n_idx), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, env_idx, S, n_inner,
-                       n_outer, K);
-    AO_HIP(hipGetLastError());
-    return 0;
-}
-
-// k_scatter_minmax of the listed envs at origin 0, with the min / max pass; X is the product over the WHOLE shard (slab = n_env * n_outer)
-template <typename T>
-__global__ void __launch_bounds__(1024) k_scatter_minmax_idx(T* __restrict__ new_map, const T* __restrict__ X,
-                                                             const int* __restrict__ outer_idx, T* __restrict__ minmax,
-                                                             const int* __restrict__ env_idx, int S, int n_outer, int splits, size_t slab) {
-    const int e = env_idx[blockIdx.x];
-    T* map = new_map + (size_t)e * S * S;
-    const T* x = X + (size_t)e * n_outer;
-    for (int k = threadIdx.x; k < n_outer; k += blockDim.x) {
-        T v = x[k];
-        for (int z = 1; z < splits; ++z) v += x[(size_t)z * slab + k];       // split-K slabs, fixed order
-        map[outer_idx[k]] = v;
-    }
-    __syncthreads();
-    block_minmax<T>(map, minmax, S, e);
-}
-
-template <typename T>
-int launch_scatter_minmax_idx(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n_idx, int n_env, int S,
-                              int n_outer, int splits, hipStream_t st) {
-    hipLaunchKernelGGL(k_scatter_minmax_idx<T>, dim3(n_idx), dim3(1024), 0, st, new_map, X, outer_idx, minmax, env_idx, S, n_outer, splits,
-                       (size_t)n_env * n_outer);
-    AO_HIP(hipGetLastError());
-    return 0;
-}
-
 #define INST(T)                                                                                                    \
-    template int launch_ring_prepare<T>(const T*, T*, const int*, const uint32_t*, const int*, uint32_t*, int*, int, int, int, \
-                                        int, int, int, int, int, int, hipStream_t);                                \
+    template int launch_ring_prepare<T>(const T*, T*, const int*, const uint32_t*, const int*, uint32_t*, int*, const int*, int, int, \
+                                        int, int, int, int, int, int, int, hipStream_t);                           \
     template int launch_mt_normal<T>(uint32_t*, int*, T*, int, int, int, int, hipStream_t);                        \
-    template int launch_scatter_minmax<T>(T*, const T*, const int*, T*, int, int, int, int, int, int, int,         \
+    template int launch_scatter_minmax<T>(T*, const T*, const int*, T*, const int*, int, int, int, int, int, int, int, int, \
                                           hipStream_t, const LayerTaps*);                                          \
     template int launch_ring_prepare_env<T>(const T*, T*, const int*, uint32_t*, int*, const EnvClock*, EnvClock*, LayerTaps*, \
                                             double, int, int, int, int, int, hipStream_t);                                                          \
     template int launch_minmax<T>(const T*, T*, int, int, hipStream_t);                                            \
-    template int launch_reset_env_rows<T>(const int*, int, T*, T*, int, EnvClock*, LayerTaps*, int, int, hipStream_t); \
-    template int launch_ring_prepare_idx<T>(const T*, T*, const int*, uint32_t*, int*, const int*, int, int, int, int, int, hipStream_t); \
-    template int launch_scatter_minmax_idx<T>(T*, const T*, const int*, T*, const int*, int, int, int, int, int, hipStream_t);
+    template int launch_reset_env_rows<T>(const int*, int, T*, T*, int, EnvClock*, LayerTaps*, int, int, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

@@ -120,31 +120,26 @@ struct Env;  // host object, env.hpp
 
 template <typename T>
 int launch_ring_prepare(const T* map, T* zx, const int* inner_idx, const uint32_t* mt_state, const int* mt_pos,
-                        uint32_t* mt_state_out, int* mt_pos_out, int n_env, int S, int n_inner, int n_outer, int K, int sx, int sy,
-                        int oy, int ox, hipStream_t st);
+                        uint32_t* mt_state_out, int* mt_pos_out, const int* env_idx, int n, int S, int n_inner, int n_outer, int K,
+                        int sx, int sy, int oy, int ox, hipStream_t st);
 template <typename T>
 int launch_mt_normal(uint32_t* mt_state, int* mt_pos, T* zx, int n_env, int K, int n_inner, int n_outer,
                      hipStream_t st);
 template <typename T>
-int launch_scatter_minmax(T* new_map, const T* X, const int* outer_idx, T* minmax, int n_env, int S, int n_outer,
-                          int splits, int oy, int ox, int with_minmax, hipStream_t st, const LayerTaps* env_taps = nullptr);
+int launch_scatter_minmax(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n, int n_env, int S,
+                          int n_outer, int splits, int oy, int ox, int with_minmax, hipStream_t st, const LayerTaps* env_taps = nullptr);
 template <typename T>
 int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk_in,
                             EnvClock* clk_out, LayerTaps* taps, double weight, int n_env, int S, int n_inner, int n_outer, int K,
                             hipStream_t st);
 template <typename T>
 int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st);
-// partial reset (aoenv_reset_envs): the index-list forms, workgroup c of a launch serves env env_idx[c] (device list, n_idx entries)
+// device index lists (env_idx, n entries): workgroup / row c of a launch serves env env_idx[c]; a null list means env c -- the full
+// reset.  launch_ring_prepare and launch_scatter_minmax above take one too, beside the shard's n_env that strides the GEMM's slabs.
 int launch_mt_seed(const uint32_t* seeds, int stride, const int* env_idx, uint32_t* mt_state, int* mt_pos, int n, hipStream_t st);
 template <typename T>
 int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, int n_valid_act, EnvClock* clk, LayerTaps* taps,
                           int n_layer, int n_env, hipStream_t st);
-template <typename T>
-int launch_ring_prepare_idx(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const int* env_idx, int n_idx,
-                            int S, int n_inner, int n_outer, int K, hipStream_t st);
-template <typename T>
-int launch_scatter_minmax_idx(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n_idx, int n_env, int S,
-                              int n_outer, int splits, hipStream_t st);
 int gemm_splits(int M, int N, int K);
 // the draw of a layer's next innovations, run beside the ring GEMM (k_ring_gemm_draw_ahead)
 struct MtAhead {

@@ -4,7 +4,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
+#include <utility>
 
 #include "common.hpp"
 #include "detector.hpp"
@@ -224,13 +226,6 @@ int upload_real(AoEnv* env, void* dst, const double* src, size_t n) {
 
 double sgn(double v) { return (v > 0) - (v < 0); }
 
-void mt_seed(uint32_t seed, uint32_t* key) {          // numpy legacy mt19937_seed / init_genrand
-    for (int pos = 0; pos < kMtN; ++pos) {
-        key[pos] = seed;
-        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)pos + 1u;
-    }
-}
-
 template <typename T>
 ShConst<T> sh_const(const AoEnv* env) {
     ShConst<T> sc;
@@ -315,8 +310,8 @@ int scatter_ring(AoEnv* env, int l, const LayerTaps* et, bool with_minmax, hipSt
     Layer& y = env->layer[l];
     AO_PROF(env, SCATTER, st);
     AO_TRY(launch_scatter_minmax<T>(env->as<T>(env->screen_ptr(l)), static_cast<const T*>(y.ring_src), y.outer_idx,
-                                    env->as<T>(env->minmax_ptr(l)), env->E, y.S, y.nout, y.ring_pending, y.org[0], y.org[1],
-                                    with_minmax ? 1 : 0, st, et));
+                                    env->as<T>(env->minmax_ptr(l)), nullptr, env->E, env->E, y.S, y.nout, y.ring_pending, y.org[0],
+                                    y.org[1], with_minmax ? 1 : 0, st, et));
     y.ring_pending = 0;
     return 0;
 }
@@ -355,8 +350,8 @@ int extrude(AoEnv* env, int l, int sx, int sy, bool lean, hipStream_t st, bool d
     T* zx = env->as<T>(env->zx);
     {
         AO_PROF(env, SHIFT_GATHER, st);                           // Z gather + xi draw, one launch
-        AO_TRY(launch_ring_prepare<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, env->E,
-                                      y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
+        AO_TRY(launch_ring_prepare<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, nullptr,
+                                      env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
     }
     int splits = 1;
     AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
@@ -364,6 +359,34 @@ int extrude(AoEnv* env, int l, int sx, int sy, bool lean, hipStream_t st, bool d
     defer_ring(env, l, zx, splits);
     if (!(defer && lean)) AO_TRY(scatter_ring<T>(env, l, nullptr, !lean, st));
     y.minmax_dirty = lean;
+    return 0;
+}
+
+// The first ring of an episode (generateNewPhaseScreen, OOPAO/Atmosphere.py:579-585) of layer l for the n envs of the device list
+// d_idx (null: env c is row c, the whole shard): the extrusion (sx, sy) = (0, 0) at origin 0 from the stream just seeded, in place,
+// scattered with the min / max pass.  The callers have put those envs at origin 0 with no ring pending and no look-ahead.  The GEMM
+// runs over the whole shard whatever the list -- its split count and the order of its sums do not depend on it; the rows of the
+// other envs are computed and never used.
+template <typename T>
+int first_ring(AoEnv* env, int l, const int* d_idx, int n, hipStream_t st) {
+    Layer& y = env->layer[l];
+    T* zx = env->as<T>(env->zx);
+    T* map = env->as<T>(env->screen_ptr(l));
+    {
+        AO_PROF(env, SHIFT_GATHER, st);
+        AO_TRY(launch_ring_prepare<T>(map, zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, d_idx, n, y.S, y.nin, y.nout, y.K, 0, 0,
+                                      0, 0, st));
+    }
+    int splits = 1;
+    AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
+    env->last_zx = zx;
+    env->last_zx_layer = l;
+    {
+        AO_PROF(env, SCATTER, st);
+        AO_TRY(launch_scatter_minmax<T>(map, env->as<T>(env->xbuf_ptr(l)), y.outer_idx, env->as<T>(env->minmax_ptr(l)), d_idx, n, env->E,
+                                        y.S, y.nout, splits, 0, 0, 1, st));
+    }
+    if (!d_idx) y.minmax_dirty = false;                            // (a list leaves the other envs' range as stale as it was)
     return 0;
 }
 
@@ -411,7 +434,7 @@ int extrude_pipelined(AoEnv* env, int l, int sx, int sy, hipStream_t st) {
     } else {
         AO_PROF(env, SHIFT_GATHER, st);
         AO_TRY(launch_ring_prepare<float>(env->as<float>(env->screen_ptr(l)), op, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur,
-                                          env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
+                                          nullptr, env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
     }
     forget_lookahead(y);
     const int splits = gemm_splits(env->E, y.nout, y.K);
@@ -1388,16 +1411,22 @@ static int screens_replaced(AoEnv* env, bool reset_buff) {
     return reset_env_clocks(env, reset_buff);
 }
 
+// one wind per layer ([L][2]) as the [L][E][2] of aoenv_set_wind_env: the same wind for every env
+static std::vector<double> wind_for_every_env(const AoEnv* env, const double* ratio) {
+    std::vector<double> r((size_t)env->L * env->E * 2);
+    for (int l = 0; l < env->L; ++l)
+        for (int e = 0; e < env->E; ++e) {
+            r[2 * ((size_t)l * env->E + e)] = ratio[2 * l];
+            r[2 * ((size_t)l * env->E + e) + 1] = ratio[2 * l + 1];
+        }
+    return r;
+}
+
 int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff) {
     AO_CHECK_ENV(env);
     if (!h_ratio) return fail("null ratio");
     if (env->per_env_wind) {                                       // the shard keeps its per-env clocks: the same wind for every env
-        std::vector<double> r((size_t)env->L * env->E * 2);
-        for (int l = 0; l < env->L; ++l)
-            for (int e = 0; e < env->E; ++e) {
-                r[2 * ((size_t)l * env->E + e)] = h_ratio[2 * l];
-                r[2 * ((size_t)l * env->E + e) + 1] = h_ratio[2 * l + 1];
-            }
+        const std::vector<double> r = wind_for_every_env(env, h_ratio);
         // (this entry point has no stream argument: the caller may be stepping on a non-blocking stream, whose pending ring /
         //  clock work must be through before the clocks are pulled, changed and pushed back on the null stream)
         AO_HIP(hipDeviceSynchronize());
@@ -1426,23 +1455,43 @@ static int require_step_constants(AoEnv* env, bool atmosphere) {
     return 0;
 }
 
-// ring RandomState seeding, first ring X = A.Z + B.xi, atm.OPD: the part of generateNewPhaseScreen after the new interior is in
-// mapShift (OOPAO/Atmosphere.py:579-592); the callers have reset the tori and the accumulators (screens_replaced)
-static int finish_new_screens(AoEnv* env, const uint32_t* h_ring_seeds, hipStream_t st) {
-    const int E = env->E, L = env->L;
-    std::vector<uint32_t> keys((size_t)E * kMtN);
-    std::vector<int> pos((size_t)E, kMtN);
-    for (int l = 0; l < L; ++l) {
-        for (int e = 0; e < E; ++e) mt_seed(h_ring_seeds[(size_t)e * L + l], &keys[(size_t)e * kMtN]);
-        AO_HIP(hipMemcpy(env->layer[l].mt_cur, keys.data(), keys.size() * 4, hipMemcpyHostToDevice));
-        AO_HIP(hipMemcpy(env->layer[l].pos_cur, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+namespace {
+// Scratch of one reset, released on every exit path.  The resets return with the kernels that read it still queued on the stream:
+// hipFree waits for the device before it releases a buffer, which is what keeps this safe (a stream-ordered or pooled free would not).
+struct TmpFree {
+    std::vector<void*> p;
+    ~TmpFree() { for (void* q : p) (void)hipFree(q); }
+    int get(void** out, size_t bytes) {
+        AO_HIP(hipMalloc(out, bytes));
+        p.push_back(*out);
+        return 0;
     }
-    AO_HIP(hipStreamSynchronize(st));
-    for (int l = 0; l < L; ++l)                                    // the first ring: one extrusion of the whole shard at origin 0
-        AO_TRY(AO_DISPATCH(env, extrude, env, l, 0, 0, false, st));
-    AO_TRY(AO_DISPATCH(env, run_phase, env, 1, 1, st));            // fill_phase_support + set_OPD + atm*tel
+};
+
+// host arrays of 32-bit words (an index list, seeds) back to back in one scratch buffer, in one upload
+int upload_words(TmpFree& tmp, std::initializer_list<std::pair<const void*, size_t>> parts, uint32_t** d_out) {
+    std::vector<uint32_t> pack;
+    for (const auto& p : parts) pack.insert(pack.end(), static_cast<const uint32_t*>(p.first), static_cast<const uint32_t*>(p.first) + p.second);
+    AO_TRY(tmp.get((void**)d_out, pack.size() * 4));
+    AO_HIP(hipMemcpy(*d_out, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
     return 0;
 }
+}  // namespace
+
+extern "C++" {
+// ring RandomState seeding, first ring X = A.Z + B.xi, atm.OPD: the part of generateNewPhaseScreen after the new interior is in
+// mapShift (OOPAO/Atmosphere.py:579-592), for the n envs of the device list d_idx (null: the whole shard); d_ring_seeds is [n][L].
+// The callers have put those envs at origin 0 with an empty accumulator (screens_replaced / k_reset_env_rows).
+template <typename T>
+static int finish_new_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_ring_seeds, hipStream_t st) {
+    for (int l = 0; l < env->L; ++l) {
+        AO_TRY(launch_mt_seed(d_ring_seeds + l, env->L, d_idx, env->layer[l].mt_cur, env->layer[l].pos_cur, n, st));
+        AO_TRY(first_ring<T>(env, l, d_idx, n, st));
+    }
+    env->atm_user_defined = false;
+    return run_phase<T>(env, 1, 1, st);                            // fill_phase_support + set_OPD + atm*tel, from the screens as they are now
+}
+}  // extern "C++"
 
 int aoenv_new_screens(AoEnv* env, const double* h_screens, const uint32_t* h_ring_seeds, void* stream) {
     AO_CHECK_ENV(env);
@@ -1478,28 +1527,19 @@ int aoenv_new_screens(AoEnv* env, const double* h_screens, const uint32_t* h_rin
             layer_base += (size_t)E * N * N;
         }
     }
-    return finish_new_screens(env, h_ring_seeds, st);
+    TmpFree tmp;
+    uint32_t* d_ring_seeds = nullptr;
+    AO_TRY(upload_words(tmp, {{h_ring_seeds, (size_t)E * L}}, &d_ring_seeds));
+    return AO_DISPATCH(env, finish_new_screens, env, nullptr, E, d_ring_seeds, st);
 }
 
 namespace {
-struct TmpFree {                                   // scratch of one reset: released on every exit path
-    std::vector<void*> p;
-    ~TmpFree() { for (void* q : p) (void)hipFree(q); }
-    int get(void** out, size_t bytes) {
-        AO_HIP(hipMalloc(out, bytes));
-        p.push_back(*out);
-        return 0;
-    }
-};
-
 // von Karman spectrum of OOPAO/phaseStats.py:206-207 (l0 = 1e-10 m: the inner-scale roll-off is 1 in float64)
 double vk_psd(double f, double r0, double L0) {
     const double fm = 5.92 / 1e-10 / (2 * 3.14159265358979323846), f0 = 1.0 / L0;
     return 0.023 * std::pow(r0, -5.0 / 3) * std::exp(-((f / fm) * (f / fm))) / std::pow(f * f + f0 * f0, 11.0 / 6);
 }
-}  // namespace
 
-namespace {
 // Tables and scratch of the device screen generator for one grid size N and up to n_env envs at a time (chunks of `ec`)
 struct ScreenGen {
     ScreenArgs sa{};
@@ -1558,6 +1598,49 @@ int make_screen_gen(TmpFree& tmp, int N, int n_env, double r0, double L0, double
 }
 }  // namespace
 
+extern "C++" {
+// New interiors (OOPAO/Atmosphere.py:568-578) for the n envs of the device list d_idx (null: env c is row c, the whole shard), every
+// layer: RandomState(seed + layer) seeded on the device from d_screen_seeds [n][L], normal(size=(N, N)) drawn twice (real, imaginary
+// parts), the screen written into the env's map.  The generator works on a compact scratch of at most g.ec envs, reused chunk after
+// chunk in stream order (no host wait in between); its tables are rebuilt whenever a layer is on a grid of another size.
+template <typename T>
+static int draw_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, double r0, double L0, double pixel_size,
+                        TmpFree& tmp, hipStream_t st) {
+    const int L = env->L;
+    ScreenGen g;
+    for (int l = 0; l < L; ++l) {
+        const int N = env->layer[l].N, S = env->layer[l].S;
+        const int n2 = 2 * N * N;
+        if (N != g.sa.N) AO_TRY(make_screen_gen(tmp, N, n, r0, L0, pixel_size, &g));   // (every layer's tables when fov = 0)
+        for (int c0 = 0; c0 < n; c0 += g.ec) {
+            const int nc = std::min(g.ec, n - c0);
+            AO_TRY(launch_mt_seed(d_screen_seeds + (size_t)c0 * L + l, L, nullptr, g.mt, g.pos, nc, st));
+            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), nc, n2, 0, n2, st));
+            g.sa.n_env = nc;
+            T* map = env->as<T>(env->screen_ptr(l));
+            if (d_idx) AO_TRY(launch_screen<T>(g.sa, map, S, st, d_idx + c0));
+            else AO_TRY(launch_screen<T>(g.sa, map + (size_t)c0 * S * S, S, st));
+        }
+    }
+    return 0;
+}
+
+// An episode reset on the device, everything on the stream: the full one (d_idx null, n = n_env, behind screens_replaced) and the
+// partial one (aoenv_reset_envs, behind its validation and the switch to per-env clocks) are this sequence; the listed envs' state
+// rows are cleared first, which the full reset leaves alone.
+template <typename T>
+static int reset_on_device(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const uint32_t* d_ring_seeds, double r0,
+                           double L0, double pixel_size, TmpFree& tmp, hipStream_t st) {
+    if (d_idx) {
+        AO_TRY(launch_reset_env_rows<T>(d_idx, n, env->as<T>(env->coefs), env->as<T>(env->dm_prev), env->A, env->env_clk[env->clk_cur],
+                                        env->env_taps, env->L, env->E, st));
+        AO_TRY(refresh_dense_dm<T>(env, st));
+    }
+    AO_TRY(draw_screens<T>(env, d_idx, n, d_screen_seeds, r0, L0, pixel_size, tmp, st));
+    return finish_new_screens<T>(env, d_idx, n, d_ring_seeds, st);
+}
+}  // extern "C++"
+
 int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds, double r0,
                              double L0, double pixel_size, void* stream) {
     AO_CHECK_ENV(env);
@@ -1567,81 +1650,13 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
     if (!(r0 > 0) || !(L0 > 0) || !(pixel_size > 0)) return fail("r0, L0 and the pixel size must be positive");
     hipStream_t st = static_cast<hipStream_t>(stream);
     AO_HIP(hipStreamSynchronize(st));
-    const int E = env->E, L = env->L;
     AO_TRY(screens_replaced(env, true));
     TmpFree tmp;
-    int N_built = -1;
-    ScreenGen g;
-    std::vector<uint32_t> keys;
-    std::vector<int> pos;
-    for (int l = 0; l < L; ++l) {
-        const int N = env->layer[l].N, S = env->layer[l].S;
-        const size_t N2 = (size_t)N * N;
-        if (N != N_built) {                                        // tables of this grid size (every layer's when fov = 0)
-            AO_TRY(make_screen_gen(tmp, N, E, r0, L0, pixel_size, &g));
-            keys.assign((size_t)g.ec * kMtN, 0u);
-            pos.assign((size_t)g.ec, kMtN);
-            N_built = N;
-        }
-        const int EC = g.ec;
-        for (int e0 = 0; e0 < E; e0 += EC) {
-            const int ne = std::min(EC, E - e0);
-            // the layer's own RandomState(seed + layer) draws normal(size=(N, N)) twice (real, imaginary parts)
-            for (int e = 0; e < ne; ++e) mt_seed(h_screen_seeds[(size_t)(e0 + e) * L + l], &keys[(size_t)e * kMtN]);
-            AO_HIP(hipMemcpyAsync(g.mt, keys.data(), (size_t)ne * kMtN * 4, hipMemcpyHostToDevice, st));
-            AO_HIP(hipMemcpyAsync(g.pos, pos.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
-            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), ne, (int)(2 * N2), 0, (int)(2 * N2), st));
-            g.sa.n_env = ne;
-            char* map = static_cast<char*>(env->screen_ptr(l)) + (size_t)e0 * S * S * env->esz;
-            if (env->esz == 4) AO_TRY(launch_screen<float>(g.sa, reinterpret_cast<float*>(map), S, st));
-            else AO_TRY(launch_screen<double>(g.sa, reinterpret_cast<double*>(map), S, st));
-            AO_HIP(hipStreamSynchronize(st));                      // keys / pos are reused by the next chunk
-        }
-    }
-    return finish_new_screens(env, h_ring_seeds, st);
+    const size_t ns = (size_t)env->E * env->L;                     // [E][L] screen seeds, [E][L] ring seeds
+    uint32_t* d_seeds = nullptr;
+    AO_TRY(upload_words(tmp, {{h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_seeds));
+    return AO_DISPATCH(env, reset_on_device, env, nullptr, env->E, d_seeds, d_seeds + ns, r0, L0, pixel_size, tmp, st);
 }
-
-extern "C++" {
-// the part of aoenv_reset_envs behind the validation and the switch to per-env clocks, everything on the stream: the listed envs'
-// rows cleared, their screens drawn, their ring streams seeded, their first ring extruded -- every launch over the device list
-// d_idx (n entries) except the ring GEMM, which runs over the whole shard as on a per-env-clock step: its split count and the order
-// of its sums are then those of the full reset whatever the list (the rows of the other envs are computed and never used).
-template <typename T>
-static int reset_listed_envs(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const uint32_t* d_ring_seeds,
-                             double r0, double L0, double pixel_size, TmpFree& tmp, hipStream_t st) {
-    const int E = env->E, L = env->L;
-    AO_TRY(launch_reset_env_rows<T>(d_idx, n, env->as<T>(env->coefs), env->as<T>(env->dm_prev), env->A, env->env_clk[env->clk_cur],
-                                    env->env_taps, L, E, st));
-    AO_TRY(refresh_dense_dm<T>(env, st));
-    const int N = env->layer[0].N, S = env->layer[0].S;           // (one grid: layers on grids of their own are refused)
-    const size_t N2 = (size_t)N * N;
-    ScreenGen g;
-    AO_TRY(make_screen_gen(tmp, N, n, r0, L0, pixel_size, &g));
-    for (int l = 0; l < L; ++l)
-        for (int c0 = 0; c0 < n; c0 += g.ec) {                    // (the scratch is reused in stream order: no host wait in between)
-            const int nc = std::min(g.ec, n - c0);
-            AO_TRY(launch_mt_seed(d_screen_seeds + (size_t)c0 * L + l, L, nullptr, g.mt, g.pos, nc, st));
-            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), nc, (int)(2 * N2), 0, (int)(2 * N2), st));
-            g.sa.n_env = nc;
-            AO_TRY(launch_screen<T>(g.sa, env->as<T>(env->screen_ptr(l)), S, st, d_idx + c0));
-        }
-    T* zx = env->as<T>(env->zx);
-    for (int l = 0; l < L; ++l) {
-        Layer& y = env->layer[l];
-        AO_TRY(launch_mt_seed(d_ring_seeds + l, L, d_idx, y.mt_cur, y.pos_cur, n, st));
-        AO_TRY(launch_ring_prepare_idx<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, d_idx, n, y.S, y.nin,
-                                          y.nout, y.K, st));
-        int splits = 1;
-        AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
-        env->last_zx = zx;
-        env->last_zx_layer = l;
-        AO_TRY(launch_scatter_minmax_idx<T>(env->as<T>(env->screen_ptr(l)), env->as<T>(env->xbuf_ptr(l)), y.outer_idx,
-                                            env->as<T>(env->minmax_ptr(l)), d_idx, n, E, y.S, y.nout, splits, st));
-    }
-    env->atm_user_defined = false;
-    return run_phase<T>(env, 1, 1, st);                            // atm.OPD and the residual phase from the screens as they are now
-}
-}  // extern "C++"
 
 int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds,
                      double r0, double L0, double pixel_size, void* stream) {
@@ -1667,17 +1682,15 @@ int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint
     if (!env->per_env_wind) {
         // One env restarted at origin 0 cannot share an origin with the others: per-env clocks from here on, every env where the shard
         // is (origin, accumulator) with the shard's wind.  aoenv_set_wind_env forgets the look-aheads and scatters a pending ring first.
-        std::vector<double> r((size_t)L * E * 2);
+        double shard[2 * kMaxLayer];
         for (int l = 0; l < L; ++l) {
             const LayerClock& k = env->layer[l].clk;
             if (!(std::fabs(k.ratio[0]) < 1.0) || !(std::fabs(k.ratio[1]) < 1.0))
                 return fail("aoenv_reset_envs: the shard's wind is %g px/frame in layer %d; per-env clocks take < 1", std::max(std::fabs(k.ratio[0]), std::fabs(k.ratio[1])), l);
-            for (int e = 0; e < E; ++e) {
-                r[2 * ((size_t)l * E + e)] = k.ratio[0];
-                r[2 * ((size_t)l * E + e) + 1] = k.ratio[1];
-            }
+            shard[2 * l] = k.ratio[0];
+            shard[2 * l + 1] = k.ratio[1];
         }
-        AO_TRY(aoenv_set_wind_env(env, r.data(), 0, stream));
+        AO_TRY(aoenv_set_wind_env(env, wind_for_every_env(env, shard).data(), 0, stream));
     } else {
         for (int l = 0; l < L; ++l) forget_lookahead(env->layer[l]);
         AO_TRY(AO_DISPATCH(env, flush_rings, env, st));            // a deferred ring of the clocks as they were
@@ -1686,15 +1699,10 @@ int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint
     // the list and the seeds in one upload: [n_idx] indices, [n_idx][L] screen seeds, [n_idx][L] ring seeds
     TmpFree tmp;
     const size_t ns = (size_t)n_idx * L;
-    std::vector<uint32_t> pack((size_t)n_idx + 2 * ns);
-    memcpy(pack.data(), h_env_idx, (size_t)n_idx * 4);
-    memcpy(pack.data() + n_idx, h_screen_seeds, ns * 4);
-    memcpy(pack.data() + n_idx + ns, h_ring_seeds, ns * 4);
     uint32_t* d_pack = nullptr;
-    AO_TRY(tmp.get((void**)&d_pack, pack.size() * 4));
-    AO_HIP(hipMemcpy(d_pack, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
+    AO_TRY(upload_words(tmp, {{h_env_idx, (size_t)n_idx}, {h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_pack));
     const int* d_idx = reinterpret_cast<const int*>(d_pack);
-    return AO_DISPATCH(env, reset_listed_envs, env, d_idx, n_idx, d_pack + n_idx, d_pack + n_idx + ns, r0, L0, pixel_size, tmp, st);
+    return AO_DISPATCH(env, reset_on_device, env, d_idx, n_idx, d_pack + n_idx, d_pack + n_idx + ns, r0, L0, pixel_size, tmp, st);
 }
 
 int aoenv_set_atm_opd(AoEnv* env, const double* h_opd, void* stream) {
@@ -2061,20 +2069,18 @@ int aoenv_test_normal(int device, uint32_t seed, int n, int n_calls, double* h_o
     DeviceGuard ao_device_guard(device);
     if (!ao_device_guard.ok) return fail("hipSetDevice(%d) failed", device);
     uint32_t* st = nullptr; int* pos = nullptr; double* zx = nullptr;
-    std::vector<uint32_t> key(kMtN);
-    mt_seed(seed, key.data());
-    int p0 = kMtN;
+    uint32_t* d_seed = nullptr;
     AO_HIP(hipMalloc((void**)&st, kMtN * 4));
     AO_HIP(hipMalloc((void**)&pos, 4));
     AO_HIP(hipMalloc((void**)&zx, (size_t)n * 8));
-    AO_HIP(hipMemcpy(st, key.data(), kMtN * 4, hipMemcpyHostToDevice));
-    AO_HIP(hipMemcpy(pos, &p0, 4, hipMemcpyHostToDevice));
-    int rc = 0;
+    AO_HIP(hipMalloc((void**)&d_seed, 4));
+    AO_HIP(hipMemcpy(d_seed, &seed, 4, hipMemcpyHostToDevice));
+    int rc = launch_mt_seed(d_seed, 1, nullptr, st, pos, 1, nullptr);                  // RandomState(seed)
     for (int c = 0; c < n_calls && !rc; ++c) {
         rc = launch_mt_normal<double>(st, pos, zx, 1, n, 0, n, nullptr);
         if (!rc && hipMemcpy(h_out + (size_t)c * n, zx, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail("copy back failed");
     }
-    (void)hipFree(st); (void)hipFree(pos); (void)hipFree(zx);
+    (void)hipFree(st); (void)hipFree(pos); (void)hipFree(zx); (void)hipFree(d_seed);
     return rc;
 }
 

@@ -67,6 +67,22 @@ def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
     return (ids, given) if return_order else ids
 
 
+def _wall_clock_seed() -> int:
+    """The seed of ``generateNewPhaseScreen(seed=None)``: the second of the day (OOPAO/Atmosphere.py:561-563)."""
+    import time
+    t = time.localtime()
+    return t.tm_hour * 3600 + t.tm_min * 60 + t.tm_sec
+
+
+def _layer_seeds(env_seeds, n_layer: int):
+    """``(screen_seeds, ring_seeds)``, both ``[k, n_layer]`` uint32, of ``k`` env seeds: layer l draws its screen from
+    ``RandomState(seed + l)`` and its rings from ``RandomState(seed + 1000 l)`` (OOPAO/Atmosphere.py:574-579)."""
+    def per_layer(step):
+        rows = [[(int(s) + step * l) & 0xFFFFFFFF for l in range(n_layer)] for s in env_seeds]
+        return np.array(rows, dtype=np.uint32).reshape(len(rows), n_layer)
+    return per_layer(1), per_layer(1000)
+
+
 class Shard:
     """One AoEnv handle of libaoenv (a shard of independent loops on one GPU)."""
 
@@ -768,17 +784,12 @@ class BatchedAOEnv:
         The screens are drawn on the device (same MT19937 stream and spectrum as the reference, float64 FFT).
         ``screens`` [n_envs, nLayer, N, N] (rad @ 500 nm, N = resolution + 4): caller-made layer screens uploaded instead
         (``aoenv_new_screens``); the rings and their RandomStates are still seeded from ``seed``."""
-        import time as _t
         if seed is None:
-            t = _t.localtime()
-            seed = t.tm_hour * 3600 + t.tm_min * 60 + t.tm_sec
+            seed = _wall_clock_seed()
         p, at = self.param, self._atm_tables
-        seeds = self.env_seeds(seed)
-        delta = at.layer_D / at.N
-        ring = np.array([[(int(s) + 1000 * l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32)
+        scr, ring = _layer_seeds(self.env_seeds(seed), p.nLayer)
         if screens is None:
-            scr = np.array([[(int(s) + l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32)
-            self._shard.new_screens_device(scr, ring, p.r0, p.L0, delta, self._stream())
+            self._shard.new_screens_device(scr, ring, p.r0, p.L0, at.layer_D / at.N, self._stream())
         elif at.uniform:
             screens = np.asarray(screens, dtype=np.float64)
             if screens.shape != (self.n_envs, p.nLayer, at.N, at.N):
@@ -815,15 +826,13 @@ class BatchedAOEnv:
         measurement behind the returned observation is ONE ``measure()`` of the whole shard: it consumes one camera frame number
         for every env.  With a noisy camera the untouched envs therefore continue like a twin that called ``measure()`` at this
         point, not like one that did not; with the ideal camera there is no difference."""
-        import time as _t
         torch = _torch()
         ids, given = normalize_env_ids(env_ids, self.n_envs, return_order=True)
         k, A_ = int(ids.size), self.nActuator
         if k == 0:
             return torch.empty((0, A_, A_), device=self.device, dtype=self.tdtype)
         if seed is None:
-            t = _t.localtime()
-            seed = t.tm_hour * 3600 + t.tm_min * 60 + t.tm_sec
+            seed = _wall_clock_seed()
         if np.ndim(seed) == 0:
             seeds = np.asarray(self.env_seeds(int(seed)))[given]
         else:
@@ -831,8 +840,7 @@ class BatchedAOEnv:
             if seeds.shape != (k,) or not np.issubdtype(seeds.dtype, np.integer):
                 raise ValueError(f"seed must be an int or {k} integers, one per listed env")
         p, at = self.param, self._atm_tables
-        scr = np.array([[(int(s) + l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32).reshape(k, p.nLayer)
-        ring = np.array([[(int(s) + 1000 * l) & 0xFFFFFFFF for l in range(p.nLayer)] for s in seeds], dtype=np.uint32).reshape(k, p.nLayer)
+        scr, ring = _layer_seeds(seeds, p.nLayer)
         self._shard.reset_envs(given, scr, ring, p.r0, p.L0, at.layer_D / at.N, self._stream())
         self._per_env_clock = True
         self.measure()

@@ -150,16 +150,19 @@ def test_partial_reset_under_the_pyramid():
     _check_partial(lambda: _make(4, "f32", geo, wfs="pyramid"), [0, 3], 5, 12)
 
 
-def test_resetting_every_env_equals_the_full_reset():
+@pytest.mark.parametrize("dtype,geo", [("f32", SMALL), ("f64", SMALL3)], ids=["f32-1layer", "f64-3layers"])
+def test_resetting_every_env_equals_the_full_reset(dtype, geo):
+    """The identity list against the null list: both resets run the same launches, so every env, step and final state is equal.
+    float32 / one layer runs the fused step kernel, float64 / three layers the batched kernels."""
     import torch
     n = 5
-    a, log_a = _make(n), []
+    a, log_a = _make(n, dtype, geo), []
     obs = _steps(a, _prologue(a, 5), 0, 3, log_a)
     rows = a.reset_envs(range(n), seed=31)
     _steps(a, rows, 3, 9, log_a)
     scr_a, buff_a = _final_state(a)
     a.close()
-    f, log_f = _make(n), []
+    f, log_f = _make(n, dtype, geo), []
     obs_f = _prologue(f, 31)
     _steps(f, obs_f, 3, 9, log_f)
     scr_f, buff_f = _final_state(f)
