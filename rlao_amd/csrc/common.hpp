@@ -276,6 +276,10 @@ struct StepArgs {
     ShConst<float> sc;
     FinishArgs<float> fa;        // n_tiles must be 1: the kernel leaves its telemetry sums in part[e][0][:]
     float* frame;                // [E][R*R]
+    // The residual phase (k.pb.phase) and the frame are outputs nobody inside the kernel reads back: the WFS takes the phase from
+    // LDS, the centroid the frame from registers.  A step whose buffers are overwritten before anyone can read them (every step of
+    // aoenv_run_integrator but the last) leaves both stores out.  Workgroup-uniform kernel arguments: scalar branches.
+    int store_phase, store_frame;
     float* signal;               // [E][2 nValid]
     float* wfs_max;              // [E]
     const float* fac_m;          // [K][nSig]

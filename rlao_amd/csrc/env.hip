@@ -747,10 +747,11 @@ void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_
 }
 
 template <typename T>
-int run_fused_step(AoEnv*, int, const void*, void*, void*, void*, double, hipStream_t) { return fail("fused step: float32 only"); }
+int run_fused_step(AoEnv*, int, const void*, void*, void*, void*, double, bool, hipStream_t) { return fail("fused step: float32 only"); }
+// observable: the phase and frame buffers may be read after this step (false: the next step overwrites them first, see StepArgs)
 template <>
 int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_reward, void* d_strehl, double gain,
-                          hipStream_t st) {
+                          bool observable, hipStream_t st) {
     if (env->amp_pupil_dirty) {
         const size_t R2 = (size_t)env->R * env->R;
         if (env->h_pupil.size() != R2 || env->h_amp.size() != R2) return fail("pupil / WFS amplitude have not been uploaded");
@@ -770,6 +771,8 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
                               static_cast<float*>(d_reward), static_cast<float*>(d_strehl), i, 1, gain, 1);
     a.fa.n_tiles = 1;
     a.frame = env->as<float>(env->frame);
+    // (atm.OPD written every step is the state-inspection mode: every step is then observable, there is no fast path to keep)
+    a.store_phase = a.store_frame = (observable || env->store_opd_atm) ? 1 : 0;
     a.signal = env->as<float>(env->signal);
     a.wfs_max = env->as<float>(env->wfs_max);
     a.fac_m = env->as<float>(env->fac_m);
@@ -802,12 +805,12 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
 
 template <typename T>
 int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
-           double gain, hipStream_t st) {
+           double gain, bool observable, hipStream_t st) {
     const bool fused_step = fused_step_ok<T>(env);
     AO_TRY(advance_atmosphere<T>(env, fused_step, st));
     env->atm_user_defined = false;
     if (fused_step) {
-        AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, st));
+        AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, observable, st));
         if (d_frame)
             AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                                   hipMemcpyDeviceToDevice, st));
@@ -1758,7 +1761,7 @@ int aoenv_step(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_fra
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return AO_DISPATCH(env, step_t, env, i, d_action, d_obs, d_frame, d_reward, d_strehl, 0.0, st);
+    return AO_DISPATCH(env, step_t, env, i, d_action, d_obs, d_frame, d_reward, d_strehl, 0.0, true, st);
 }
 
 int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_obs, void* d_frame, void* d_reward,
@@ -1770,9 +1773,11 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // only the last step's residual phase and camera frame can be read afterwards (aoenv_buffer, aoenv_download, aoenv_compute_psf,
+    // d_frame, checkpoints: all of them between calls): the fused step leaves the stores of the other steps out
     for (int k = 0; k < n_steps; ++k)
         AO_TRY(AO_DISPATCH(env, step_t, env, i0 + k, d_obs /*unused*/, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward,
-                           d_strehl, gain, st));
+                           d_strehl, gain, k == n_steps - 1, st));
     return 0;
 }
 

@@ -392,7 +392,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                     }
                 }
                 if (k.pa.store_atm) *reinterpret_cast<f32x4s*>(k.pb.opd_atm + pix0 + q) = atm;
-                *reinterpret_cast<f32x4s*>(k.pb.phase + pix0 + q) = phi;
+                if (a.store_phase) *reinterpret_cast<f32x4s*>(k.pb.phase + pix0 + q) = phi;   // only where it can be read (StepArgs)
                 // lenslet (i, j) element E[a][b] = phase[i p + b][j p + a]: the reference tiles phase.T
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -469,17 +469,24 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         camera_sh6_lane(pxv, ok, (uint32_t)((li * 6) * R + lj * 6 + q3), R, (uint32_t)e, a.det, tab_s, a.pa.lmax);
         camera_unpack(pxv, Ia, Ib);
     }
+    // the frame goes to memory only on a step after which it can be read (StepArgs): the centroid below has it in registers
     if (ok) {
-        float* fr = a.frame + pix0 + (size_t)(li * 6) * R + lj * 6 + q3;
+        if (a.store_frame) {
+            float* fr = a.frame + pix0 + (size_t)(li * 6) * R + lj * 6 + q3;
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+                fr[(size_t)u * R] = Ia[u];
+                fr[(size_t)u * R + 3] = Ib[u];
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            fr[(size_t)u * R] = Ia[u];
-            fr[(size_t)u * R + 3] = Ib[u];
             mx = Ia[u] > mx ? Ia[u] : mx;
             mx = Ib[u] > mx ? Ib[u] : mx;
         }
     }
-    if (a.det.active && (a.det.dark_e > 0.f || a.det.readout_noise != 0.f)) {
+    // (counter-based streams: nothing but the frame depends on these pixels, so an unread frame skips them altogether)
+    if (a.store_frame && a.det.active && (a.det.dark_e > 0.f || a.det.readout_noise != 0.f)) {
         // the camera also reads out the pixels of the lenslets that are not valid (no light): dark + read-out noise, ADC
         const float rtab = recip_table_lane();
         for (int idx = tid; idx < n_sub * n_sub * 9; idx += 1024) {
