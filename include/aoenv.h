@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define AOENV_ABI_VERSION 6
+#define AOENV_ABI_VERSION 7
 
 enum { AOENV_F32 = 0, AOENV_F64 = 1 };
 enum { AOENV_WFS_SH = 0, AOENV_WFS_PYRAMID = 1 };
@@ -162,6 +162,26 @@ int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* 
 int aoenv_get_clock_env(AoEnv* env, double* h_clock);
 int aoenv_set_clock_env(AoEnv* env, const double* h_clock);
 
+/* Replaces: the r0 setter (OOPAO/Atmosphere.py:792-807) when every env has its OWN Fried parameter (a trainer that sweeps the
+ * seeing, one value per run, batched).  h_r0 is [n_env] float64, metres at 500 nm; r0_tables is the r0 the uploaded AOENV_C_AB
+ * was built at.  No tables per env and no second product: with s = (r0_def / r0)^(5/3), A = (zx s)^T (zz^-1 / s) does not depend
+ * on r0 and B = chol(xx s - A zx s) goes as r0^(-5/6), so X = A Z + B(r0_e) xi = A Z + B(r0_tables) (sigma_e xi) with
+ * sigma_e = (r0_tables / r0_e)^(5/6).  The library keeps h_r0 on the host (aoenv_get_r0_env, the resets) and sigma_e, computed on
+ * the host as pow(r0_tables / h_r0[e], 5.0 / 6), as float64 [n_env] on the device; every kernel that writes innovations into
+ * [Z | xi] multiplies them by sigma_e in float64 before converting to the env dtype.  The MT19937 streams are untouched
+ * (AOENV_B_MT_STATE is what it is without the feature), and sigma_e == 1 exactly for h_r0[e] == r0_tables.  It takes effect from
+ * each env's next ring extrusion: screens on the device are not rescaled (the reference's setter does not either), a deferred ring
+ * already computed is scattered as it is, a ring look-ahead drawn with the old factors is forgotten.  Works with shared and per-env
+ * clocks, both sensors, and layers on grids of their own (sigma_e is the same for every layer).  While it is active,
+ * aoenv_new_screens_device and aoenv_reset_envs give env e the screens of their `r0` argument multiplied by (r0 / r0_e)^(5/6)
+ * (computed on the host in float64, applied once to the finished float64 screen); aoenv_new_screens takes the host's screens as
+ * they are.  Re-uploading AOENV_C_AB at another r0 needs a new call with that r0_tables.
+ * h_r0 == NULL: back to one r0 for all envs (the factors are absent, not ones).  The stream is waited for once.
+ * Refused, with nothing changed: a null env, an entry that is not finite and positive, such an r0_tables.
+ * aoenv_get_r0_env fills h_r0 [n_env]; it fails while the shard has one r0. */
+int aoenv_set_r0_env(AoEnv* env, const double* h_r0, double r0_tables, void* stream);
+int aoenv_get_r0_env(AoEnv* env, double* h_r0);
+
 /* Replaces: atm.generateNewPhaseScreen(seed) (OOPAO/Atmosphere.py:560-592) for every env of the shard.
  *   h_screens [n_env][n_layer][N*N] float64: the new layer.phase screens (rad @ 500 nm), or NULL to keep
  *             the current interior (not with per-env clocks).  Layers on grids of their own (layer_res_l): layer-major
@@ -197,6 +217,9 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
  * cost of per-env clocks on every step (the ring kernels run on every step: about 26 % at the 8 m Shack-Hartmann geometry,
  * DESIGN.md section 4.2).  The screen generation and the ring operands are work for n_idx envs, driven by a device index list;
  * the ring product itself runs once per layer over the whole shard, so that it sums in the order of the full reset.
+ * With a per-env Fried parameter (aoenv_set_r0_env) a listed env restarts with ITS r0: its screens are those of `r0` times
+ * (r0 / r0_e)^(5/6) -- row c of the factors belongs to env h_env_idx[c] -- and its first ring is drawn with sigma_e; to restart an
+ * env at a new seeing, call aoenv_set_r0_env first.
  * n_idx == 0 succeeds and does nothing (the clocks stay as they are).  Refused, with nothing changed: null pointers, n_idx < 0,
  * an index outside [0, n_env), a duplicate index, n_layer == 0, missing ring tables, non-positive r0 / L0 / pixel_size, a shared
  * wind of a pixel per frame or more, and shards with layers on grids of their own (AoCfg.layer_res_l), which have no per-env

@@ -7,31 +7,33 @@ namespace ao {
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_mt_normal(uint32_t* __restrict__ mt_state, int* __restrict__ mt_pos,
-                                                   T* __restrict__ zx, int K, int n_inner, int n_outer) {
-    mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, blockIdx.x);
+                                                   T* __restrict__ zx, int K, int n_inner, int n_outer,
+                                                   const double* __restrict__ xi_scale) {
+    mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, blockIdx.x, xi_scale);
 }
 
 // One launch for the two independent halves of the ring operand [Z | xi] of an env: blockIdx.x == 0 gathers Z, blockIdx.x == 1 draws
 // the n_outer innovations xi of the layer's MT19937 stream.  The env is blockIdx.y, or env_idx[blockIdx.y] of a device index list
-// (the partial reset, aoenv_reset_envs); null list: row c is env c, as everywhere a list is taken.
+// (the partial reset, aoenv_reset_envs); null list: row c is env c, as everywhere a list is taken.  xi_scale is indexed by the env
+// itself, list or not.
 template <typename T>
 __global__ void __launch_bounds__(256) k_ring_prepare(const T* __restrict__ map, T* __restrict__ zx,
                                                       const int* __restrict__ inner_idx, const uint32_t* mt_state,
                                                       const int* mt_pos, uint32_t* mt_state_out, int* mt_pos_out, int S,
                                                       int n_inner, int n_outer, int K, int sx, int sy, int oy, int ox,
-                                                      const int* __restrict__ env_idx) {
+                                                      const int* __restrict__ env_idx, const double* __restrict__ xi_scale) {
     const int e = env_idx ? env_idx[blockIdx.y] : blockIdx.y;
     if (blockIdx.x == 0) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, sx, sy, oy, ox, e, threadIdx.x, 256);
-    else mt_normal_body<T>(mt_state, mt_pos, mt_state_out, mt_pos_out, zx, K, n_inner, n_outer, e);
+    else mt_normal_body<T>(mt_state, mt_pos, mt_state_out, mt_pos_out, zx, K, n_inner, n_outer, e, xi_scale);
 }
 
 template <typename T>
 int launch_ring_prepare(const T* map, T* zx, const int* inner_idx, const uint32_t* mt_state, const int* mt_pos,
                         uint32_t* mt_state_out, int* mt_pos_out, const int* env_idx, int n, int S, int n_inner, int n_outer, int K,
-                        int sx, int sy, int oy, int ox, hipStream_t st) {
+                        int sx, int sy, int oy, int ox, const double* xi_scale, hipStream_t st) {
     if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
     hipLaunchKernelGGL(k_ring_prepare<T>, dim3(2, n), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, mt_state_out,
-                       mt_pos_out, S, n_inner, n_outer, K, sx, sy, oy, ox, env_idx);
+                       mt_pos_out, S, n_inner, n_outer, K, sx, sy, oy, ox, env_idx, xi_scale);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -45,7 +47,7 @@ __global__ void __launch_bounds__(256) k_ring_prepare_env(const T* __restrict__ 
                                                           const int* __restrict__ inner_idx, uint32_t* mt_state, int* mt_pos,
                                                           const EnvClock* __restrict__ clk_in, EnvClock* __restrict__ clk_out,
                                                           LayerTaps* __restrict__ taps, double weight, int S, int n_inner,
-                                                          int n_outer, int K) {
+                                                          int n_outer, int K, const double* __restrict__ xi_scale) {
     const int e = blockIdx.y;
     EnvClock c = clk_in[e];
     const int oy = c.org[0], ox = c.org[1];
@@ -67,26 +69,26 @@ __global__ void __launch_bounds__(256) k_ring_prepare_env(const T* __restrict__ 
             taps[e] = t;
         }
     } else if (cross) {
-        mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, e);
+        mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, e, xi_scale);
     }
 }
 
 template <typename T>
 int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk_in,
                             EnvClock* clk_out, LayerTaps* taps, double weight, int n_env, int S, int n_inner, int n_outer, int K,
-                            hipStream_t st) {
+                            const double* xi_scale, hipStream_t st) {
     if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
     hipLaunchKernelGGL(k_ring_prepare_env<T>, dim3(2, n_env), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, clk_in, clk_out,
-                       taps, weight, S, n_inner, n_outer, K);
+                       taps, weight, S, n_inner, n_outer, K, xi_scale);
     AO_HIP(hipGetLastError());
     return 0;
 }
 
 template <typename T>
 int launch_mt_normal(uint32_t* mt_state, int* mt_pos, T* zx, int n_env, int K, int n_inner, int n_outer,
-                     hipStream_t st) {
+                     const double* xi_scale, hipStream_t st) {
     if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
-    hipLaunchKernelGGL(k_mt_normal<T>, dim3(n_env), dim3(256), 0, st, mt_state, mt_pos, zx, K, n_inner, n_outer);
+    hipLaunchKernelGGL(k_mt_normal<T>, dim3(n_env), dim3(256), 0, st, mt_state, mt_pos, zx, K, n_inner, n_outer, xi_scale);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -245,12 +247,12 @@ int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, i
 
 #define INST(T)                                                                                                    \
     template int launch_ring_prepare<T>(const T*, T*, const int*, const uint32_t*, const int*, uint32_t*, int*, const int*, int, int, \
-                                        int, int, int, int, int, int, int, hipStream_t);                           \
-    template int launch_mt_normal<T>(uint32_t*, int*, T*, int, int, int, int, hipStream_t);                        \
+                                        int, int, int, int, int, int, int, const double*, hipStream_t);            \
+    template int launch_mt_normal<T>(uint32_t*, int*, T*, int, int, int, int, const double*, hipStream_t);         \
     template int launch_scatter_minmax<T>(T*, const T*, const int*, T*, const int*, int, int, int, int, int, int, int, int, \
                                           hipStream_t, const LayerTaps*);                                          \
     template int launch_ring_prepare_env<T>(const T*, T*, const int*, uint32_t*, int*, const EnvClock*, EnvClock*, LayerTaps*, \
-                                            double, int, int, int, int, int, hipStream_t);                                                          \
+                                            double, int, int, int, int, int, const double*, hipStream_t);                                                       \
     template int launch_minmax<T>(const T*, T*, int, int, hipStream_t);                                            \
     template int launch_reset_env_rows<T>(const int*, int, T*, T*, int, EnvClock*, LayerTaps*, int, int, hipStream_t);
 INST(float)

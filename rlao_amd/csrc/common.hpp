@@ -121,17 +121,18 @@ struct Env;  // host object, env.hpp
 template <typename T>
 int launch_ring_prepare(const T* map, T* zx, const int* inner_idx, const uint32_t* mt_state, const int* mt_pos,
                         uint32_t* mt_state_out, int* mt_pos_out, const int* env_idx, int n, int S, int n_inner, int n_outer, int K,
-                        int sx, int sy, int oy, int ox, hipStream_t st);
+                        int sx, int sy, int oy, int ox, const double* xi_scale, hipStream_t st);
 template <typename T>
 int launch_mt_normal(uint32_t* mt_state, int* mt_pos, T* zx, int n_env, int K, int n_inner, int n_outer,
-                     hipStream_t st);
+                     const double* xi_scale, hipStream_t st);
 template <typename T>
 int launch_scatter_minmax(T* new_map, const T* X, const int* outer_idx, T* minmax, const int* env_idx, int n, int n_env, int S,
                           int n_outer, int splits, int oy, int ox, int with_minmax, hipStream_t st, const LayerTaps* env_taps = nullptr);
 template <typename T>
 int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk_in,
                             EnvClock* clk_out, LayerTaps* taps, double weight, int n_env, int S, int n_inner, int n_outer, int K,
-                            hipStream_t st);
+                            const double* xi_scale, hipStream_t st);
+// xi_scale of the launches above: [n_env] float64 factors of the innovations (per-env Fried parameter, mt_normal_body), or null
 template <typename T>
 int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st);
 // device index lists (env_idx, n entries): workgroup / row c of a launch serves env env_idx[c]; a null list means env c -- the full
@@ -149,6 +150,7 @@ struct MtAhead {
     int* pos_out;
     float* zx_out;           // [n_env][K]: the draw goes to columns n_inner ..
     int K, n_inner, n_outer, n_env;
+    const double* xi_scale;  // [n_env] per-env Fried parameter (mt_normal_body), or null
 };
 int launch_ring_gemm_draw_ahead(const float* X, const float* W, float* Cpart, int M, int N, int K, int splits, const MtAhead& m,
                                 hipStream_t st);
@@ -371,6 +373,7 @@ struct ScreenArgs {
     FftPlan plan;
     int N, n_env, seq_per_block;
     double delta;            // layer pixel size [m]
+    const double* scale;     // [E] per-env Fried parameter: factor of generated env c's finished screen, (r0 / r0_e)^(5/6); or null
 };
 // writes layer.phase (rad @ 500 nm) of n_env envs into the interior of their (N+2)^2 mapShift: generated env c goes to map c of
 // `map`, or -- env_idx (a device list of n_env entries) given -- to map env_idx[c] (aoenv_reset_envs)

@@ -81,6 +81,12 @@ struct AoEnv {
     EnvClock* env_clk[2] = {nullptr, nullptr};   // [L][E] each: current / next (k_ring_prepare_env reads one, writes the other)
     int clk_cur = 0;
     LayerTaps* env_taps = nullptr;           // [L][E] taps of the current step
+    // per-env Fried parameter (aoenv_set_r0_env): the ring tables stay those of r0_tables; env e's innovations are multiplied by
+    // sigma_e = (r0_tables / r0_e)^(5/6) where they are written into [Z | xi] (mt_normal_body), its new screens by (r0 / r0_e)^(5/6)
+    bool per_env_r0 = false;
+    std::vector<double> h_r0;                // [E] metres at 500 nm (the resets and checkpoints read it)
+    double* xi_scale = nullptr;              // [E] float64 sigma_e on the device
+    const double* sigma() const { return per_env_r0 ? xi_scale : nullptr; }   // what every launch that draws innovations is handed
     bool use_coefs_img = false;              // aoenv_set_option(AOENV_OPT_COEFS_IMAGE); always on above 1024 actuators
     bool defer_ring = true;                  // aoenv_set_option(AOENV_OPT_DEFER_RING)
     bool have[AOENV_C_COUNT] = {false};
@@ -351,7 +357,7 @@ int extrude(AoEnv* env, int l, int sx, int sy, bool lean, hipStream_t st, bool d
     {
         AO_PROF(env, SHIFT_GATHER, st);                           // Z gather + xi draw, one launch
         AO_TRY(launch_ring_prepare<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, nullptr,
-                                      env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
+                                      env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], env->sigma(), st));
     }
     int splits = 1;
     AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
@@ -375,7 +381,7 @@ int first_ring(AoEnv* env, int l, const int* d_idx, int n, hipStream_t st) {
     {
         AO_PROF(env, SHIFT_GATHER, st);
         AO_TRY(launch_ring_prepare<T>(map, zx, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur, d_idx, n, y.S, y.nin, y.nout, y.K, 0, 0,
-                                      0, 0, st));
+                                      0, 0, env->sigma(), st));
     }
     int splits = 1;
     AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
@@ -434,11 +440,12 @@ int extrude_pipelined(AoEnv* env, int l, int sx, int sy, hipStream_t st) {
     } else {
         AO_PROF(env, SHIFT_GATHER, st);
         AO_TRY(launch_ring_prepare<float>(env->as<float>(env->screen_ptr(l)), op, y.inner_idx, y.mt_cur, y.pos_cur, y.mt_cur, y.pos_cur,
-                                          nullptr, env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], st));
+                                          nullptr, env->E, y.S, y.nin, y.nout, y.K, sx, sy, y.org[0], y.org[1], env->sigma(), st));
     }
     forget_lookahead(y);
     const int splits = gemm_splits(env->E, y.nout, y.K);
-    MtAhead m{y.mt_cur, y.pos_cur, y.mt_alt, y.pos_alt, static_cast<float*>(env->zx_pipe_ptr(1 - cur, l)), y.K, y.nin, y.nout, env->E};
+    MtAhead m{y.mt_cur, y.pos_cur, y.mt_alt, y.pos_alt, static_cast<float*>(env->zx_pipe_ptr(1 - cur, l)), y.K, y.nin, y.nout, env->E,
+              env->sigma()};
     {
         AO_PROF(env, GEMM_RING, st);
         AO_TRY(launch_ring_gemm_draw_ahead(op, env->as<float>(y.ab), static_cast<float*>(env->xbuf_ptr(l)), env->E, y.nout, y.K, splits, m,
@@ -469,7 +476,7 @@ int advance_atmosphere_env(AoEnv* env, bool lean, hipStream_t st) {
             AO_PROF(env, SHIFT_GATHER, st);
             AO_TRY(launch_ring_prepare_env<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur,
                                               env->env_clk[env->clk_cur] + row, env->env_clk[1 - env->clk_cur] + row, env->env_taps + row,
-                                              y.weight, env->E, y.S, y.nin, y.nout, y.K, st));
+                                              y.weight, env->E, y.S, y.nin, y.nout, y.K, env->sigma(), st));
         }
         int splits = 1;
         AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
@@ -1444,6 +1451,47 @@ int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff) {
     return 0;
 }
 
+// ---- per-env Fried parameter -------------------------------------------------------------------------------------------
+int aoenv_set_r0_env(AoEnv* env, const double* h_r0, double r0_tables, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_r0) {                                                   // back to one r0 for the shard
+        if (!env->per_env_r0) return 0;
+        for (int l = 0; l < env->L; ++l) forget_lookahead(env->layer[l]);   // drawn with the sigma that is going away
+        env->per_env_r0 = false;
+        env->h_r0.clear();
+        return 0;
+    }
+    if (!(r0_tables > 0) || !std::isfinite(r0_tables)) return fail("aoenv_set_r0_env: r0_tables = %g, must be positive and finite", r0_tables);
+    const size_t E = (size_t)env->E;
+    for (size_t e = 0; e < E; ++e)
+        if (!(h_r0[e] > 0) || !std::isfinite(h_r0[e])) return fail("aoenv_set_r0_env: r0[%zu] = %g, must be positive and finite", e, h_r0[e]);
+    std::vector<double> sg(E);
+    for (size_t e = 0; e < E; ++e) sg[e] = std::pow(r0_tables / h_r0[e], 5.0 / 6);
+    if (!env->xi_scale) {
+        void* p_ = nullptr;
+        AO_HIP(hipMalloc(&p_, E * sizeof(double)));
+        env->allocs.push_back(p_);
+        env->xi_scale = static_cast<double*>(p_);
+    }
+    // ordered on the stream behind the launches that read the old factors (a deferred ring was computed from them and is scattered
+    // as it is)
+    AO_HIP(hipMemcpyAsync(env->xi_scale, sg.data(), E * sizeof(double), hipMemcpyHostToDevice, st));
+    AO_HIP(hipStreamSynchronize(st));
+    for (int l = 0; l < env->L; ++l) forget_lookahead(env->layer[l]);       // an operand drawn ahead carries the old sigma
+    env->h_r0.assign(h_r0, h_r0 + E);
+    env->per_env_r0 = true;
+    return 0;
+}
+
+int aoenv_get_r0_env(AoEnv* env, double* h_r0) {
+    AO_CHECK_ENV(env);
+    if (!h_r0) return fail("null argument");
+    if (!env->per_env_r0) return fail("the shard has one r0 for all envs (aoenv_set_r0_env has not been called, or was cleared)");
+    std::copy(env->h_r0.begin(), env->h_r0.end(), h_r0);
+    return 0;
+}
+
 static int require_step_constants(AoEnv* env, bool atmosphere) {
     static const int base[] = {AOENV_C_PUPIL, AOENV_C_ACT_IDX, AOENV_C_WFS_AMP, AOENV_C_SH_SUBAP_IDX};
     for (int k : base)
@@ -1478,6 +1526,16 @@ int upload_words(TmpFree& tmp, std::initializer_list<std::pair<const void*, size
     AO_TRY(tmp.get((void**)d_out, pack.size() * 4));
     AO_HIP(hipMemcpy(*d_out, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
     return 0;
+}
+
+// Per-env Fried parameter: the factor of the new screens of the n envs of a reset generated at `r0`, (r0 / r0_e)^(5/6) in float64
+// (the generator's amplitudes go as r0^(-5/6), vk_psd); row c belongs to env idx[c], or env c without a list.  Empty while the
+// shard has one r0.
+void screen_factors(const AoEnv* env, const int32_t* idx, int n, double r0, std::vector<double>& f) {
+    f.clear();
+    if (!env->per_env_r0) return;
+    f.resize((size_t)n);
+    for (int c = 0; c < n; ++c) f[c] = std::pow(r0 / env->h_r0[idx ? idx[c] : c], 5.0 / 6);
 }
 }  // namespace
 
@@ -1606,9 +1664,10 @@ extern "C++" {
 // layer: RandomState(seed + layer) seeded on the device from d_screen_seeds [n][L], normal(size=(N, N)) drawn twice (real, imaginary
 // parts), the screen written into the env's map.  The generator works on a compact scratch of at most g.ec envs, reused chunk after
 // chunk in stream order (no host wait in between); its tables are rebuilt whenever a layer is on a grid of another size.
+// d_scale [n] (per-env Fried parameter, else null): the finished float64 screen of row c is multiplied by d_scale[c].
 template <typename T>
-static int draw_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, double r0, double L0, double pixel_size,
-                        TmpFree& tmp, hipStream_t st) {
+static int draw_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const double* d_scale, double r0, double L0,
+                        double pixel_size, TmpFree& tmp, hipStream_t st) {
     const int L = env->L;
     ScreenGen g;
     for (int l = 0; l < L; ++l) {
@@ -1618,8 +1677,9 @@ static int draw_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_s
         for (int c0 = 0; c0 < n; c0 += g.ec) {
             const int nc = std::min(g.ec, n - c0);
             AO_TRY(launch_mt_seed(d_screen_seeds + (size_t)c0 * L + l, L, nullptr, g.mt, g.pos, nc, st));
-            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), nc, n2, 0, n2, st));
+            AO_TRY(launch_mt_normal<double>(g.mt, g.pos, const_cast<double*>(g.sa.nrm), nc, n2, 0, n2, nullptr, st));
             g.sa.n_env = nc;
+            g.sa.scale = d_scale ? d_scale + c0 : nullptr;
             T* map = env->as<T>(env->screen_ptr(l));
             if (d_idx) AO_TRY(launch_screen<T>(g.sa, map, S, st, d_idx + c0));
             else AO_TRY(launch_screen<T>(g.sa, map + (size_t)c0 * S * S, S, st));
@@ -1632,14 +1692,14 @@ static int draw_screens(AoEnv* env, const int* d_idx, int n, const uint32_t* d_s
 // partial one (aoenv_reset_envs, behind its validation and the switch to per-env clocks) are this sequence; the listed envs' state
 // rows are cleared first, which the full reset leaves alone.
 template <typename T>
-static int reset_on_device(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const uint32_t* d_ring_seeds, double r0,
-                           double L0, double pixel_size, TmpFree& tmp, hipStream_t st) {
+static int reset_on_device(AoEnv* env, const int* d_idx, int n, const uint32_t* d_screen_seeds, const uint32_t* d_ring_seeds,
+                           const double* d_scale, double r0, double L0, double pixel_size, TmpFree& tmp, hipStream_t st) {
     if (d_idx) {
         AO_TRY(launch_reset_env_rows<T>(d_idx, n, env->as<T>(env->coefs), env->as<T>(env->dm_prev), env->A, env->env_clk[env->clk_cur],
                                         env->env_taps, env->L, env->E, st));
         AO_TRY(refresh_dense_dm<T>(env, st));
     }
-    AO_TRY(draw_screens<T>(env, d_idx, n, d_screen_seeds, r0, L0, pixel_size, tmp, st));
+    AO_TRY(draw_screens<T>(env, d_idx, n, d_screen_seeds, d_scale, r0, L0, pixel_size, tmp, st));
     return finish_new_screens<T>(env, d_idx, n, d_ring_seeds, st);
 }
 }  // extern "C++"
@@ -1656,9 +1716,14 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
     AO_TRY(screens_replaced(env, true));
     TmpFree tmp;
     const size_t ns = (size_t)env->E * env->L;                     // [E][L] screen seeds, [E][L] ring seeds
-    uint32_t* d_seeds = nullptr;
-    AO_TRY(upload_words(tmp, {{h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_seeds));
-    return AO_DISPATCH(env, reset_on_device, env, nullptr, env->E, d_seeds, d_seeds + ns, r0, L0, pixel_size, tmp, st);
+    std::vector<double> fac;                                       // (first in the pack: 8-byte aligned)
+    screen_factors(env, nullptr, env->E, r0, fac);
+    const size_t nf = 2 * fac.size();
+    uint32_t* d_pack = nullptr;
+    AO_TRY(upload_words(tmp, {{fac.data(), nf}, {h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_pack));
+    const uint32_t* d_seeds = d_pack + nf;
+    const double* d_scale = nf ? reinterpret_cast<const double*>(d_pack) : nullptr;
+    return AO_DISPATCH(env, reset_on_device, env, nullptr, env->E, d_seeds, d_seeds + ns, d_scale, r0, L0, pixel_size, tmp, st);
 }
 
 int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint32_t* h_screen_seeds, const uint32_t* h_ring_seeds,
@@ -1699,13 +1764,19 @@ int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint
         AO_TRY(AO_DISPATCH(env, flush_rings, env, st));            // a deferred ring of the clocks as they were
         AO_HIP(hipStreamSynchronize(st));
     }
-    // the list and the seeds in one upload: [n_idx] indices, [n_idx][L] screen seeds, [n_idx][L] ring seeds
+    // the list and the seeds in one upload: (per-env r0: [n_idx] float64 screen factors, first: 8-byte aligned,) [n_idx] indices,
+    // [n_idx][L] screen seeds, [n_idx][L] ring seeds
     TmpFree tmp;
     const size_t ns = (size_t)n_idx * L;
+    std::vector<double> fac;
+    screen_factors(env, h_env_idx, n_idx, r0, fac);
+    const size_t nf = 2 * fac.size();
     uint32_t* d_pack = nullptr;
-    AO_TRY(upload_words(tmp, {{h_env_idx, (size_t)n_idx}, {h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_pack));
-    const int* d_idx = reinterpret_cast<const int*>(d_pack);
-    return AO_DISPATCH(env, reset_on_device, env, d_idx, n_idx, d_pack + n_idx, d_pack + n_idx + ns, r0, L0, pixel_size, tmp, st);
+    AO_TRY(upload_words(tmp, {{fac.data(), nf}, {h_env_idx, (size_t)n_idx}, {h_screen_seeds, ns}, {h_ring_seeds, ns}}, &d_pack));
+    const int* d_idx = reinterpret_cast<const int*>(d_pack + nf);
+    const uint32_t* d_seeds = d_pack + nf + n_idx;
+    const double* d_scale = nf ? reinterpret_cast<const double*>(d_pack) : nullptr;
+    return AO_DISPATCH(env, reset_on_device, env, d_idx, n_idx, d_seeds, d_seeds + ns, d_scale, r0, L0, pixel_size, tmp, st);
 }
 
 int aoenv_set_atm_opd(AoEnv* env, const double* h_opd, void* stream) {
@@ -2082,7 +2153,7 @@ int aoenv_test_normal(int device, uint32_t seed, int n, int n_calls, double* h_o
     AO_HIP(hipMemcpy(d_seed, &seed, 4, hipMemcpyHostToDevice));
     int rc = launch_mt_seed(d_seed, 1, nullptr, st, pos, 1, nullptr);                  // RandomState(seed)
     for (int c = 0; c < n_calls && !rc; ++c) {
-        rc = launch_mt_normal<double>(st, pos, zx, 1, n, 0, n, nullptr);
+        rc = launch_mt_normal<double>(st, pos, zx, 1, n, 0, n, nullptr, nullptr);
         if (!rc && hipMemcpy(h_out + (size_t)c * n, zx, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail("copy back failed");
     }
     (void)hipFree(st); (void)hipFree(pos); (void)hipFree(zx); (void)hipFree(d_seed);

@@ -183,7 +183,8 @@ __global__ void __launch_bounds__(256) k_ring_gemm_draw_ahead(const float* __res
         return;
     }
     const int e = ((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
-    if (e < m.n_env) mt_normal_body<float>(m.mt_in, m.pos_in, m.mt_out, m.pos_out, m.zx_out, m.K, m.n_inner, m.n_outer, e);
+    if (e < m.n_env) mt_normal_body<float>(m.mt_in, m.pos_in, m.mt_out, m.pos_out, m.zx_out, m.K, m.n_inner, m.n_outer, e,
+                                           m.xi_scale);
 }
 
 int launch_ring_gemm_draw_ahead(const float* X, const float* W, float* Cpart, int M, int N, int K, int splits, const MtAhead& m,

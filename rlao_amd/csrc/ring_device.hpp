@@ -81,9 +81,12 @@ __device__ inline void mt_twist(uint32_t* s) {
 
 // mt_state_out / mt_pos_out: where the advanced stream is stored (== the inputs: in place; another buffer: the draw is
 // speculative -- the ring look-ahead of env.hip -- and the caller commits it by swapping the buffers)
+// xi_scale: per-env Fried parameter (aoenv_set_r0_env): [n_env] float64 sigma_e = (r0_tables / r0_e)^(5/6); the deviates of env e
+// are multiplied by it in float64, before the conversion to T -- X = A Z + B(r0_e) xi = A Z + B(r0_tables) (sigma_e xi).  The
+// stream itself is the same either way.  Null: one r0 for the shard, the deviates are stored as drawn.
 template <typename T>
 __device__ inline void mt_normal_body(const uint32_t* mt_state, const int* mt_pos, uint32_t* mt_state_out, int* mt_pos_out,
-                                      T* __restrict__ zx, int K, int n_inner, int n_outer, int e) {
+                                      T* __restrict__ zx, int K, int n_inner, int n_outer, int e, const double* xi_scale) {
     __shared__ uint32_t s[kMtN];
     __shared__ int scan[256];
     __shared__ int sh_pos, sh_got, sh_stop;
@@ -121,6 +124,11 @@ __device__ inline void mt_normal_body(const uint32_t* mt_state, const int* mt_po
                 const double f = sqrt(-2.0 * log(r2) / r2);
                 n0 = f * x2;                                      // returned first
                 n1 = f * x1;                                      // cached, returned next
+                if (xi_scale) {
+                    const double sg = xi_scale[e];
+                    n0 *= sg;
+                    n1 *= sg;
+                }
             }
         }
         // inclusive scan of the accept flags over the workgroup: ballot + popcount inside a wave, 4 wave totals in LDS

@@ -108,6 +108,7 @@ __global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* _
     for (int w = 0; w < (int)blockDim.x / kWave; ++w) mean += red[w];
     mean /= (double)N * N;
     T* m = map + (size_t)(env_idx ? env_idx[e] : e) * S * S;
+    const double scale = a.scale ? a.scale[e] : 1.0;               // per-env Fried parameter, once on the finished float64 screen (x 1.0 is exact)
     for (int q = threadIdx.x; q < N * N; q += blockDim.x) {
         const int y = q / N, x = q - y * N;
         const double xc = (x - N / 2.0) * a.delta, yc = (y - N / 2.0) * a.delta;
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(1024) k_screen_finish(const ScreenArgs a, T* _
             sincos(two_pi * (a.sub[3 * t + 1] * xc + a.sub[3 * t + 2] * yc), &sn, &cs);
             lo += cr[t] * cs - ci[t] * sn;
         }
-        m[(size_t)(y + 1) * S + x + 1] = (T)((lo - mean) + hi[q]);
+        m[(size_t)(y + 1) * S + x + 1] = (T)(((lo - mean) + hi[q]) * scale);
     }
 }
 

@@ -67,6 +67,35 @@ def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
     return (ids, given) if return_order else ids
 
 
+def resolve_r0_per_env(r0, env_ids, n_envs: int, current) -> np.ndarray:
+    """The Fried parameter of every env after a per-env assignment, ``[n_envs]`` float64 [m @ 500 nm].  ``current``: the values
+    in force, a scalar (one r0 for the shard) or ``[n_envs]``.  Without ``env_ids``, ``r0`` is ``[n_envs]``; with them (anything
+    ``normalize_env_ids`` takes) it is one value per listed env, in the order of ``env_ids`` (a mask: ascending), or a scalar for
+    all of them, and the other envs keep their value.  Raises ``ValueError`` for a wrong shape and for values that are not
+    finite and positive.  Pure host code."""
+    n_envs = int(n_envs)
+    if hasattr(r0, "detach"):
+        r0 = r0.detach().cpu().numpy()
+    try:
+        v = np.asarray(r0, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("r0 must be numeric") from None
+    full = np.broadcast_to(np.asarray(current, dtype=np.float64), (n_envs,)).copy()
+    if env_ids is None:
+        if v.shape != (n_envs,):
+            raise ValueError(f"per-env r0 must have shape (n_envs={n_envs},), got {v.shape}")
+        full[:] = v
+    else:
+        given = normalize_env_ids(env_ids, n_envs, return_order=True)[1]
+        if v.ndim != 0 and v.shape != (given.size,):
+            raise ValueError(f"r0 must be a scalar or have one value per listed env, shape ({given.size},), got {v.shape}")
+        full[given] = v
+        v = full[given]
+    if not (np.isfinite(v).all() and (v > 0).all()):
+        raise ValueError("every r0 must be finite and positive")
+    return full
+
+
 def _wall_clock_seed() -> int:
     """The seed of ``generateNewPhaseScreen(seed=None)``: the second of the day (OOPAO/Atmosphere.py:561-563)."""
     import time
@@ -210,6 +239,18 @@ class Shard:
         c = np.ascontiguousarray(clock, dtype=np.float64)
         L.check(self.lib.aoenv_set_clock_env(self.h, c.ctypes.data_as(C.c_void_p)))
 
+    # per-env Fried parameter: r0 [n_env] metres at 500 nm (None: one r0 for the shard again); r0_tables: the r0 of the uploaded C_AB
+    def set_r0_env(self, r0, r0_tables: float, stream=0):
+        a = None if r0 is None else np.ascontiguousarray(r0, dtype=np.float64)
+        if a is not None and a.shape != (self.cfg.n_env,):
+            raise ValueError(f"per-env r0 must have shape ({self.cfg.n_env},)")
+        L.check(self.lib.aoenv_set_r0_env(self.h, None if a is None else a.ctypes.data_as(C.c_void_p), float(r0_tables), C.c_void_p(stream)))
+
+    def get_r0_env(self) -> np.ndarray:
+        out = np.zeros(self.cfg.n_env)
+        L.check(self.lib.aoenv_get_r0_env(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
 
 # ----------------------------------------------------------------------------------------------------
 # reach-through proxies (only the uses listed in SURVEY.md 8b)
@@ -256,15 +297,23 @@ class _AtmProxy:
 
     @property
     def r0(self):
-        return self._e.param.r0
+        """The shard's r0, or -- per-env r0 active (set_r0_per_env) -- an [n_envs] array."""
+        e = self._e
+        return e.param.r0 if e._r0_env is None else e._r0_env.copy()
 
     @r0.setter
     def r0(self, val):
-        """OOPAO/Atmosphere.py:792-807: rescales the covariances; only B changes (A is r0-invariant)."""
+        """OOPAO/Atmosphere.py:792-807: rescales the covariances; only B changes (A is r0-invariant).  A scalar: one r0 for the
+        shard (a per-env r0 ends).  An array of length n_envs: every env its own (set_r0_per_env; the tables are not touched)."""
         e = self._e
+        if np.ndim(val) != 0:
+            e.set_r0_per_env(val)
+            return
         e.param.r0 = float(val)
         e._atm_tables.set_r0(e.param.r0)
         e._shard.upload_ring_tables(e._atm_tables, only_ab=True)
+        e._shard.set_r0_env(None, e.param.r0, e._stream())
+        e._r0_env = None
 
     @property
     def nLayer(self):
@@ -496,6 +545,7 @@ class BatchedAOEnv:
         self._done = None
         self._wind_env = None                                      # (speed, direction) [n_envs, nLayer] once per-env winds are set
         self._per_env_clock = False
+        self._r0_env = None                                        # [n_envs] Fried parameters once per-env r0 is set
 
     # -- construction --------------------------------------------------------------------------------
     def set_params_file(self, param_file, oopao_path):
@@ -578,6 +628,8 @@ class BatchedAOEnv:
 
         # -- the loop shard -----------------------------------------------------------------------------
         self._shard = self._make_shard(self.n_envs, self.dtype, n_layer=p.nLayer, max_group=1)
+        self._r0_env = self._wind_env = None                        # a new shard: one r0, one wind, the shared clock
+        self._per_env_clock = False
         sh = self._shard
         at = self._atm_tables
         sh.upload_ring_tables(at)
@@ -774,6 +826,19 @@ class BatchedAOEnv:
         self._wind_env = (s.copy(), d.copy())
         self._per_env_clock = True
 
+    def set_r0_per_env(self, r0, env_ids=None):
+        """Every env its own Fried parameter [m @ 500 nm]: ``r0`` of shape [n_envs], or -- with ``env_ids`` (a list or a mask) --
+        one value per listed env (or one scalar for them), the others keeping theirs (from the uniform state: ``param.r0``).
+        What a driver does that loops over an r0 list with ``env.atm.r0 = ...`` between runs, batched.  The ring tables are not
+        touched: B goes as r0^(-5/6) and A not at all, so env e's innovations are scaled by (param.r0 / r0[e])^(5/6) where they
+        are drawn (``aoenv_set_r0_env``).  It takes effect from each env's next ring extrusion; screens already on the device are
+        not rescaled (the reference's setter does not do that either, OOPAO/Atmosphere.py:792-807) -- new screens
+        (``generate_new_phase_screen``, ``reset_envs``) are drawn at each env's own r0.  ``atm.r0 = array`` calls this;
+        ``atm.r0 = scalar`` returns to one r0.  Multi-GPU: each rank passes the values of its own envs."""
+        full = resolve_r0_per_env(r0, env_ids, self.n_envs, self.param.r0 if self._r0_env is None else self._r0_env)
+        self._shard.set_r0_env(full, self.param.r0, self._stream())
+        self._r0_env = full
+
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset
         return int(seed) + idx * self.env_seed_stride
@@ -800,6 +865,7 @@ class BatchedAOEnv:
                 raise ValueError(f"screens must be a list of per-layer arrays [{self.n_envs}, N_l, N_l] with N_l = {at.layer_res}")
             flat = np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in screens])
             self._shard.new_screens(flat, ring, self._stream())
+        # (a per-env r0 is kept too: the library draws every env's screens and first ring at its own r0)
         if self._wind_env is not None:
             self.set_wind_per_env(reset=True)                       # every env keeps its own wind over the episodes
         else:
@@ -809,7 +875,7 @@ class BatchedAOEnv:
         """tel*dm*wfs: one WFS measurement of (atmosphere + DM), no turbulence update."""
         self._shard.measure(self._stream())
 
-    def reset_envs(self, env_ids, seed=None):
+    def reset_envs(self, env_ids, seed=None, r0=None):
         """A new episode for SOME envs (``aoenv_reset_envs``): what ``generate_new_phase_screen(seed); dm.coefs = 0; dm_prev = 0;
         measure(); reset_soft()`` does for the whole batch, for the listed envs only -- a diverged loop restarted on its own,
         staggered episodes, autoreset.  Every other env's screens, streams, clocks and commands stay as they are.
@@ -820,7 +886,10 @@ class BatchedAOEnv:
         wall clock, as ``generate_new_phase_screen`` does.  Returns the ``reset_soft()`` observations of the listed envs,
         ``[k, nAct, nAct]`` in the order of ``env_ids``, as a new tensor (``output='numpy'``: the one env's array); the same rows are
         put into the env's retained last observation (``get_state``).  Tensors handed out earlier are not written to: the
-        observation a caller holds for the other envs stays valid.
+        observation a caller holds for the other envs stays valid.  ``r0``: a scalar or one value per listed env -- the listed envs
+        restart with that Fried parameter (``set_r0_per_env(r0, env_ids)``, applied before the device reset); None: every env keeps
+        the r0 it has.  Bad arguments raise before anything is touched; if the library refuses the reset itself (layers on grids of
+        their own, a shared wind of a pixel per frame or more), the r0 values of before the call are put back before the error is raised.
 
         The shard runs per-env clocks from here on (see ``set_wind_per_env``; per-env winds set earlier are kept).  The
         measurement behind the returned observation is ONE ``measure()`` of the whole shard: it consumes one camera frame number
@@ -841,7 +910,16 @@ class BatchedAOEnv:
                 raise ValueError(f"seed must be an int or {k} integers, one per listed env")
         p, at = self.param, self._atm_tables
         scr, ring = _layer_seeds(seeds, p.nLayer)
-        self._shard.reset_envs(given, scr, ring, p.r0, p.L0, at.layer_D / at.N, self._stream())
+        before = self._r0_env
+        if r0 is not None:
+            self.set_r0_per_env(r0, given)
+        try:
+            self._shard.reset_envs(given, scr, ring, p.r0, p.L0, at.layer_D / at.N, self._stream())
+        except L.AoEnvError:
+            if r0 is not None:                                      # the library refused the reset: the r0 of before the call again
+                self._shard.set_r0_env(before, p.r0, self._stream())
+                self._r0_env = before
+            raise
         self._per_env_clock = True
         self.measure()
         scratch = torch.empty_like(self._obs)
@@ -951,6 +1029,7 @@ class BatchedAOEnv:
             "buff": None if self._per_env_clock else sh.get_buff(p.nLayer).copy(),
             "clock_env": sh.get_clock_env(p.nLayer, self.n_envs) if self._per_env_clock else None,
             "wind_env": self._wind_env,
+            "r0_env": None if self._r0_env is None else self._r0_env.copy(),
             "mt": sh.download(L.B_MT_STATE, (p.nLayer, self.n_envs, 625), st, dtype=np.uint32),
             "coefs": sh.download(L.B_COEFS, (self.n_envs, self.nValidAct), st),
             "dm_prev": sh.download(L.B_DM_PREV, (self.n_envs, self.nValidAct), st),
@@ -964,6 +1043,11 @@ class BatchedAOEnv:
         sh, p = self._shard, self.param
         st = self._stream()
         p.windSpeed, p.windDirection = list(state["windSpeed"]), list(state["windDirection"])
+        if state.get("r0_env") is not None:                          # (a checkpoint from before per-env r0 existed has no such key)
+            self.set_r0_per_env(state["r0_env"])
+        elif self._r0_env is not None:
+            sh.set_r0_env(None, p.r0, st)
+            self._r0_env = None
         if state.get("clock_env") is not None:                       # per-env clocks: ratios and accumulators of every env
             clk = np.asarray(state["clock_env"])
             self._shard.set_wind_env(clk[..., :2], False, st)

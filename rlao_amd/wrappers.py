@@ -18,6 +18,11 @@ def _env_rows(env, env_ids):
     return normalize_env_ids(env_ids, getattr(env, "n_envs", 1), return_order=True)[1].astype("int64")
 
 
+def _reset_envs(env, env_ids, seed, r0):
+    """``env.reset_envs``; ``r0`` (a new Fried parameter for the listed envs) is passed on only when it is given."""
+    return env.reset_envs(env_ids, seed) if r0 is None else env.reset_envs(env_ids, seed, r0=r0)
+
+
 def _with_rows_cleared(buffered, rows):
     """Copies of the buffered actions with the rows of the listed envs zeroed (the buffered tensors are the caller's own)."""
     out = []
@@ -57,8 +62,11 @@ class TorchWrapper:
     def reset_soft(self):
         return _torch().as_tensor(self._env.reset_soft(), dtype=_torch().float32)
 
-    def reset_envs(self, env_ids, seed=None):
-        return _torch().as_tensor(self._env.reset_envs(env_ids, seed), dtype=_torch().float32)
+    def reset_envs(self, env_ids, seed=None, r0=None):
+        return _torch().as_tensor(_reset_envs(self._env, env_ids, seed, r0), dtype=_torch().float32)
+
+    def set_r0_per_env(self, r0, env_ids=None):
+        return self._env.set_r0_per_env(r0, env_ids)
 
 
 class TimeDelayEnv:
@@ -94,12 +102,15 @@ class TimeDelayEnv:
         self._fill()
         return obs
 
-    def reset_envs(self, env_ids, seed=None):
+    def reset_envs(self, env_ids, seed=None, r0=None):
         """A new episode for the listed envs (``BatchedAOEnv.reset_envs``): their rows of the delayed actions are cleared too."""
         rows = _env_rows(self._env, env_ids)
-        obs = self._env.reset_envs(env_ids, seed)
+        obs = _reset_envs(self._env, env_ids, seed, r0)
         self.action_buffer = _with_rows_cleared(self.action_buffer, rows)
         return obs
+
+    def set_r0_per_env(self, r0, env_ids=None):
+        return self._env.set_r0_per_env(r0, env_ids)
 
     def step(self, i, action):
         self.action_buffer.append(action)
@@ -209,7 +220,11 @@ class HistoryEnv:
         self._push(obs)
         return self._out(), {}
 
-    def reset_envs(self, env_ids, seed=None):
+    def set_r0_per_env(self, r0, env_ids=None):
+        """Every env its own Fried parameter (``BatchedAOEnv.set_r0_per_env``); histories and delayed actions go on."""
+        return self._env.set_r0_per_env(r0, env_ids)
+
+    def reset_envs(self, env_ids, seed=None, r0=None):
         """``reset()`` for the listed envs only (``BatchedAOEnv.reset_envs``): new turbulence, flat DM and one measurement for them;
         their history rows restart as ``reset()`` starts the whole batch -- empty but for the new observation in the newest slot -- and
         their rows of the delayed actions are cleared.  The other envs' histories, and the frame counter, go on.  Returns the windows
@@ -218,7 +233,7 @@ class HistoryEnv:
         torch = _torch()
         h = self._hist
         rows = _env_rows(self._env, env_ids)
-        obs = torch.as_tensor(self._env.reset_envs(env_ids, seed), dtype=torch.float32, device=h.buf.device)
+        obs = torch.as_tensor(_reset_envs(self._env, env_ids, seed, r0), dtype=torch.float32, device=h.buf.device)
         if obs.dim() == 2:
             obs = obs.unsqueeze(0)
         sel = torch.as_tensor(rows, device=h.buf.device)
