@@ -151,13 +151,18 @@ int aoenv_upload_layer(AoEnv* env, int kind, int layer, const void* h_data, size
 int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff);
 
 /* The same setters when every env has its OWN wind (a trainer that draws wind speed / direction per run, e.g.
- * MAIN/integrator_oopao_razor.py:41-44, batched): h_ratio is [n_layer][n_env][2] float64, |ratio| < 1 pixel per frame.
+ * MAIN/integrator_oopao_razor.py:41-44, batched): h_ratio is [n_layer][n_env][2] float64, |ratio| < n pixels per frame on each
+ * axis, n the ceiling AOENV_OPT_ENV_WIND_PIXELS (default 1); a larger ratio is refused with nothing changed.
  * The shard switches to per-env clocks for good: accumulators, torus origins and warp taps of every (env, layer) live on
  * the device and are advanced there, by the same arithmetic as the shared host clock (an env stepped by its own clock is
  * bit-identical to a shard stepped with that wind); on every step one launch per layer advances the clocks and prepares the
- * ring operands of the envs that cross a pixel, and the ring GEMM runs over the whole shard.  aoenv_set_wind keeps working
+ * ring operands of the envs that cross a pixel, and the ring GEMM runs over the whole shard.  A layer in which some env's wind is
+ * a pixel per frame or more first makes max over the envs of max(floor |rx|, floor |ry|) whole-pixel rounds (scatter of the round
+ * before, one launch for the operands of the envs that take part, the GEMM over the whole shard), in the order of the shared
+ * clock: all whole pixels, then the sub-pixel crossing, from the env's one stream.  aoenv_set_wind keeps working
  * afterwards (the same wind for every env); new screens reset accumulators and origins as for the shared clock.
- * Clock state for checkpoints: h_clock [n_layer][n_env][4] float64 = {ratio x, ratio y, buff x, buff y}. */
+ * Clock state for checkpoints: h_clock [n_layer][n_env][4] float64 = {ratio x, ratio y, buff x, buff y}; aoenv_set_clock_env
+ * takes |ratio| below the same ceiling and |buff| < 1, and changes nothing when it refuses. */
 int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* stream);
 int aoenv_get_clock_env(AoEnv* env, double* h_clock);
 int aoenv_set_clock_env(AoEnv* env, const double* h_clock);
@@ -213,7 +218,8 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
  * its commands zeroed; screens, streams, clocks, commands and telemetry of every other env stay bit for bit as they were.
  * The shard switches to per-env clocks FOR GOOD, exactly as aoenv_set_wind_env does (a shared origin cannot describe one env
  * restarted at origin 0): from the shared clock every env starts at the shared origin and accumulator with the shard's wind, which
- * must be < 1 pixel per frame; a deferred ring is scattered and a ring look-ahead forgotten first.  From then on the shard pays the
+ * must be below the ceiling AOENV_OPT_ENV_WIND_PIXELS (default: < 1 pixel per frame) and is handed to every env's clock; a
+ * deferred ring is scattered and a ring look-ahead forgotten first.  From then on the shard pays the
  * cost of per-env clocks on every step (the ring kernels run on every step: about 26 % at the 8 m Shack-Hartmann geometry,
  * DESIGN.md section 4.2).  The screen generation and the ring operands are work for n_idx envs, driven by a device index list;
  * the ring product itself runs once per layer over the whole shard, so that it sums in the order of the full reset.
@@ -222,7 +228,7 @@ int aoenv_new_screens_device(AoEnv* env, const uint32_t* h_screen_seeds, const u
  * env at a new seeing, call aoenv_set_r0_env first.
  * n_idx == 0 succeeds and does nothing (the clocks stay as they are).  Refused, with nothing changed: null pointers, n_idx < 0,
  * an index outside [0, n_env), a duplicate index, n_layer == 0, missing ring tables, non-positive r0 / L0 / pixel_size, a shared
- * wind of a pixel per frame or more, and shards with layers on grids of their own (AoCfg.layer_res_l), which have no per-env
+ * wind at or above the ceiling AOENV_OPT_ENV_WIND_PIXELS (default: a pixel per frame or more), and shards with layers on grids of their own (AoCfg.layer_res_l), which have no per-env
  * clocks.  Host synchronisation as in aoenv_new_screens_device (the stream is waited for once, before the clocks are switched). */
 int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint32_t* h_screen_seeds,
                      const uint32_t* h_ring_seeds, double r0, double L0, double pixel_size, void* stream);
@@ -336,6 +342,11 @@ enum AoOption {
                                  their own in front of the GEMM.  [Round-2 note: the same work one crossing ahead on a SECOND STREAM was
                                  slower -- with one 1024-lane workgroup per CU the side stream finds no free CU (5.59 -> 4.97 M env-steps/s)] */
     AOENV_OPT_FAST_TRIG = 2, /* 1 (default): v_sin/v_cos after Cody-Waite reduction in the float32 SH kernel; 0: sincosf */
+    AOENV_OPT_ENV_WIND_PIXELS = 10, /* n in [1, 8] (default 1): per-env clocks (aoenv_set_wind_env, aoenv_set_clock_env, the switch
+                                 inside aoenv_reset_envs) take |ratio| < n pixels per frame on each axis; a step then makes up to n - 1
+                                 whole-pixel ring rounds per layer in front of the sub-pixel one.  Other values are rejected, and so is
+                                 lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
+                                 whose winds stay below one pixel per frame nothing: the same launches */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
                                  also keeps the shard off the fused step kernel; other bits are rejected */
 };

@@ -21,7 +21,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
 
 
 (OPT_FAST_WFS, OPT_MFMA_GEMM, OPT_FAST_TRIG, OPT_STORE_ATM_OPD, OPT_FUSED_TAIL, OPT_FUSED_STEP, OPT_DEFER_RING, OPT_COEFS_IMAGE,
- OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD) = range(10)
+ OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD, OPT_ENV_WIND_PIXELS) = range(11)
 OPT_FORCE_PATH = 99
 # enum AoPath: bits of OPT_FORCE_PATH
 PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN = 256, 512, 1024

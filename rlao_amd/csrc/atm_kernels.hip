@@ -42,6 +42,8 @@ int launch_ring_prepare(const T* map, T* zx, const int* inner_idx, const uint32_
 // which envs cross a pixel this step is decided here, on the device, with the host clock's arithmetic (clock_subpixel, common.hpp).
 // Both workgroups of an env read clk_in and come to the same verdict; blockIdx.x == 0 writes the advanced clock to clk_out (the host
 // swaps the two) and this step's taps; an env that crosses gathers its Z through its OLD origin and draws its innovations in place.
+// A clock of a pixel per frame or more has made its whole-pixel rounds in front of this launch (k_ring_round_env), which leave
+// clk_in alone: the OLD origin is clk_in's moved by those rounds (none below one pixel per frame).
 template <typename T>
 __global__ void __launch_bounds__(256) k_ring_prepare_env(const T* __restrict__ map, T* __restrict__ zx,
                                                           const int* __restrict__ inner_idx, uint32_t* mt_state, int* mt_pos,
@@ -50,8 +52,9 @@ __global__ void __launch_bounds__(256) k_ring_prepare_env(const T* __restrict__ 
                                                           int n_outer, int K, const double* __restrict__ xi_scale) {
     const int e = blockIdx.y;
     EnvClock c = clk_in[e];
-    const int oy = c.org[0], ox = c.org[1];
     int bx, by;
+    clock_rounds_origin(c.ratio, clock_rounds(c.ratio, 0, &bx, &by), S, c.org);
+    const int oy = c.org[0], ox = c.org[1];
     const bool cross = clock_subpixel(c.ratio, c.buff, &bx, &by);
     if (blockIdx.x == 0) {
         if (cross) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, bx, by, oy, ox, e, threadIdx.x, 256);
@@ -80,6 +83,46 @@ int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t*
     if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
     hipLaunchKernelGGL(k_ring_prepare_env<T>, dim3(2, n_env), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, clk_in, clk_out,
                        taps, weight, S, n_inner, n_outer, K, xi_scale);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+
+// Round j of the whole-pixel rounds of a step (per-env clocks of a pixel per frame or more; clock_rounds, common.hpp): the part of
+// updateLayer in front of the sub-pixel crossing, one extrusion per round.  Both workgroups of an env read its clock, which no
+// round changes, and decide whether the env takes part in round j.  One that does gathers its Z through its origin after the j
+// earlier rounds and draws its innovations in place; blockIdx.x == 0 records ring = 1 and the origin after this round in the env's
+// taps row for the scatter (the other fields of the row are rewritten by k_ring_prepare_env before anyone reads them).  An env
+// that sits the round out gets ring = 0.
+template <typename T>
+__global__ void __launch_bounds__(256) k_ring_round_env(const T* __restrict__ map, T* __restrict__ zx,
+                                                        const int* __restrict__ inner_idx, uint32_t* mt_state, int* mt_pos,
+                                                        const EnvClock* __restrict__ clk, LayerTaps* __restrict__ taps, int j, int S,
+                                                        int n_inner, int n_outer, int K, const double* __restrict__ xi_scale) {
+    const int e = blockIdx.y;
+    const EnvClock c = clk[e];
+    int sx, sy;
+    const bool part = j < clock_rounds(c.ratio, j, &sx, &sy);
+    if (blockIdx.x == 0) {
+        int org[2] = {c.org[0], c.org[1]};
+        clock_rounds_origin(c.ratio, j, S, org);
+        if (part) gather_ring<T>(map, zx, inner_idx, S, n_inner, K, sx, sy, org[0], org[1], e, threadIdx.x, 256);
+        if (threadIdx.x == 0) {
+            taps[e].oy = ((org[0] - sy) % S + S) % S;
+            taps[e].ox = ((org[1] - sx) % S + S) % S;
+            taps[e].ring = part ? 1 : 0;
+        }
+    } else if (part) {
+        mt_normal_body<T>(mt_state, mt_pos, mt_state, mt_pos, zx, K, n_inner, n_outer, e, xi_scale);
+    }
+}
+
+template <typename T>
+int launch_ring_round_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk,
+                          LayerTaps* taps, int j, int n_env, int S, int n_inner, int n_outer, int K, const double* xi_scale,
+                          hipStream_t st) {
+    if (n_outer % 2) return fail("mt_normal: n_outer=%d must be even", n_outer);
+    hipLaunchKernelGGL(k_ring_round_env<T>, dim3(2, n_env), dim3(256), 0, st, map, zx, inner_idx, mt_state, mt_pos, clk, taps, j, S,
+                       n_inner, n_outer, K, xi_scale);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -253,6 +296,8 @@ int launch_reset_env_rows(const int* env_idx, int n_idx, T* coefs, T* dm_prev, i
                                           hipStream_t, const LayerTaps*);                                          \
     template int launch_ring_prepare_env<T>(const T*, T*, const int*, uint32_t*, int*, const EnvClock*, EnvClock*, LayerTaps*, \
                                             double, int, int, int, int, int, const double*, hipStream_t);                                                       \
+    template int launch_ring_round_env<T>(const T*, T*, const int*, uint32_t*, int*, const EnvClock*, LayerTaps*, int, int, int, \
+                                          int, int, int, const double*, hipStream_t);                              \
     template int launch_minmax<T>(const T*, T*, int, int, hipStream_t);                                            \
     template int launch_reset_env_rows<T>(const int*, int, T*, T*, int, EnvClock*, LayerTaps*, int, int, hipStream_t);
 INST(float)

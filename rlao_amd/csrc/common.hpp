@@ -51,7 +51,7 @@ struct LayerTaps {
 // aoenv_set_wind_env: k_ring_prepare_env): the same source, compiled without floating-point contraction, so that an env
 // stepped by its own clock is bit-identical to a shard stepped by the host clock with that wind.
 struct EnvClock {
-    double ratio[2];       // pixels per frame (x, y), |ratio| < 1 for per-env clocks          Atmosphere.py:362-363
+    double ratio[2];       // pixels per frame (x, y); per-env clocks: |ratio| < AOENV_OPT_ENV_WIND_PIXELS   Atmosphere.py:362-363
     double buff[2];        // sub-pixel accumulator                                             Atmosphere.py:392-404
     int org[2];            // torus origin (oy, ox)
     int pad_[2];
@@ -76,6 +76,36 @@ __host__ __device__ inline bool clock_subpixel(const double ratio[2], double buf
     *by = fabs(buff[1]) < 1 ? 0 : (int)clock_sgn(buff[1]);
     for (int d = 0; d < 2; ++d) buff[d] = fmod(fabs(buff[d]), 1.0) * clock_sgn(buff[d]);
     return *bx != 0 || *by != 0;
+}
+
+// the whole-pixel part of updateLayer (OOPAO/Atmosphere.py:378-389), in front of the sub-pixel one: a clock makes
+// mx = max(floor |rx|, floor |ry|) one-pixel extrusions ("rounds") per step.  With mn the smaller floor, a round j < mn moves
+// (sgn rx, sgn ry), a round mn <= j < mx only along the axis whose floor is mx.  Returns mx, and in (*sx, *sy) the direction of
+// round j ((0, 0) for j >= mx: the clock sits that round out).
+__host__ __device__ inline int clock_rounds(const double ratio[2], int j, int* sx, int* sy) {
+#pragma clang fp contract(off)
+    const int nx = (int)fabs(ratio[0]), ny = (int)fabs(ratio[1]);
+    const int mn = nx < ny ? nx : ny, mx = nx > ny ? nx : ny;
+    const int s0 = (int)clock_sgn(ratio[0]), s1 = (int)clock_sgn(ratio[1]);
+    if (j < mn) {
+        *sx = s0;
+        *sy = s1;
+    } else if (j < mx) {
+        *sx = nx == mn ? 0 : s0;
+        *sy = ny == mn ? 0 : s1;
+    } else {
+        *sx = *sy = 0;
+    }
+    return mx;
+}
+
+// the torus origin (oy, ox) after the first j rounds of a step, in closed form: axis d has moved in min(j, floor |r_d|) of them
+__host__ __device__ inline void clock_rounds_origin(const double ratio[2], int j, int S, int org[2]) {
+#pragma clang fp contract(off)
+    const int nx = (int)fabs(ratio[0]), ny = (int)fabs(ratio[1]);
+    const int cx = (j < nx ? j : nx) * (int)clock_sgn(ratio[0]), cy = (j < ny ? j : ny) * (int)clock_sgn(ratio[1]);
+    org[0] = ((org[0] - cy) % S + S) % S;
+    org[1] = ((org[1] - cx) % S + S) % S;
 }
 
 // tap offsets and weights of the sub-pixel warp for the accumulator `buff` (OOPAO/Atmosphere.py:406-407)
@@ -132,6 +162,11 @@ template <typename T>
 int launch_ring_prepare_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk_in,
                             EnvClock* clk_out, LayerTaps* taps, double weight, int n_env, int S, int n_inner, int n_outer, int K,
                             const double* xi_scale, hipStream_t st);
+// round j of the whole-pixel rounds of a per-env step (clock_rounds): [Z | xi] of the envs that take part, their taps' ring / origin
+template <typename T>
+int launch_ring_round_env(const T* map, T* zx, const int* inner_idx, uint32_t* mt_state, int* mt_pos, const EnvClock* clk,
+                          LayerTaps* taps, int j, int n_env, int S, int n_inner, int n_outer, int K, const double* xi_scale,
+                          hipStream_t st);
 // xi_scale of the launches above: [n_env] float64 factors of the innovations (per-env Fried parameter, mt_normal_body), or null
 template <typename T>
 int launch_minmax(const T* maps, T* minmax, int n_env, int S, hipStream_t st);

@@ -59,6 +59,7 @@ struct Layer {
     RingAhead ahead;
     bool gather_next = false;               // the next fused step kernel is to gather Z into zx_pipe[ahead.buf][l]
     bool minmax_dirty = false;              // the min / max table is stale (ring extruded without the min / max pass)
+    int env_rounds = 0;                     // per-env clocks: whole-pixel rounds of a step, the maximum over the envs (clock_rounds)
 };
 
 }  // namespace ao
@@ -80,6 +81,7 @@ struct AoEnv {
     bool per_env_wind = false;
     EnvClock* env_clk[2] = {nullptr, nullptr};   // [L][E] each: current / next (k_ring_prepare_env reads one, writes the other)
     int clk_cur = 0;
+    int wind_pixels = 1;                     // aoenv_set_option(AOENV_OPT_ENV_WIND_PIXELS): per-env clocks take |ratio| < wind_pixels
     LayerTaps* env_taps = nullptr;           // [L][E] taps of the current step
     // per-env Fried parameter (aoenv_set_r0_env): the ring tables stay those of r0_tables; env e's innovations are multiplied by
     // sigma_e = (r0_tables / r0_e)^(5/6) where they are written into [Z | xi] (mt_normal_body), its new screens by (r0 / r0_e)^(5/6)
@@ -465,6 +467,11 @@ int extrude_pipelined(AoEnv* env, int l, int sx, int sy, hipStream_t st) {
 // Per-env clocks: one launch per layer advances every env's clock on the device and prepares [Z | xi] of the envs that cross a
 // pixel; the ring GEMM runs over the whole shard (rows of the other envs are computed and never used: which envs cross is
 // not known on the host, and with independent winds some env crosses on nearly every step anyway).
+// A layer in which some env's wind is a pixel per frame or more (Layer::env_rounds > 0) first makes that many whole-pixel rounds,
+// as the shared clock does in advance_atmosphere: per round the previous round's ring is scattered (the gather reads the screen),
+// k_ring_round_env prepares [Z | xi] of the envs that take part, and the GEMM again runs over the whole shard -- its split count and
+// the order of its sums must not depend on who takes part.  The rounds leave the clocks alone; k_ring_prepare_env then starts from the
+// origin after them.  Per env this is the shared clock's order, all whole rounds and then the sub-pixel crossing, from one stream.
 template <typename T>
 int advance_atmosphere_env(AoEnv* env, bool lean, hipStream_t st) {
     for (int l = 0; l < env->L; ++l) {
@@ -472,6 +479,18 @@ int advance_atmosphere_env(AoEnv* env, bool lean, hipStream_t st) {
         const Layer& y = env->layer[l];
         T* zx = env->as<T>(env->zx);
         const size_t row = (size_t)l * env->E;
+        for (int j = 0; j < y.env_rounds; ++j) {
+            {
+                AO_PROF(env, SHIFT_GATHER, st);
+                AO_TRY(launch_ring_round_env<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur,
+                                                env->env_clk[env->clk_cur] + row, env->env_taps + row, j, env->E, y.S, y.nin, y.nout,
+                                                y.K, env->sigma(), st));
+            }
+            int splits = 1;
+            AO_TRY(ring_gemm<T>(env, l, zx, &splits, st));
+            defer_ring(env, l, zx, splits);
+            AO_TRY(flush_ring<T>(env, l, st));                     // the next gather reads the screen
+        }
         {
             AO_PROF(env, SHIFT_GATHER, st);
             AO_TRY(launch_ring_prepare_env<T>(env->as<T>(env->screen_ptr(l)), zx, y.inner_idx, y.mt_cur, y.pos_cur,
@@ -493,13 +512,11 @@ int advance_atmosphere(AoEnv* env, bool lean, hipStream_t st) {
     for (int l = 0; l < env->L; ++l) {
         LayerClock& k = env->layer[l].clk;
         if (k.ratio[0] == 0 && k.ratio[1] == 0) continue;
-        const int ns[2] = {(int)std::fabs(k.ratio[0]), (int)std::fabs(k.ratio[1])};
-        const int mn = ns[0] < ns[1] ? ns[0] : ns[1], mx = ns[0] > ns[1] ? ns[0] : ns[1];
-        const int s0 = (int)sgn(k.ratio[0]), s1 = (int)sgn(k.ratio[1]);
-        for (int i = 0; i < mn; ++i) AO_TRY(extrude<T>(env, l, s0, s1, lean, st));
-        for (int j = 0; j < mx - mn; ++j)
-            AO_TRY(extrude<T>(env, l, ns[0] == mn ? 0 : s0, ns[1] == mn ? 0 : s1, lean, st));
         int b0, b1;
+        for (int j = 0, mx = clock_rounds(k.ratio, 0, &b0, &b1); j < mx; ++j) {   // whole pixels first (common.hpp)
+            clock_rounds(k.ratio, j, &b0, &b1);
+            AO_TRY(extrude<T>(env, l, b0, b1, lean, st));
+        }
         if (clock_subpixel(k.ratio, k.buff, &b0, &b1)) {          // (the arithmetic the per-env device clocks share, common.hpp)
             if (lean && env->defer_ring && env->use_lookahead && env->zx_pipe && !env->layer[l].ring_pending) {
                 AO_TRY(extrude_pipelined(env, l, b0, b1, st));
@@ -1298,13 +1315,16 @@ static int alloc_env_clocks(AoEnv* env) {
     return 0;
 }
 
-// host copy of the clocks -> device (current buffer) + the taps they imply (no ring pending)
+// host copy of the clocks -> device (current buffer) + the taps they imply (no ring pending), and every layer's round count
 static int push_env_clocks(AoEnv* env, const std::vector<EnvClock>& clk) {
     const size_t n = (size_t)env->L * env->E;
     std::vector<LayerTaps> taps(n);
-    for (int l = 0; l < env->L; ++l)
+    for (int l = 0; l < env->L; ++l) {
+        env->layer[l].env_rounds = 0;                              // (the host holds every ratio here)
         for (int e = 0; e < env->E; ++e) {
             const EnvClock& c = clk[(size_t)l * env->E + e];
+            int sx, sy;
+            env->layer[l].env_rounds = std::max(env->layer[l].env_rounds, clock_rounds(c.ratio, 0, &sx, &sy));
             LayerTaps& t = taps[(size_t)l * env->E + e];
             t = LayerTaps{};
             t.oy = c.org[0];
@@ -1312,6 +1332,7 @@ static int push_env_clocks(AoEnv* env, const std::vector<EnvClock>& clk) {
             taps_from_buff(c.buff, t);
             t.weight = env->layer[l].weight;
         }
+    }
     AO_HIP(hipMemcpy(env->env_clk[env->clk_cur], clk.data(), n * sizeof(EnvClock), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(env->env_taps, taps.data(), n * sizeof(LayerTaps), hipMemcpyHostToDevice));
     return 0;
@@ -1328,7 +1349,9 @@ int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* 
     if (!h_ratio) return fail("null ratio");
     const size_t n = (size_t)env->L * env->E;
     for (size_t i = 0; i < 2 * n; ++i)
-        if (!(std::fabs(h_ratio[i]) < 1.0)) return fail("per-env wind: |ratio| = %g px/frame, must be < 1 (an env extrudes at most one ring per step)", std::fabs(h_ratio[i]));
+        if (!(std::fabs(h_ratio[i]) < (double)env->wind_pixels))
+            return fail("per-env wind: |ratio| = %g px/frame, must be < %d (%s)", std::fabs(h_ratio[i]), env->wind_pixels,
+                        env->wind_pixels == 1 ? "an env extrudes at most one ring per step" : "AOENV_OPT_ENV_WIND_PIXELS");
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int l = 0; l < env->L; ++l) forget_lookahead(env->layer[l]);
     AO_TRY(AO_DISPATCH(env, flush_rings, env, st));                // a deferred ring of the clocks as they were
@@ -1383,7 +1406,7 @@ int aoenv_set_clock_env(AoEnv* env, const double* h_clock) {
     AO_TRY(pull_env_clocks(env, clk));                             // (keeps the origins)
     for (size_t i = 0; i < clk.size(); ++i) {
         for (int d = 0; d < 2; ++d) {
-            if (!(std::fabs(h_clock[4 * i + d]) < 1.0)) return fail("per-env wind: |ratio| must be < 1 px/frame");
+            if (!(std::fabs(h_clock[4 * i + d]) < (double)env->wind_pixels)) return fail("per-env wind: |ratio| must be < %d px/frame", env->wind_pixels);
             if (!(std::fabs(h_clock[4 * i + 2 + d]) < 1.0)) return fail("|buff| must be < 1");
             clk[i].ratio[d] = h_clock[4 * i + d];
             clk[i].buff[d] = h_clock[4 * i + 2 + d];
@@ -1753,8 +1776,8 @@ int aoenv_reset_envs(AoEnv* env, const int32_t* h_env_idx, int n_idx, const uint
         double shard[2 * kMaxLayer];
         for (int l = 0; l < L; ++l) {
             const LayerClock& k = env->layer[l].clk;
-            if (!(std::fabs(k.ratio[0]) < 1.0) || !(std::fabs(k.ratio[1]) < 1.0))
-                return fail("aoenv_reset_envs: the shard's wind is %g px/frame in layer %d; per-env clocks take < 1", std::max(std::fabs(k.ratio[0]), std::fabs(k.ratio[1])), l);
+            if (!(std::fabs(k.ratio[0]) < (double)env->wind_pixels) || !(std::fabs(k.ratio[1]) < (double)env->wind_pixels))
+                return fail("aoenv_reset_envs: the shard's wind is %g px/frame in layer %d; per-env clocks take < %d", std::max(std::fabs(k.ratio[0]), std::fabs(k.ratio[1])), l, env->wind_pixels);
             shard[2 * l] = k.ratio[0];
             shard[2 * l + 1] = k.ratio[1];
         }
@@ -2108,6 +2131,15 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
         case AOENV_OPT_COEFS_IMAGE:
             if (value) AO_TRY(alloc_dm_rows(env));
             env->use_coefs_img = value != 0;
+            return 0;
+        case AOENV_OPT_ENV_WIND_PIXELS:
+            if (value < 1 || value > 8) return fail("AOENV_OPT_ENV_WIND_PIXELS: %d outside [1, 8]", value);
+            if (env->per_env_wind)                                 // (Layer::env_rounds is the largest floor |ratio| the clocks hold)
+                for (int l = 0; l < env->L; ++l)
+                    if (env->layer[l].env_rounds >= value)
+                        return fail("AOENV_OPT_ENV_WIND_PIXELS: layer %d holds a per-env wind of %d px/frame or more, the ceiling cannot go to %d",
+                                    l, env->layer[l].env_rounds, value);
+            env->wind_pixels = value;
             return 0;
         case AOENV_OPT_FORCE_PATH:
             if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN))

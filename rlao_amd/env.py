@@ -545,6 +545,7 @@ class BatchedAOEnv:
         self._done = None
         self._wind_env = None                                      # (speed, direction) [n_envs, nLayer] once per-env winds are set
         self._per_env_clock = False
+        self._wind_pixels = 1                                      # ceiling of the per-env winds [px / frame] (set_wind_ceiling)
         self._r0_env = None                                        # [n_envs] Fried parameters once per-env r0 is set
 
     # -- construction --------------------------------------------------------------------------------
@@ -630,6 +631,7 @@ class BatchedAOEnv:
         self._shard = self._make_shard(self.n_envs, self.dtype, n_layer=p.nLayer, max_group=1)
         self._r0_env = self._wind_env = None                        # a new shard: one r0, one wind, the shared clock
         self._per_env_clock = False
+        self._wind_pixels = 1
         sh = self._shard
         at = self._atm_tables
         sh.upload_ring_tables(at)
@@ -807,11 +809,28 @@ class BatchedAOEnv:
         self._wind_env = None                                      # one wind for the shard again (per-env clocks stay per-env)
         self._shard.set_wind(self._atm_tables.wind_ratio(p.windSpeed, p.windDirection, p.samplingTime), reset)
 
-    def set_wind_per_env(self, speed=None, direction=None, reset: bool = False):
+    @property
+    def wind_pixels(self) -> int:
+        """The ceiling of per-env winds: every env's wind stays below this many pixels per frame on each axis (default 1)."""
+        return self._wind_pixels
+
+    def set_wind_ceiling(self, n: int):
+        """Per-env clocks take winds below ``n`` pixels per frame and axis (``AOENV_OPT_ENV_WIND_PIXELS``; n in 1 .. 8, default
+        1).  Above 1 a step makes up to n - 1 whole-pixel ring rounds per layer in front of the sub-pixel one; a shard whose winds
+        all stay below a pixel per frame launches what it did before.  Also what a shared-clock shard with a wind of a pixel per
+        frame or more needs before ``reset_envs``.  Refused, with nothing changed: n outside 1 .. 8, or at or below a wind the
+        per-env clocks hold."""
+        n = int(n)
+        L.check(self._shard.lib.aoenv_set_option(self._shard.h, L.OPT_ENV_WIND_PIXELS, n))
+        self._wind_pixels = n
+
+    def set_wind_per_env(self, speed=None, direction=None, reset: bool = False, max_pixels=None):
         """Every env its own wind: ``speed`` [m/s] and ``direction`` [deg] of shape [n_envs, nLayer] (one of them may be None:
         the shard's current value).  What a trainer does that draws the wind per run (MAIN/integrator_oopao_razor.py:41-44,
         OOPAO/Atmosphere.py:829-873), batched: env e then evolves exactly like a shard whose shared wind is (speed[e],
-        direction[e]).  At most one pixel per frame and axis.  ``atm.windSpeed = array2d`` / ``atm.windDirection = array2d`` call this."""
+        direction[e]).  Every wind stays below ``wind_pixels`` pixels per frame and axis (default 1); ``max_pixels``: an int raises
+        (or lowers) that ceiling first (``set_wind_ceiling``), None leaves it.  ``atm.windSpeed = array2d`` /
+        ``atm.windDirection = array2d`` call this at the current ceiling."""
         p = self.param
         cur_s, cur_d = (self._wind_env if self._wind_env is not None else
                         (np.tile(np.asarray(p.windSpeed, float), (self.n_envs, 1)), np.tile(np.asarray(p.windDirection, float), (self.n_envs, 1))))
@@ -822,6 +841,8 @@ class BatchedAOEnv:
         ratio = np.zeros((p.nLayer, self.n_envs, 2))
         for e in range(self.n_envs):
             ratio[:, e] = self._atm_tables.wind_ratio(s[e], d[e], p.samplingTime)
+        if max_pixels is not None:
+            self.set_wind_ceiling(max_pixels)
         self._shard.set_wind_env(ratio, reset, self._stream())
         self._wind_env = (s.copy(), d.copy())
         self._per_env_clock = True
@@ -889,7 +910,7 @@ class BatchedAOEnv:
         observation a caller holds for the other envs stays valid.  ``r0``: a scalar or one value per listed env -- the listed envs
         restart with that Fried parameter (``set_r0_per_env(r0, env_ids)``, applied before the device reset); None: every env keeps
         the r0 it has.  Bad arguments raise before anything is touched; if the library refuses the reset itself (layers on grids of
-        their own, a shared wind of a pixel per frame or more), the r0 values of before the call are put back before the error is raised.
+        their own, a shared wind at or above the ceiling ``wind_pixels``), the r0 values of before the call are put back before the error is raised.
 
         The shard runs per-env clocks from here on (see ``set_wind_per_env``; per-env winds set earlier are kept).  The
         measurement behind the returned observation is ONE ``measure()`` of the whole shard: it consumes one camera frame number
@@ -1029,6 +1050,7 @@ class BatchedAOEnv:
             "buff": None if self._per_env_clock else sh.get_buff(p.nLayer).copy(),
             "clock_env": sh.get_clock_env(p.nLayer, self.n_envs) if self._per_env_clock else None,
             "wind_env": self._wind_env,
+            "wind_pixels": self._wind_pixels,
             "r0_env": None if self._r0_env is None else self._r0_env.copy(),
             "mt": sh.download(L.B_MT_STATE, (p.nLayer, self.n_envs, 625), st, dtype=np.uint32),
             "coefs": sh.download(L.B_COEFS, (self.n_envs, self.nValidAct), st),
@@ -1048,9 +1070,14 @@ class BatchedAOEnv:
         elif self._r0_env is not None:
             sh.set_r0_env(None, p.r0, st)
             self._r0_env = None
+        ceiling = int(state.get("wind_pixels", 1))                   # (a checkpoint from before the ceiling existed: 1)
+        if ceiling > self._wind_pixels:
+            self.set_wind_ceiling(ceiling)                           # up: before the clocks that need it
         if state.get("clock_env") is not None:                       # per-env clocks: ratios and accumulators of every env
             clk = np.asarray(state["clock_env"])
             self._shard.set_wind_env(clk[..., :2], False, st)
+            if ceiling < self._wind_pixels:
+                self.set_wind_ceiling(ceiling)                       # down: after the clocks that were over it are gone
             self._per_env_clock = True
             self._wind_env = state.get("wind_env")
             sh.upload_state(L.B_SCREEN, self._flat_screens(state["screen"]), st)
@@ -1058,6 +1085,8 @@ class BatchedAOEnv:
         else:
             if self._per_env_clock:
                 raise ValueError("this env runs per-env clocks; the state was saved from a shared-clock env")
+            if ceiling < self._wind_pixels:
+                self.set_wind_ceiling(ceiling)
             self._push_wind(reset=False)
             sh.upload_state(L.B_SCREEN, self._flat_screens(state["screen"]), st)
             sh.set_buff(state["buff"])
