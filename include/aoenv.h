@@ -116,7 +116,8 @@ enum AoBuf {
     AOENV_B_XI,              /* [n_env][n_inner+n_outer] last [Z | xi] operand of the ring extrusion      */
     AOENV_B_MT_STATE,        /* [n_layer][n_env][625] uint32 (whatever the env dtype): the 624 MT19937 state words of
                                 the layer's ring RandomState and its position (OOPAO/Atmosphere.py:201, 308)         */
-    AOENV_B_COUNTERS,        /* [4] uint32: frame counter of the camera noise streams, 3 reserved                 */
+    AOENV_B_COUNTERS,        /* [4] uint32: frame counter of the camera noise streams, step counter of the exploration
+                                stream (aoenv_run_rollout), 2 reserved                                              */
     AOENV_B_DM_PREV,         /* [n_env][A]     env.dm_prev: the leaky integrator's state.  aoenv_step computes
                                 dm.coefs = dm_prev * leak + action and copies it back to dm_prev; aoenv_set_coefs (dm.coefs = ...
                                 from outside) leaves it alone, as in the reference (MAIN/OOPAOEnv/OOPAOEnv.py:314, 508-509), so
@@ -270,6 +271,43 @@ int aoenv_step(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_fra
  * action = gain * obs; obs, reward, strehl = step(i0 + k, action).  d_obs is in/out. */
 int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_obs, void* d_frame,
                          void* d_reward, void* d_strehl, void* stream);
+
+/* Replaces: env.sample_noise's filter F = M2C_CL @ pinv(M2C_CL) (MAIN/OOPAOEnv/OOPAOEnv.py:383, 566-570), for aoenv_run_rollout.
+ * F = Fl @ Fr in factored form.  h_factors = [f64 K*A] Fr then [f64 A*K] Fl;  K in [1, A].
+ * NULL / K == 0: no filter (n = z: the reference's F = 1 before set_params).  Refused with nothing changed: K out of range,
+ * non-finite entries.  The stream is waited for once. */
+int aoenv_set_noise_filter(AoEnv* env, const double* h_factors, int K, void* stream);
+
+/* Replaces: the exploration episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89), kept on the device and recorded:
+ *     action = gain * obs + env.sample_noise(sigma);  next_obs, _, reward, strehl, done, _ = env.step(i, action)
+ * for the frames [i0, i0 + n_steps), every observation, action, reward and Strehl ratio written into the caller's trajectory buffers
+ * (what replay.append takes).  One extra launch per step forms the action; the step is the explicit-action step of aoenv_step, so a
+ * twin env stepped with the recorded actions reproduces the trajectory bit for bit, on every kind of shard.
+ * The noise is sigma_e * vec_to_img(Fl (Fr z)), z ~ N(0, 1)^A from a counter-based Philox4x32-7 stream (rlao_amd/csrc/explore.hpp)
+ * keyed by `seed` and indexed by (quad of valid actuators, env_index_offset + env, exploration step counter): reproducible, and the
+ * same for an env wherever it sits in a batch.  Step k of a call uses counter + k and the call leaves counter + n_steps behind; the
+ * counter restarts at 0 only when `seed` differs from the previous call's, and it is word 1 of AOENV_B_COUNTERS (a counter
+ * uploaded with aoenv_upload_state belongs to the seed of the next call).  gain * obs is one multiply in the env dtype: at
+ * sigma == 0 the action is bit for bit the gain * obs a caller forms.
+ * Refused: a null cfg / d_obs / d_action, frames outside [0, n_loop), a negative or non-finite sigma or gain, (A + K) elements that do
+ * not fit in a workgroup's LDS, and what aoenv_step refuses.  d_sigma_env is not inspected (it lives on the device).
+ * A return accumulator, if attached, receives every step's reward. */
+typedef struct AoRollout {
+    int32_t  i0, n_steps;          /* frames [i0, i0 + n_steps) within n_loop; n_steps == 0 succeeds and does nothing */
+    int32_t  env_index_offset;     /* global index of env 0 of this shard */
+    int32_t  reserved;
+    double   gain;                 /* may be 0: open-loop exploration */
+    double   sigma;                /* >= 0, used when d_sigma_env is NULL */
+    const void* d_sigma_env;       /* [n_env] env dtype, caller-owned, or NULL */
+    uint64_t seed;
+} AoRollout;
+
+/* d_obs    [n_steps+1][n_env][nAct][nAct]  slot 0 = the current observation (in); slot k+1 = obs after step k (out)
+ * d_action [n_steps][n_env][nAct][nAct]    out: the action applied in step k
+ * d_reward, d_strehl [n_steps][n_env]      out, either may be NULL
+ * d_frame  [n_env][cam][cam] or NULL       out: the LAST step's frame, as aoenv_run_integrator */
+int aoenv_run_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward,
+                      void* d_strehl, void* d_frame, void* stream);
 
 /* Replaces: tel.computePSF(zeroPaddingFactor) (OOPAO/Telescope.py:258-357) of the current residual phase (tel.src.phase):
  * d_psf [n_env][M][M], M = zero_padding * R (even), env dtype: the short-exposure PSF of every env.  As the reference does for even

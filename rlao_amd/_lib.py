@@ -44,6 +44,11 @@ class AoDetector(C.Structure):
                 ("readout_noise", C.c_double), ("seed", C.c_uint64)]
 
 
+class AoRollout(C.Structure):
+    _fields_ = [("i0", C.c_int32), ("n_steps", C.c_int32), ("env_index_offset", C.c_int32), ("reserved", C.c_int32),
+                ("gain", C.c_double), ("sigma", C.c_double), ("d_sigma_env", C.c_void_p), ("seed", C.c_uint64)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "aoenv_last_error": (C.c_char_p, []),
@@ -68,6 +73,9 @@ EXPORTS = {
                              C.c_void_p]),
     "aoenv_run_integrator": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_noise_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "aoenv_run_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "aoenv_compute_psf": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -343,6 +343,24 @@ int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes
 int step_alias_capacity(int n_act);
 int launch_env_step(const StepArgs& a, hipStream_t st);
 
+// exploration action of aoenv_run_rollout (rollout_kernels.hip): action = gain * obs + sigma_e vec_to_img(Fl (Fr z)), z from explore.hpp
+template <typename T>
+struct RolloutActionArgs {
+    const T* obs;            // [E][nAct^2]
+    T* action;               // [E][nAct^2]
+    const T* fr;             // [K][A] right factor of the noise filter, or null with n_filter == 0 (n = z)
+    const T* fl_t;           // [K][A] left factor, transposed
+    const int* act_slot;     // [nAct^2] pixel -> index among the valid actuators, -1 = not an actuator
+    const T* sigma_env;      // [E] or null: sigma for every env
+    T gain, sigma;
+    int n_act, n_valid_act, n_filter;
+    uint32_t seed_lo, seed_hi, counter, env_offset;
+};
+constexpr size_t kRolloutLdsMax = 160 * 1024;                     // LDS of a CU
+size_t rollout_action_lds(int n_valid_act, int n_filter, size_t esz);
+template <typename T>
+int launch_rollout_action(const RolloutActionArgs<T>& a, int n_env, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

@@ -160,6 +160,18 @@ struct AoEnv {
     PoissonAlias alias() const { return PoissonAlias{alias_tab, alias_words, alias_lmax}; }
     bool det_seeded = false;                // a seed has been set: the frame counter survives later aoenv_set_detector calls
     void* ret_acc = nullptr;                // caller-owned [E] episode-return accumulator (aoenv_set_return_accumulator)
+    // exploration rollout (aoenv_run_rollout): the noise filter F = Fl Fr in factored form, the inverse of act_idx, the stream position
+    void* noise_fr = nullptr;               // [K][A]
+    void* noise_fl_t = nullptr;             // [K][A] Fl transposed
+    size_t noise_cap = 0;                   // elements each of the two is sized for
+    int noise_K = 0;                        // 0: no filter (n = z)
+    std::vector<int32_t> h_act_idx;         // host copy of AOENV_C_ACT_IDX
+    int* act_slot = nullptr;                // [nAct^2] pixel -> index among the valid actuators, -1 elsewhere
+    bool act_slot_dirty = true;
+    void* rollout_scratch = nullptr;        // [2][E] reward / strehl rows nobody asked for
+    uint32_t explore_counter = 0;           // word 1 of AOENV_B_COUNTERS
+    uint64_t explore_seed = 0;
+    bool explore_seeded = false;            // false: the counter (0, or an uploaded checkpoint's) belongs to the next call's seed
     std::vector<void*> allocs;
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool use_fast_wfs = true;               // aoenv_set_option(AOENV_OPT_FAST_WFS)
@@ -1213,6 +1225,8 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             for (int i = 0; i < env->A; ++i)
                 if (ix[i] < 0 || ix[i] >= env->nAct * env->nAct) return fail("actuator index %d out of range", ix[i]);
             AO_HIP(hipMemcpy(env->act_idx, h, (size_t)env->A * 4, hipMemcpyHostToDevice));
+            env->h_act_idx.assign(ix, ix + env->A);
+            env->act_slot_dirty = true;
             break;
         }
         case AOENV_C_WFS_AMP:
@@ -1875,6 +1889,103 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
     return 0;
 }
 
+int aoenv_set_noise_filter(AoEnv* env, const double* h_factors, int K, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_factors || K == 0) {
+        env->noise_K = 0;
+        return 0;
+    }
+    const int A = env->A;
+    if (K < 1 || K > A) return fail("aoenv_set_noise_filter: rank %d outside [1, A=%d]", K, A);
+    const size_t n = (size_t)K * A;
+    for (size_t i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(h_factors[i])) return fail("aoenv_set_noise_filter: entry %zu is not finite", i);
+    AO_HIP(hipStreamSynchronize(st));                              // a rollout in flight reads the factors in place
+    if (n > env->noise_cap) {
+        void *fr = nullptr, *fl = nullptr;
+        AO_TRY(dmalloc(env, &fr, n * env->esz, false));
+        AO_TRY(dmalloc(env, &fl, n * env->esz, false));
+        env->noise_fr = fr; env->noise_fl_t = fl; env->noise_cap = n;
+    }
+    std::vector<double> t(n);                                      // Fl [A][K] -> [K][A]
+    const double* fl = h_factors + n;
+    for (int a = 0; a < A; ++a)
+        for (int k = 0; k < K; ++k) t[(size_t)k * A + a] = fl[(size_t)a * K + k];
+    env->noise_K = 0;                                              // (a failed copy leaves no half-written filter in use)
+    AO_TRY(upload_real(env, env->noise_fr, h_factors, n));
+    AO_TRY(upload_real(env, env->noise_fl_t, t.data(), n));
+    env->noise_K = K;
+    return 0;
+}
+
+extern "C++" {
+template <typename T>
+static int run_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl, void* d_frame,
+                         uint32_t counter, hipStream_t st) {
+    const size_t img = (size_t)env->nAct * env->nAct, E = env->E;
+    T* scratch = env->as<T>(env->rollout_scratch);
+    RolloutActionArgs<T> a{};
+    a.fr = env->noise_K ? env->as<T>(env->noise_fr) : nullptr;
+    a.fl_t = env->noise_K ? env->as<T>(env->noise_fl_t) : nullptr;
+    a.act_slot = env->act_slot;
+    a.sigma_env = static_cast<const T*>(cfg->d_sigma_env);
+    a.gain = (T)cfg->gain;
+    a.sigma = (T)cfg->sigma;
+    a.n_act = env->nAct;
+    a.n_valid_act = env->A;
+    a.n_filter = env->noise_K;
+    a.seed_lo = (uint32_t)(cfg->seed & 0xffffffffu);
+    a.seed_hi = (uint32_t)(cfg->seed >> 32);
+    a.env_offset = (uint32_t)cfg->env_index_offset;
+    for (int k = 0; k < cfg->n_steps; ++k) {
+        const bool last = k == cfg->n_steps - 1;
+        a.obs = static_cast<const T*>(d_obs) + (size_t)k * E * img;
+        a.action = static_cast<T*>(d_action) + (size_t)k * E * img;
+        a.counter = counter + (uint32_t)k;
+        AO_TRY(launch_rollout_action<T>(a, env->E, st));
+        // the explicit-action step of aoenv_step; only the last step's residual phase and frame can be read afterwards
+        AO_TRY(step_t<T>(env, cfg->i0 + k, a.action, static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
+                         d_reward ? static_cast<T*>(d_reward) + (size_t)k * E : scratch,
+                         d_strehl ? static_cast<T*>(d_strehl) + (size_t)k * E : scratch + E, 0.0, last, st));
+    }
+    return 0;
+}
+}  // extern "C++"
+
+int aoenv_run_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl, void* d_frame,
+                      void* stream) {
+    AO_CHECK_ENV(env);
+    if (!cfg || !d_obs || !d_action) return fail("aoenv_run_rollout: null cfg / obs / action");
+    if (cfg->i0 < 0 || cfg->n_steps < 0 || (int64_t)cfg->i0 + cfg->n_steps > env->c.n_loop)
+        return fail("frames [%d, %lld) outside [0, n_loop=%d)", cfg->i0, (long long)cfg->i0 + cfg->n_steps, env->c.n_loop);
+    if (!(cfg->sigma >= 0) || !std::isfinite(cfg->sigma)) return fail("aoenv_run_rollout: sigma must be finite and >= 0");
+    if (!(cfg->gain >= 0) || !std::isfinite(cfg->gain)) return fail("aoenv_run_rollout: gain must be finite and >= 0");
+    AO_TRY(require_step_constants(env, true));
+    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    if (rollout_action_lds(env->A, env->noise_K, env->esz) > kRolloutLdsMax)
+        return fail("aoenv_run_rollout: %d actuators and filter rank %d need %zu bytes of LDS, a workgroup has %zu", env->A, env->noise_K,
+                    rollout_action_lds(env->A, env->noise_K, env->esz), kRolloutLdsMax);
+    if (cfg->n_steps == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (env->act_slot_dirty) {
+        const size_t img = (size_t)env->nAct * env->nAct;
+        std::vector<int> slot(img, -1);
+        for (int i = 0; i < env->A; ++i) slot[env->h_act_idx[i]] = i;
+        if (!env->act_slot) AO_TRY(dmalloc(env, (void**)&env->act_slot, img * sizeof(int), false));
+        AO_HIP(hipStreamSynchronize(st));
+        AO_HIP(hipMemcpy(env->act_slot, slot.data(), img * sizeof(int), hipMemcpyHostToDevice));
+        env->act_slot_dirty = false;
+    }
+    if (!env->rollout_scratch) AO_TRY(dmalloc(env, &env->rollout_scratch, (size_t)2 * env->E * env->esz));
+    // the stream position goes on from call to call; only another seed starts it again
+    const uint32_t counter = (env->explore_seeded && env->explore_seed != cfg->seed) ? 0 : env->explore_counter;
+    env->explore_seed = cfg->seed;
+    env->explore_seeded = true;
+    env->explore_counter = counter + (uint32_t)cfg->n_steps;
+    return AO_DISPATCH(env, run_rollout_t, env, cfg, d_obs, d_action, d_reward, d_strehl, d_frame, counter, st);
+}
+
 extern "C++" {
 template <typename T>
 static int compute_psf_t(AoEnv* env, int zp, void* d_psf, hipStream_t st) {
@@ -2034,7 +2145,7 @@ int aoenv_download(AoEnv* env, int which, void* h_dst, size_t bytes, void* strea
     }
     if (which == AOENV_B_COUNTERS) {
         uint32_t* out = static_cast<uint32_t*>(h_dst);
-        out[0] = env->det.frame_counter; out[1] = out[2] = out[3] = 0;
+        out[0] = env->det.frame_counter; out[1] = env->explore_counter; out[2] = out[3] = 0;
         return 0;
     }
     if (which == AOENV_B_OPD_ATM && env->L > 0 && !env->atm_user_defined && !env->store_opd_atm) {
@@ -2083,6 +2194,8 @@ int aoenv_upload_state(AoEnv* env, int which, const void* h_src, size_t bytes, v
     }
     if (which == AOENV_B_COUNTERS) {
         env->det.frame_counter = static_cast<const uint32_t*>(h_src)[0];
+        env->explore_counter = static_cast<const uint32_t*>(h_src)[1];
+        env->explore_seeded = false;                               // the uploaded position belongs to the seed of the next rollout
         return 0;
     }
     AO_HIP(hipMemcpy(b.ptr, h_src, bytes, hipMemcpyHostToDevice));

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -33,6 +34,10 @@ CAMERAS = {
 def _torch():
     import torch
     return torch
+
+
+# what BatchedAOEnv.rollout returns: obs [K+1, N, a, a], action [K, N, a, a], reward [K, N], strehl [K, N]
+Rollout = namedtuple("Rollout", ["obs", "action", "reward", "strehl"])
 
 
 def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
@@ -524,6 +529,7 @@ class BatchedAOEnv:
         self.env_seed_stride = int(env_seed_stride)
         self.env_index_offset = int(env_index_offset)
         self.detector_seed = 0
+        self.explore_seed = 0                                      # keys the exploration noise of rollout(); kept in get_state()
         # attributes of the reference env (MAIN/OOPAOEnv/OOPAOEnv.py:19-72)
         self.gainCL = None
         self.net_gain = 0.5
@@ -640,6 +646,7 @@ class BatchedAOEnv:
         sh.upload(L.C_WFS_UNITS, np.array([units]))
         sh.upload(L.C_RECON, self.reconstructor)
         sh.upload(L.C_RECON_FACTORS, np.concatenate([self.modal_CM.reshape(-1), self.M2C_CL.reshape(-1)]))
+        self.set_noise_filter(np.linalg.pinv(self.M2C_CL), self.M2C_CL)      # the factors of self.F (OOPAOEnv.py:383)
         self._push_wind(reset=True)
         N, A_ = self.n_envs, self.nActuator
         self._obs = torch.zeros((N, A_, A_), device=self.device, dtype=self.tdtype)
@@ -1039,6 +1046,72 @@ class BatchedAOEnv:
             C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._strehl.data_ptr()), C.c_void_p(self._stream())))
         return self._obs, self._reward, self._strehl
 
+    def set_noise_filter(self, Fr=None, Fl=None):
+        """The filter of ``rollout``'s exploration noise in factored form, ``F = Fl @ Fr`` with ``Fr`` [K, A] and ``Fl`` [A, K]
+        (``set_params`` uploads ``pinv(M2C_CL)`` and ``M2C_CL``, the factors of ``self.F``); no arguments: no filter, ``n = z``,
+        the reference's ``F = 1`` before ``set_params``.  ``self.F`` and ``sample_noise`` are not touched."""
+        sh = self._shard
+        if Fr is None or Fl is None:
+            L.check(sh.lib.aoenv_set_noise_filter(sh.h, None, 0, C.c_void_p(self._stream())))
+            return
+        Fr, Fl = np.asarray(Fr, dtype=np.float64), np.asarray(Fl, dtype=np.float64)
+        if Fr.ndim != 2 or Fr.shape[1] != self.nValidAct or Fl.shape != Fr.shape[::-1]:
+            raise ValueError(f"Fr must be [K, {self.nValidAct}] and Fl [{self.nValidAct}, K], got {Fr.shape} and {Fl.shape}")
+        fac = np.ascontiguousarray(np.concatenate([Fr.reshape(-1), Fl.reshape(-1)]))
+        L.check(sh.lib.aoenv_set_noise_filter(sh.h, fac.ctypes.data_as(C.c_void_p), int(Fr.shape[0]), C.c_void_p(self._stream())))
+
+    def rollout(self, i0: int, n_steps: int, sigma, gain=None, seed=None, sigma_env=None):
+        """An exploration episode as a replay-ready trajectory, on the device (the warm-up loop of MAIN/PO4AO/mbrl.py:64-89):
+        for the frames ``i0 .. i0 + n_steps - 1``  ``action = gain * obs + sample_noise(sigma)``, then ``step(i, action)``.
+        Returns ``Rollout(obs [K+1, N, a, a], action [K, N, a, a], reward [K, N], strehl [K, N])``, four new tensors:
+        ``obs[k], action[k], reward[k], obs[k + 1]`` is what ``replay.append`` takes; ``obs[0]`` is the current observation.
+        The noise is ``sigma * vec_to_img(F @ z)`` with ``z`` from a counter-based stream keyed by ``seed`` (default: the env's
+        ``explore_seed``, which a given seed replaces, so that a repeated call continues the stream) and indexed by the env's
+        global index (``env_index_offset`` + row) and a step counter: reproducible, independent of where an env sits in a shard,
+        part of ``get_state()``.  ``sigma_env`` [N] gives every env its own sigma (``sigma`` is then ignored); ``gain`` defaults to
+        ``gainCL`` and may be 0.  The env is left as ``n_steps`` calls of ``step`` leave it (last obs / reward / strehl, ``SR``,
+        the frame)."""
+        torch = _torch()
+        K, N, A_ = int(n_steps), self.n_envs, self.nActuator
+        if K < 0:
+            raise ValueError("n_steps must be >= 0")
+        sd = int(self.explore_seed if seed is None else seed)
+        g = float(self.gainCL if gain is None else gain)
+        sig = None
+        if sigma_env is not None:
+            if not torch.is_tensor(sigma_env):
+                sv = np.asarray(sigma_env, dtype=np.float64)
+                if not (np.isfinite(sv).all() and (sv >= 0).all()):
+                    raise ValueError("sigma_env must be finite and >= 0")
+            sig = torch.as_tensor(sigma_env).to(device=self.device, dtype=self.tdtype).contiguous()
+            if tuple(sig.shape) != (N,):
+                raise ValueError(f"sigma_env must have shape ({N},), got {tuple(sig.shape)}")
+        obs = torch.empty((K + 1, N, A_, A_), device=self.device, dtype=self.tdtype)
+        obs[0] = self._obs
+        action = torch.empty((K, N, A_, A_), device=self.device, dtype=self.tdtype)
+        reward = torch.empty((K, N), device=self.device, dtype=self.tdtype)
+        strehl = torch.empty((K, N), device=self.device, dtype=self.tdtype)
+        view = self.return_frame == "view"
+        fr = torch.empty((N, self.cam_res, self.cam_res), device=self.device, dtype=self.tdtype) \
+            if (K > 0 and self.return_frame and not view) else None
+        cfg = L.AoRollout(i0=int(i0), n_steps=K, env_index_offset=int(self.env_index_offset), reserved=0, gain=g,
+                          sigma=0.0 if sig is not None else float(sigma), d_sigma_env=None if sig is None else sig.data_ptr(),
+                          seed=sd & 0xFFFFFFFFFFFFFFFF)
+        if K > 0:                                                  # (no steps: nothing to launch, and empty tensors have no address)
+            L.check(self._shard.lib.aoenv_run_rollout(
+                self._shard.h, C.byref(cfg), C.c_void_p(obs.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(reward.data_ptr()),
+                C.c_void_p(strehl.data_ptr()), C.c_void_p(fr.data_ptr()) if fr is not None else None, C.c_void_p(self._stream())))
+        self.explore_seed = sd                                     # (after the call: a refused rollout changes nothing)
+        if K > 0:
+            if view:
+                fr = self._frame_alias()
+            # (clones: the env's own tensors are not windows into the trajectory the caller now owns)
+            self._obs, self._reward, self._strehl, self._frame = obs[K].clone(), reward[K - 1].clone(), strehl[K - 1].clone(), fr
+            self.SR.extend(strehl.clone().unbind(0))
+        if self.output == "numpy":
+            return Rollout(*(t.detach().to("cpu", dtype=torch.float64).numpy()[:, 0] for t in (obs, action, reward, strehl)))
+        return Rollout(obs, action, reward, strehl)
+
     # -- checkpoint / resume (SURVEY.md section 5: env state = screens, sub-pixel accumulators, ring RNG, dm coefs) --------
     def get_state(self) -> dict:
         """Everything the next ``step`` depends on, as host arrays: restoring it with ``set_state`` (same geometry, same
@@ -1057,6 +1130,7 @@ class BatchedAOEnv:
             "dm_prev": sh.download(L.B_DM_PREV, (self.n_envs, self.nValidAct), st),
             "signal": sh.download(L.B_SIGNAL, (self.n_envs, self.nSignal), st),
             "counters": sh.download(L.B_COUNTERS, (4,), st, dtype=np.uint32),
+            "explore_seed": int(self.explore_seed),                # the seed word 1 of the counters belongs to (rollout)
             "obs": self._obs.detach().cpu().numpy().copy(),
             "windSpeed": list(p.windSpeed), "windDirection": list(p.windDirection),
         }
@@ -1095,6 +1169,7 @@ class BatchedAOEnv:
         sh.upload_state(L.B_DM_PREV, state.get("dm_prev", state["coefs"]), st)
         sh.upload_state(L.B_SIGNAL, state["signal"], st)
         sh.upload_state(L.B_COUNTERS, state["counters"], st, dtype=np.uint32)
+        self.explore_seed = int(state.get("explore_seed", self.explore_seed))   # (a checkpoint from before rollout() has none)
         self._obs = _torch().as_tensor(state["obs"]).to(device=self.device, dtype=self.tdtype).clone()   # (never into a handed-out tensor)
 
     def _download_screens(self):

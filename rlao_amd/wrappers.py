@@ -68,6 +68,12 @@ class TorchWrapper:
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
 
+    def rollout(self, i0, n_steps, sigma, gain=None, seed=None, sigma_env=None):
+        """``BatchedAOEnv.rollout`` in this wrapper's return convention: float32 tensors."""
+        torch = _torch()
+        tr = self._env.rollout(i0, n_steps, sigma, gain=gain, seed=seed, sigma_env=sigma_env)
+        return type(tr)(*(torch.as_tensor(t).float() for t in tr))
+
 
 class TimeDelayEnv:
     """Control delay of ``delay`` frames: the env receives the action issued ``delay`` steps earlier."""
@@ -117,6 +123,11 @@ class TimeDelayEnv:
         out = self._env.step(i, self.action_buffer[0])
         del self.action_buffer[0]
         return out
+
+    def rollout(self, *args, **kw):
+        raise NotImplementedError(
+            "TimeDelayEnv cannot run rollout(): the library loop applies action k in step k, and this wrapper exists to apply it "
+            f"{self.d} step(s) later; step the wrapper frame by frame, or call rollout() on the env it wraps")
 
 
 class Box:
@@ -244,6 +255,32 @@ class HistoryEnv:
         self.action_buffer = _with_rows_cleared(self.action_buffer, rows)
         win = h.window()[sel]                                       # (advanced indexing: a copy)
         return win.cpu().numpy() if self.single else win
+
+    def rollout(self, n_steps, sigma, gain=None, seed=None, sigma_env=None):
+        """``BatchedAOEnv.rollout`` from this wrapper's frame counter on (no frame index argument, as ``step``; a run that
+        reaches ``nLoop`` is cut there and goes on at frame 0, like ``step``'s counter).  Returns the env's trajectory (a list of
+        them where the run was cut); the device history is refilled from the tail of the trajectory, so that ``obs_history`` is what
+        ``n_steps`` calls of ``step`` with those actions would have left.  Needs ``delay == 1``: the library loop applies action k
+        in step k."""
+        if self.delay != 1:
+            raise NotImplementedError(f"HistoryEnv.rollout: delay is {self.delay}, the library loop applies action k in step k (delay 1)")
+        e = self._env
+        n_loop = int(e.param.nLoop) if hasattr(e, "param") else 1 << 30
+        parts, left = [], int(n_steps)
+        while left > 0:
+            i = self.t % n_loop
+            n = min(left, n_loop - i)
+            tr = e.rollout(i, n, sigma, gain=gain, seed=seed, sigma_env=sigma_env)
+            seed = None                                             # (the next part continues the stream)
+            obs = tr.obs if len(tr.obs.shape) == 4 else tr.obs[:, None]
+            for k in range(max(1, n + 1 - self.n_history), n + 1):
+                self._push(obs[k])
+            self.t += n
+            left -= n
+            parts.append(tr)
+        if not parts:
+            return e.rollout(self.t % n_loop, 0, sigma, gain=gain, seed=seed, sigma_env=sigma_env)
+        return parts[0] if len(parts) == 1 else parts
 
     def _push(self, obs):
         torch = _torch()
