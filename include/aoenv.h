@@ -309,6 +309,51 @@ typedef struct AoRollout {
 int aoenv_run_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward,
                       void* d_strehl, void* d_frame, void* stream);
 
+/* Replaces: ConvPolicy (MAIN/PO4AO/conv_models_simple.py:56-111), the trainer's policy, evaluated inside the library:
+ *     out = net(cat([obs, past_obs, past_act], dim=1));  out = out.clamp(-1, 1);  action = vec_to_img(F @ out[valid])
+ * net = Conv2d(2H-1, n_filt, 3, padding=1), LeakyReLU, Conv2d(n_filt, n_filt, 3, padding=1), LeakyReLU, Conv2d(n_filt, 1, 3, padding=1).
+ * The weights are host float64 arrays in torch's Conv2d layout, so a state_dict of the reference trainer loads unchanged; they are
+ * copied (and, for the float32 matrix-core kernel, re-laid) before the call returns.  F = Fl @ Fr in factored form, as
+ * aoenv_set_noise_filter takes it.  The two hidden images ([n_env][n_filt][nAct^2], env dtype) are allocated here and freed when
+ * the policy is forgotten or replaced.  float32 shards with n_filt % 16 == 0 run the two wide convolutions on the matrix cores;
+ * float64 shards, any other n_filt and path = 1 take the general kernel (same sums in the same order, on the vector unit).
+ * Refused with nothing changed: n_history / n_filt / proj_rank out of range, a path other than 0 / 1, null or non-finite weights,
+ * a non-finite slope, clamp_abs <= 0 (or NaN).  The stream is waited for once. */
+typedef struct AoPolicy {
+    int32_t n_history;      /* H in [1, 32]; input channels C_in = 2H - 1 */
+    int32_t n_filt;         /* filters of the two hidden layers, in [1, 128] */
+    int32_t proj_rank;      /* K of the projection factors, 0 = no projection */
+    int32_t path;           /* 0 = default kernels, 1 = force the general kernel (parity tests) */
+    double  negative_slope; /* LeakyReLU, torch default 0.01 */
+    double  clamp_abs;      /* > 0, may be +inf */
+    const double *h_w1, *h_b1;  /* [n_filt][C_in][3][3], [n_filt]   torch Conv2d layout */
+    const double *h_w2, *h_b2;  /* [n_filt][n_filt][3][3], [n_filt] */
+    const double *h_w3, *h_b3;  /* [1][n_filt][3][3], [1] */
+    const double *h_proj;       /* as aoenv_set_noise_filter: [K*A] Fr then [A*K] Fl, or NULL */
+} AoPolicy;
+int aoenv_set_policy(AoEnv* env, const AoPolicy* cfg, void* stream);   /* NULL cfg: forget the policy */
+
+/* Replaces: policy(obs, torch.cat([past_obs, past_act], dim=1)) (MAIN/PO4AO/mbrl.py:73; ConvPolicy.forward,
+ * conv_models_simple.py:83-111).  d_obs [n_env][nAct][nAct]; d_past_obs, d_past_act [n_env][H-1][nAct][nAct], OLDEST FIRST, the
+ * order mbrl.py:80-81 rolls them in (not read when H == 1); d_action [n_env][nAct][nAct] out, zero off the valid actuators.
+ * All in the env dtype.  Channel order [obs, past_obs.., past_act..] (conv_models_simple.py:89).
+ * Refused: no policy set, a null obs / action, a null history with H > 1. */
+int aoenv_policy_forward(AoEnv* env, const void* d_obs, const void* d_past_obs, const void* d_past_act,
+                         void* d_action, void* stream);
+
+/* Replaces: the policy episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89, the branch of :72-74), on the device and recorded as
+ * aoenv_run_rollout records the warm-up episodes:
+ *     action = policy(obs, cat([past_obs, past_act])) + env.sample_noise(sigma);  step;  roll past_obs, past_act (:80-81)
+ * Buffers, cfg, noise stream, counter and refusals as aoenv_run_rollout; cfg->gain must be 0.  At sigma == 0 (the reference adds
+ * no noise after the warm-up) the action is bit for bit what aoenv_policy_forward returns for the same windows.
+ * No history ring lives in the library: at step k past channel c is trajectory slot k - (H-1) + c of d_obs / d_action when that
+ * is >= 0 and row k + c of d_past_obs / d_past_act otherwise.  On return d_past_obs / d_past_act (in/out, [n_env][H-1][nAct][nAct],
+ * oldest first, not read when H == 1) hold the windows n_steps iterations of mbrl.py:80-81 leave.  A caller that restarts some
+ * envs (aoenv_reset_envs) clears their rows itself.
+ * Three launches per step in front of the step: the two wide convolutions and the last stage. */
+int aoenv_run_policy_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward,
+                             void* d_strehl, void* d_frame, void* d_past_obs, void* d_past_act, void* stream);
+
 /* Replaces: tel.computePSF(zeroPaddingFactor) (OOPAO/Telescope.py:258-357) of the current residual phase (tel.src.phase):
  * d_psf [n_env][M][M], M = zero_padding * R (even), env dtype: the short-exposure PSF of every env.  As the reference does for even
  * image sizes (oversampling 2, :303-305), the field is transformed at N = 2 M and |fftshift(fft2(E phasor)) / N|^2 is sum-binned 2 x 2.

@@ -49,6 +49,12 @@ class AoRollout(C.Structure):
                 ("gain", C.c_double), ("sigma", C.c_double), ("d_sigma_env", C.c_void_p), ("seed", C.c_uint64)]
 
 
+class AoPolicy(C.Structure):
+    _fields_ = [("n_history", C.c_int32), ("n_filt", C.c_int32), ("proj_rank", C.c_int32), ("path", C.c_int32),
+                ("negative_slope", C.c_double), ("clamp_abs", C.c_double)] + [
+                    (n, C.c_void_p) for n in ("h_w1", "h_b1", "h_w2", "h_b2", "h_w3", "h_b3", "h_proj")]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "aoenv_last_error": (C.c_char_p, []),
@@ -76,6 +82,10 @@ EXPORTS = {
     "aoenv_set_noise_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_run_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "aoenv_set_policy": (C.c_int, [C.c_void_p, C.POINTER(AoPolicy), C.c_void_p]),
+    "aoenv_policy_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_run_policy_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_compute_psf": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),

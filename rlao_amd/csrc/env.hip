@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "detector.hpp"
+#include "policy.hpp"
 #include "sh_device.hpp"
 
 namespace ao {
@@ -172,6 +173,15 @@ struct AoEnv {
     uint32_t explore_counter = 0;           // word 1 of AOENV_B_COUNTERS
     uint64_t explore_seed = 0;
     bool explore_seeded = false;            // false: the counter (0, or an uploaded checkpoint's) belongs to the next call's seed
+    // the policy (aoenv_set_policy): weights in the env dtype (torch layout), the two wide layers re-laid for the MFMA kernel,
+    // the projection factors, the two hidden images [E][n_filt][nAct^2]
+    struct Policy {
+        bool set = false, mfma = false;
+        int H = 0, F = 0, Kp = 0;
+        double slope = 0, clamp_abs = 0, b3 = 0;
+        void *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *wt1 = nullptr, *wt2 = nullptr;
+        void *proj_fr = nullptr, *proj_fl_t = nullptr, *hid1 = nullptr, *hid2 = nullptr;
+    } policy;
     std::vector<void*> allocs;
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool use_fast_wfs = true;               // aoenv_set_option(AOENV_OPT_FAST_WFS)
@@ -1953,37 +1963,248 @@ static int run_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_
 }
 }  // extern "C++"
 
+// what the two recorded rollouts (aoenv_run_rollout, aoenv_run_policy_rollout) refuse alike
+static int rollout_check(AoEnv* env, const AoRollout* cfg, const void* d_obs, const void* d_action, const char* who) {
+    if (!cfg || !d_obs || !d_action) return fail("%s: null cfg / obs / action", who);
+    if (cfg->i0 < 0 || cfg->n_steps < 0 || (int64_t)cfg->i0 + cfg->n_steps > env->c.n_loop)
+        return fail("frames [%d, %lld) outside [0, n_loop=%d)", cfg->i0, (long long)cfg->i0 + cfg->n_steps, env->c.n_loop);
+    if (!(cfg->sigma >= 0) || !std::isfinite(cfg->sigma)) return fail("%s: sigma must be finite and >= 0", who);
+    if (!(cfg->gain >= 0) || !std::isfinite(cfg->gain)) return fail("%s: gain must be finite and >= 0", who);
+    AO_TRY(require_step_constants(env, true));
+    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    return 0;
+}
+
+// the inverse of AOENV_C_ACT_IDX on the device
+static int ensure_act_slot(AoEnv* env, hipStream_t st) {
+    if (!env->act_slot_dirty) return 0;
+    const size_t img = (size_t)env->nAct * env->nAct;
+    std::vector<int> slot(img, -1);
+    for (int i = 0; i < env->A; ++i) slot[env->h_act_idx[i]] = i;
+    if (!env->act_slot) AO_TRY(dmalloc(env, (void**)&env->act_slot, img * sizeof(int), false));
+    AO_HIP(hipStreamSynchronize(st));
+    AO_HIP(hipMemcpy(env->act_slot, slot.data(), img * sizeof(int), hipMemcpyHostToDevice));
+    env->act_slot_dirty = false;
+    return 0;
+}
+
+// the tables a rollout needs, and the position of the exploration stream: it goes on from call to call, only another seed starts
+// it again.  Returns the counter of the call's first step and leaves counter + n_steps behind.
+static int rollout_begin(AoEnv* env, const AoRollout* cfg, hipStream_t st, uint32_t* counter) {
+    AO_TRY(ensure_act_slot(env, st));
+    if (!env->rollout_scratch) AO_TRY(dmalloc(env, &env->rollout_scratch, (size_t)2 * env->E * env->esz));
+    *counter = (env->explore_seeded && env->explore_seed != cfg->seed) ? 0 : env->explore_counter;
+    env->explore_seed = cfg->seed;
+    env->explore_seeded = true;
+    env->explore_counter = *counter + (uint32_t)cfg->n_steps;
+    return 0;
+}
+
 int aoenv_run_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl, void* d_frame,
                       void* stream) {
     AO_CHECK_ENV(env);
-    if (!cfg || !d_obs || !d_action) return fail("aoenv_run_rollout: null cfg / obs / action");
-    if (cfg->i0 < 0 || cfg->n_steps < 0 || (int64_t)cfg->i0 + cfg->n_steps > env->c.n_loop)
-        return fail("frames [%d, %lld) outside [0, n_loop=%d)", cfg->i0, (long long)cfg->i0 + cfg->n_steps, env->c.n_loop);
-    if (!(cfg->sigma >= 0) || !std::isfinite(cfg->sigma)) return fail("aoenv_run_rollout: sigma must be finite and >= 0");
-    if (!(cfg->gain >= 0) || !std::isfinite(cfg->gain)) return fail("aoenv_run_rollout: gain must be finite and >= 0");
-    AO_TRY(require_step_constants(env, true));
-    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    AO_TRY(rollout_check(env, cfg, d_obs, d_action, "aoenv_run_rollout"));
     if (rollout_action_lds(env->A, env->noise_K, env->esz) > kRolloutLdsMax)
         return fail("aoenv_run_rollout: %d actuators and filter rank %d need %zu bytes of LDS, a workgroup has %zu", env->A, env->noise_K,
                     rollout_action_lds(env->A, env->noise_K, env->esz), kRolloutLdsMax);
     if (cfg->n_steps == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (env->act_slot_dirty) {
-        const size_t img = (size_t)env->nAct * env->nAct;
-        std::vector<int> slot(img, -1);
-        for (int i = 0; i < env->A; ++i) slot[env->h_act_idx[i]] = i;
-        if (!env->act_slot) AO_TRY(dmalloc(env, (void**)&env->act_slot, img * sizeof(int), false));
-        AO_HIP(hipStreamSynchronize(st));
-        AO_HIP(hipMemcpy(env->act_slot, slot.data(), img * sizeof(int), hipMemcpyHostToDevice));
-        env->act_slot_dirty = false;
-    }
-    if (!env->rollout_scratch) AO_TRY(dmalloc(env, &env->rollout_scratch, (size_t)2 * env->E * env->esz));
-    // the stream position goes on from call to call; only another seed starts it again
-    const uint32_t counter = (env->explore_seeded && env->explore_seed != cfg->seed) ? 0 : env->explore_counter;
-    env->explore_seed = cfg->seed;
-    env->explore_seeded = true;
-    env->explore_counter = counter + (uint32_t)cfg->n_steps;
+    uint32_t counter = 0;
+    AO_TRY(rollout_begin(env, cfg, st, &counter));
     return AO_DISPATCH(env, run_rollout_t, env, cfg, d_obs, d_action, d_reward, d_strehl, d_frame, counter, st);
+}
+
+// ---- the policy (policy.hpp) ---------------------------------------------------------------------------------------------------
+static void dfree(AoEnv* env, void* p) {
+    if (!p) return;
+    env->allocs.erase(std::remove(env->allocs.begin(), env->allocs.end(), p), env->allocs.end());
+    (void)hipFree(p);                                              // (waits for the device)
+}
+static void policy_release(AoEnv* env, AoEnv::Policy& p) {
+    for (void* q : {p.w1, p.b1, p.w2, p.b2, p.w3, p.wt1, p.wt2, p.proj_fr, p.proj_fl_t, p.hid1, p.hid2}) dfree(env, q);
+    p = AoEnv::Policy{};
+}
+
+int aoenv_set_policy(AoEnv* env, const AoPolicy* cfg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!cfg) {
+        AO_HIP(hipStreamSynchronize(st));
+        policy_release(env, env->policy);
+        return 0;
+    }
+    const int H = cfg->n_history, F = cfg->n_filt, Kp = cfg->proj_rank, A = env->A;
+    if (H < 1 || H > kPolicyMaxHistory) return fail("aoenv_set_policy: n_history %d outside [1, %d]", H, kPolicyMaxHistory);
+    if (F < 1 || F > kPolicyMaxFilt) return fail("aoenv_set_policy: n_filt %d outside [1, %d]", F, kPolicyMaxFilt);
+    if (Kp < 0 || Kp > A) return fail("aoenv_set_policy: proj_rank %d outside [0, A=%d]", Kp, A);
+    if (cfg->path != 0 && cfg->path != 1) return fail("aoenv_set_policy: path %d is neither 0 nor 1", cfg->path);
+    if (!std::isfinite(cfg->negative_slope)) return fail("aoenv_set_policy: negative_slope is not finite");
+    if (!(cfg->clamp_abs > 0)) return fail("aoenv_set_policy: clamp_abs must be > 0");
+    if (!cfg->h_w1 || !cfg->h_b1 || !cfg->h_w2 || !cfg->h_b2 || !cfg->h_w3 || !cfg->h_b3 || (Kp > 0 && !cfg->h_proj))
+        return fail("aoenv_set_policy: null weights");
+    const int C1 = 2 * H - 1;
+    const size_t n1 = (size_t)F * C1 * 9, n2 = (size_t)F * F * 9, n3 = (size_t)F * 9, np = (size_t)Kp * A;
+    const struct { const double* p; size_t n; const char* name; } arrays[] = {
+        {cfg->h_w1, n1, "w1"}, {cfg->h_b1, (size_t)F, "b1"}, {cfg->h_w2, n2, "w2"}, {cfg->h_b2, (size_t)F, "b2"},
+        {cfg->h_w3, n3, "w3"}, {cfg->h_b3, 1, "b3"}, {cfg->h_proj, 2 * np, "proj"}};
+    for (const auto& a : arrays)
+        for (size_t i = 0; i < a.n; ++i)
+            if (!std::isfinite(a.p[i])) return fail("aoenv_set_policy: %s[%zu] is not finite", a.name, i);
+    AO_HIP(hipStreamSynchronize(st));                              // an evaluation in flight reads the old policy in place
+    AoEnv::Policy p;
+    p.H = H; p.F = F; p.Kp = Kp;
+    p.slope = cfg->negative_slope; p.clamp_abs = cfg->clamp_abs; p.b3 = cfg->h_b3[0];
+    p.mfma = env->esz == 4 && cfg->path == 0 && F % 16 == 0 && policy_mfma_fits(env->nAct, C1) && policy_mfma_fits(env->nAct, F);
+    const size_t z = env->esz, hid = (size_t)env->E * F * env->nAct * env->nAct * z;
+    auto build = [&]() -> int {
+        AO_TRY(dmalloc(env, &p.w1, n1 * z, false)); AO_TRY(upload_real(env, p.w1, cfg->h_w1, n1));
+        AO_TRY(dmalloc(env, &p.b1, F * z, false));  AO_TRY(upload_real(env, p.b1, cfg->h_b1, F));
+        AO_TRY(dmalloc(env, &p.w2, n2 * z, false)); AO_TRY(upload_real(env, p.w2, cfg->h_w2, n2));
+        AO_TRY(dmalloc(env, &p.b2, F * z, false));  AO_TRY(upload_real(env, p.b2, cfg->h_b2, F));
+        AO_TRY(dmalloc(env, &p.w3, n3 * z, false)); AO_TRY(upload_real(env, p.w3, cfg->h_w3, n3));
+        if (p.mfma) {
+            std::vector<float> t;
+            policy_relayout(cfg->h_w1, F, C1, t);
+            AO_TRY(dmalloc(env, &p.wt1, t.size() * 4, false));
+            AO_HIP(hipMemcpy(p.wt1, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+            policy_relayout(cfg->h_w2, F, F, t);
+            AO_TRY(dmalloc(env, &p.wt2, t.size() * 4, false));
+            AO_HIP(hipMemcpy(p.wt2, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (Kp > 0) {
+            std::vector<double> t(np);                             // Fl [A][K] -> [K][A], as aoenv_set_noise_filter
+            const double* fl = cfg->h_proj + np;
+            for (int a = 0; a < A; ++a)
+                for (int k = 0; k < Kp; ++k) t[(size_t)k * A + a] = fl[(size_t)a * Kp + k];
+            AO_TRY(dmalloc(env, &p.proj_fr, np * z, false));   AO_TRY(upload_real(env, p.proj_fr, cfg->h_proj, np));
+            AO_TRY(dmalloc(env, &p.proj_fl_t, np * z, false)); AO_TRY(upload_real(env, p.proj_fl_t, t.data(), np));
+        }
+        AO_TRY(dmalloc(env, &p.hid1, hid, false));
+        AO_TRY(dmalloc(env, &p.hid2, hid, false));
+        return 0;
+    };
+    if (int rc = build()) {                                        // (out of memory: the policy in use stays)
+        policy_release(env, p);
+        return rc;
+    }
+    p.set = true;
+    policy_release(env, env->policy);
+    env->policy = p;
+    return 0;
+}
+
+extern "C++" {
+// one evaluation: two wide convolutions and the last stage; `in` names the first layer's channels, `aa` carries the noise
+template <typename T>
+static int policy_eval_t(AoEnv* env, ConvIn<T> in, PolicyActionArgs<T> aa, hipStream_t st) {
+    const AoEnv::Policy& p = env->policy;
+    const int F = p.F, E = env->E, nAct = env->nAct, img = nAct * nAct;
+    T *h1 = env->as<T>(p.hid1), *h2 = env->as<T>(p.hid2);
+    in.plain = nullptr; in.H = p.H; in.C = 2 * p.H - 1; in.E = E; in.img = img;
+    ConvIn<T> in2{};
+    in2.plain = h1; in2.C = F; in2.E = E; in2.img = img;
+    bool done = false;
+    if constexpr (sizeof(T) == 4) {
+        if (p.mfma) {
+            AO_TRY(launch_policy_conv_mfma(in, env->as<float>(p.wt1), env->as<float>(p.b1), h1, nAct, F, (float)p.slope, E, st));
+            AO_TRY(launch_policy_conv_mfma(in2, env->as<float>(p.wt2), env->as<float>(p.b2), h2, nAct, F, (float)p.slope, E, st));
+            done = true;
+        }
+    }
+    if (!done) {
+        AO_TRY(launch_policy_conv_general<T>(in, env->as<T>(p.w1), env->as<T>(p.b1), h1, nAct, F, (T)p.slope, E, st));
+        AO_TRY(launch_policy_conv_general<T>(in2, env->as<T>(p.w2), env->as<T>(p.b2), h2, nAct, F, (T)p.slope, E, st));
+    }
+    aa.hidden = h2;
+    aa.w3 = env->as<T>(p.w3);
+    aa.b3 = (T)p.b3;
+    aa.clamp_abs = (T)p.clamp_abs;
+    aa.proj_fr = p.Kp ? env->as<T>(p.proj_fr) : nullptr;
+    aa.proj_fl_t = p.Kp ? env->as<T>(p.proj_fl_t) : nullptr;
+    aa.act_slot = env->act_slot;
+    aa.n_act = nAct; aa.n_valid_act = env->A; aa.n_filt = F; aa.proj_rank = p.Kp;
+    return launch_policy_action<T>(aa, E, st);
+}
+
+template <typename T>
+static int policy_forward_t(AoEnv* env, const void* d_obs, const void* d_past_obs, const void* d_past_act, void* d_action, hipStream_t st) {
+    ConvIn<T> in{};
+    in.obs = static_cast<const T*>(d_obs);
+    in.past_obs = static_cast<const T*>(d_past_obs);
+    in.past_act = static_cast<const T*>(d_past_act);
+    in.k = 0;                                                      // every past channel from the caller's windows
+    PolicyActionArgs<T> aa{};
+    aa.action = static_cast<T*>(d_action);                         // sigma = 0: no noise
+    return policy_eval_t<T>(env, in, aa, st);
+}
+
+template <typename T>
+static int run_policy_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl,
+                                void* d_frame, void* d_past_obs, void* d_past_act, uint32_t counter, hipStream_t st) {
+    const size_t img = (size_t)env->nAct * env->nAct, E = env->E;
+    T* scratch = env->as<T>(env->rollout_scratch);
+    ConvIn<T> in{};
+    in.obs = static_cast<const T*>(d_obs);
+    in.act = static_cast<const T*>(d_action);
+    in.past_obs = static_cast<const T*>(d_past_obs);
+    in.past_act = static_cast<const T*>(d_past_act);
+    PolicyActionArgs<T> aa{};
+    aa.fr = env->noise_K ? env->as<T>(env->noise_fr) : nullptr;
+    aa.fl_t = env->noise_K ? env->as<T>(env->noise_fl_t) : nullptr;
+    aa.sigma_env = static_cast<const T*>(cfg->d_sigma_env);
+    aa.sigma = (T)cfg->sigma;
+    aa.n_filter = env->noise_K;
+    aa.seed_lo = (uint32_t)(cfg->seed & 0xffffffffu);
+    aa.seed_hi = (uint32_t)(cfg->seed >> 32);
+    aa.env_offset = (uint32_t)cfg->env_index_offset;
+    for (int k = 0; k < cfg->n_steps; ++k) {
+        const bool last = k == cfg->n_steps - 1;
+        in.k = k;
+        aa.action = static_cast<T*>(d_action) + (size_t)k * E * img;
+        aa.counter = counter + (uint32_t)k;
+        AO_TRY(policy_eval_t<T>(env, in, aa, st));
+        AO_TRY(step_t<T>(env, cfg->i0 + k, aa.action, static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
+                         d_reward ? static_cast<T*>(d_reward) + (size_t)k * E : scratch,
+                         d_strehl ? static_cast<T*>(d_strehl) + (size_t)k * E : scratch + E, 0.0, last, st));
+    }
+    // the windows n_steps iterations of mbrl.py:80-81 leave (the trajectory is complete: stream order)
+    AO_TRY(launch_policy_roll<T>(static_cast<T*>(d_past_obs), static_cast<const T*>(d_obs), cfg->n_steps, env->policy.H, env->E, (int)img, st));
+    return launch_policy_roll<T>(static_cast<T*>(d_past_act), static_cast<const T*>(d_action), cfg->n_steps, env->policy.H, env->E, (int)img, st);
+}
+}  // extern "C++"
+
+static int policy_ready(AoEnv* env, const char* who) {
+    if (!env->policy.set) return fail("%s: no policy has been set (aoenv_set_policy)", who);
+    if (!env->have[AOENV_C_ACT_IDX]) return fail("constant table %d has not been uploaded", (int)AOENV_C_ACT_IDX);
+    if (policy_action_lds(env->A, env->policy.Kp, env->noise_K, env->esz) > kPolicyLdsMax)
+        return fail("%s: %d actuators and ranks %d / %d need %zu bytes of LDS, a workgroup has %zu", who, env->A, env->policy.Kp,
+                    env->noise_K, policy_action_lds(env->A, env->policy.Kp, env->noise_K, env->esz), kPolicyLdsMax);
+    return 0;
+}
+
+int aoenv_policy_forward(AoEnv* env, const void* d_obs, const void* d_past_obs, const void* d_past_act, void* d_action, void* stream) {
+    AO_CHECK_ENV(env);
+    AO_TRY(policy_ready(env, "aoenv_policy_forward"));
+    if (!d_obs || !d_action) return fail("aoenv_policy_forward: null obs / action");
+    if (env->policy.H > 1 && (!d_past_obs || !d_past_act)) return fail("aoenv_policy_forward: null history with n_history = %d", env->policy.H);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AO_TRY(ensure_act_slot(env, st));
+    return AO_DISPATCH(env, policy_forward_t, env, d_obs, d_past_obs, d_past_act, d_action, st);
+}
+
+int aoenv_run_policy_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl,
+                             void* d_frame, void* d_past_obs, void* d_past_act, void* stream) {
+    AO_CHECK_ENV(env);
+    AO_TRY(policy_ready(env, "aoenv_run_policy_rollout"));
+    AO_TRY(rollout_check(env, cfg, d_obs, d_action, "aoenv_run_policy_rollout"));
+    if (cfg->gain != 0) return fail("aoenv_run_policy_rollout: gain must be 0 (a residual controller is out of scope), got %g", cfg->gain);
+    if (env->policy.H > 1 && (!d_past_obs || !d_past_act))
+        return fail("aoenv_run_policy_rollout: null history with n_history = %d", env->policy.H);
+    if (cfg->n_steps == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint32_t counter = 0;
+    AO_TRY(rollout_begin(env, cfg, st, &counter));
+    return AO_DISPATCH(env, run_policy_rollout_t, env, cfg, d_obs, d_action, d_reward, d_strehl, d_frame, d_past_obs, d_past_act, counter, st);
 }
 
 extern "C++" {

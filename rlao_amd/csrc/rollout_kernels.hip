@@ -12,9 +12,10 @@
 //      Both sums have one order whatever n_env, e or the number of idle lanes (an idle lane adds an exact zero).
 //   4. the image: every pixel gain * obs (one multiply in the env dtype, not contracted), plus sigma_e n[slot] at the valid actuators
 //      (slot = the inverse of AOENV_C_ACT_IDX, -1 elsewhere): pixels are read and written contiguously, once.
+// Steps 1 - 3 are explore_draw_lds and apply_factored_lds of noise_device.hpp, which the policy rollout's last stage shares.
 // The factors are shared by all envs and come from L2 (K A elements each: 2 x 64 KB at the 8 m geometry in float32).
 #include "common.hpp"
-#include "explore.hpp"
+#include "noise_device.hpp"
 
 namespace ao {
 
@@ -27,32 +28,8 @@ __global__ __launch_bounds__(256) void k_rollout_action(RolloutActionArgs<T> a) 
     T* zs = reinterpret_cast<T*>(rollout_smem);                    // [A rounded up to 4]: z, then n
     T* ts = zs + ((A + 3) & ~3);                                   // [K]
     const int e = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & (kWave - 1), w = tid / kWave;
-
-    for (int q = tid; 4 * q < A; q += 256) {
-        float z4[4];
-        explore_normals(a.seed_lo, a.seed_hi, (uint32_t)q, a.env_offset + (uint32_t)e, a.counter, z4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) zs[4 * q + j] = (T)z4[j];      // (the tail of the last quad lands in the padding)
-    }
-    __syncthreads();
-    if (K > 0) {
-        for (int k = w; k < K; k += 256 / kWave) {
-            const T* row = a.fr + (size_t)k * A;
-            T acc = 0;
-            for (int i = lane; i < A; i += kWave) acc += row[i] * zs[i];
-#pragma unroll
-            for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
-            if (lane == 0) ts[k] = acc;
-        }
-        __syncthreads();
-        for (int i = tid; i < A; i += 256) {                       // (z[i] has no reader left: step 2 ended at the barrier)
-            T acc = 0;
-            for (int k = 0; k < K; ++k) acc += a.fl_t[(size_t)k * A + i] * ts[k];
-            zs[i] = acc;
-        }
-        __syncthreads();
-    }
+    explore_draw_lds<T, 256>(zs, A, a.seed_lo, a.seed_hi, a.env_offset + (uint32_t)e, a.counter);
+    if (K > 0) apply_factored_lds<T, 256>(a.fr, a.fl_t, zs, ts, A, K);
     const int img = a.n_act * a.n_act;
     const T g = a.gain, sigma = a.sigma_env ? a.sigma_env[e] : a.sigma;
     const T* ob = a.obs + (size_t)e * img;

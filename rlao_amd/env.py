@@ -40,6 +40,41 @@ def _torch():
 Rollout = namedtuple("Rollout", ["obs", "action", "reward", "strehl"])
 
 
+def policy_arrays(policy) -> dict:
+    """The weights of a PO4AO ``ConvPolicy`` (MAIN/PO4AO/conv_models_simple.py:56-111) as host float64 arrays in torch's Conv2d
+    layout: ``w1 [F, 2H-1, 3, 3], b1 [F], w2 [F, F, 3, 3], b2 [F], w3 [1, F, 3, 3], b3 [1]`` plus ``negative_slope``, ``n_history``
+    and ``n_filt``.  ``policy``: a module with the reference's ``.net``; an ``nn.Sequential`` of that shape (Conv2d at positions
+    0, 2, 4, the slope read from the LeakyReLU at position 1); or a dict, either of arrays ``w1 .. b3`` (optionally
+    ``negative_slope``, default torch's 0.01) or a ``state_dict`` with the keys ``[net.]0.weight .. [net.]4.bias``."""
+    def arr(t):
+        t = t.detach().cpu().numpy() if hasattr(t, "detach") else t
+        return np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+
+    slope = 0.01
+    if isinstance(policy, dict):
+        if "w1" in policy:
+            raw = [policy[k] for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+        else:
+            pre = "net." if "net.0.weight" in policy else ""
+            raw = [policy[f"{pre}{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias")]
+        slope = float(policy.get("negative_slope", slope))
+    else:
+        net = getattr(policy, "net", policy)
+        if len(net) != 5:
+            raise ValueError(f"the policy network must be Conv2d, LeakyReLU, Conv2d, LeakyReLU, Conv2d; got {len(net)} modules")
+        raw = [t for i in (0, 2, 4) for t in (net[i].weight, net[i].bias)]
+        slope = float(getattr(net[1], "negative_slope", slope))
+        if float(getattr(net[3], "negative_slope", slope)) != slope:
+            raise ValueError("the two LeakyReLU slopes differ")
+    w1, b1, w2, b2, w3, b3 = (arr(t) for t in raw)
+    F = w1.shape[0]
+    if w1.ndim != 4 or w1.shape[2:] != (3, 3) or w1.shape[1] % 2 != 1:
+        raise ValueError(f"w1 must be [F, 2H-1, 3, 3], got {w1.shape}")
+    if w2.shape != (F, F, 3, 3) or w3.shape != (1, F, 3, 3) or b1.shape != (F,) or b2.shape != (F,) or b3.shape != (1,):
+        raise ValueError(f"layer shapes do not chain: {w1.shape} {b1.shape} {w2.shape} {b2.shape} {w3.shape} {b3.shape}")
+    return dict(w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, negative_slope=slope, n_history=(w1.shape[1] + 1) // 2, n_filt=int(F))
+
+
 def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
     """The envs a partial reset names, as a sorted unique ``int32`` array.  ``env_ids``: a 1-D integer sequence / array / tensor
     (each id in ``[0, n_envs)``, none twice, any order) or a boolean mask of length ``n_envs``.  Raises ``ValueError`` for an input
@@ -530,6 +565,7 @@ class BatchedAOEnv:
         self.env_index_offset = int(env_index_offset)
         self.detector_seed = 0
         self.explore_seed = 0                                      # keys the exploration noise of rollout(); kept in get_state()
+        self.policy_n_history = None                               # H of the policy set_policy() uploaded, None: no policy
         # attributes of the reference env (MAIN/OOPAOEnv/OOPAOEnv.py:19-72)
         self.gainCL = None
         self.net_gain = 0.5
@@ -1071,12 +1107,17 @@ class BatchedAOEnv:
         part of ``get_state()``.  ``sigma_env`` [N] gives every env its own sigma (``sigma`` is then ignored); ``gain`` defaults to
         ``gainCL`` and may be 0.  The env is left as ``n_steps`` calls of ``step`` leave it (last obs / reward / strehl, ``SR``,
         the frame)."""
+        g = float(self.gainCL if gain is None else gain)
+        return self._recorded_rollout(self._shard.lib.aoenv_run_rollout, i0, n_steps, sigma, g, seed, sigma_env, ())
+
+    def _recorded_rollout(self, entry, i0, n_steps, sigma, g, seed, sigma_env, extra):
+        """The buffers, the call and the env-state bookkeeping ``rollout`` and ``policy_rollout`` share.  ``entry``: the library's
+        loop; ``extra``: the device pointers it takes between the frame and the stream."""
         torch = _torch()
         K, N, A_ = int(n_steps), self.n_envs, self.nActuator
         if K < 0:
             raise ValueError("n_steps must be >= 0")
         sd = int(self.explore_seed if seed is None else seed)
-        g = float(self.gainCL if gain is None else gain)
         sig = None
         if sigma_env is not None:
             if not torch.is_tensor(sigma_env):
@@ -1098,9 +1139,9 @@ class BatchedAOEnv:
                           sigma=0.0 if sig is not None else float(sigma), d_sigma_env=None if sig is None else sig.data_ptr(),
                           seed=sd & 0xFFFFFFFFFFFFFFFF)
         if K > 0:                                                  # (no steps: nothing to launch, and empty tensors have no address)
-            L.check(self._shard.lib.aoenv_run_rollout(
+            L.check(entry(
                 self._shard.h, C.byref(cfg), C.c_void_p(obs.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(reward.data_ptr()),
-                C.c_void_p(strehl.data_ptr()), C.c_void_p(fr.data_ptr()) if fr is not None else None, C.c_void_p(self._stream())))
+                C.c_void_p(strehl.data_ptr()), C.c_void_p(fr.data_ptr()) if fr is not None else None, *extra, C.c_void_p(self._stream())))
         self.explore_seed = sd                                     # (after the call: a refused rollout changes nothing)
         if K > 0:
             if view:
@@ -1111,6 +1152,79 @@ class BatchedAOEnv:
         if self.output == "numpy":
             return Rollout(*(t.detach().to("cpu", dtype=torch.float64).numpy()[:, 0] for t in (obs, action, reward, strehl)))
         return Rollout(obs, action, reward, strehl)
+
+    # -- the trainer's policy inside the library (MAIN/PO4AO/conv_models_simple.py:56-111, mbrl.py:72-74) ----------------------
+    def set_policy(self, policy, F=True, clamp=1.0, path=0):
+        """Upload a PO4AO ``ConvPolicy`` for ``policy_action`` / ``policy_rollout``; ``None`` forgets it (and frees its hidden
+        images).  ``policy``: what ``policy_arrays`` takes (a module with ``.net``, an ``nn.Sequential``, a dict).  ``F``: the
+        projection on the controlled modes: ``True`` the factors ``pinv(M2C_CL), M2C_CL`` of ``self.F`` (after ``set_params``),
+        ``None`` no projection, a pair ``(Fr [K, A], Fl [A, K])`` custom factors.  ``clamp``: the reference clamps to [-1, 1].
+        ``path=1`` forces the general kernel (parity tests)."""
+        sh = self._shard
+        if policy is None:
+            L.check(sh.lib.aoenv_set_policy(sh.h, None, C.c_void_p(self._stream())))
+            self.policy_n_history = None
+            return
+        w = policy_arrays(policy)
+        if F is True:
+            F = (np.linalg.pinv(self.M2C_CL), self.M2C_CL)
+        proj, rank = None, 0
+        if F is not None and F is not False:
+            Fr, Fl = (np.asarray(x, dtype=np.float64) for x in F)
+            if Fr.ndim != 2 or Fr.shape[1] != self.nValidAct or Fl.shape != Fr.shape[::-1]:
+                raise ValueError(f"Fr must be [K, {self.nValidAct}] and Fl [{self.nValidAct}, K], got {Fr.shape} and {Fl.shape}")
+            proj, rank = np.ascontiguousarray(np.concatenate([Fr.reshape(-1), Fl.reshape(-1)])), int(Fr.shape[0])
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        cfg = L.AoPolicy(n_history=w["n_history"], n_filt=w["n_filt"], proj_rank=rank, path=int(path),
+                         negative_slope=w["negative_slope"], clamp_abs=float(clamp), h_w1=ptr(w["w1"]), h_b1=ptr(w["b1"]),
+                         h_w2=ptr(w["w2"]), h_b2=ptr(w["b2"]), h_w3=ptr(w["w3"]), h_b3=ptr(w["b3"]),
+                         h_proj=None if proj is None else ptr(proj))
+        L.check(sh.lib.aoenv_set_policy(sh.h, C.byref(cfg), C.c_void_p(self._stream())))
+        self.policy_n_history = int(w["n_history"])
+
+    def _history_tensor(self, t, name, copy):
+        torch = _torch()
+        N, A_, H = self.n_envs, self.nActuator, self.policy_n_history
+        if t is None:
+            return torch.zeros((N, H - 1, A_, A_), device=self.device, dtype=self.tdtype)
+        t = torch.as_tensor(t)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        if tuple(t.shape) != (N, H - 1, A_, A_):
+            raise ValueError(f"{name} must have shape ({N}, {H - 1}, {A_}, {A_}), got {tuple(t.shape)}")
+        return t.to(device=self.device, dtype=self.tdtype, copy=copy).contiguous()      # (copy: the rollout writes into it)
+
+    def _require_policy(self):
+        if self.policy_n_history is None:
+            L.check(self._shard.lib.aoenv_policy_forward(self._shard.h, None, None, None, None, None))   # the library's own refusal
+
+    def policy_action(self, obs, past_obs=None, past_act=None):
+        """``policy(obs, cat([past_obs, past_act], dim=1))`` (mbrl.py:73) by the library's kernels: ``obs`` [N, a, a], ``past_obs`` and
+        ``past_act`` [N, H-1, a, a] OLDEST FIRST, as mbrl.py:80-81 rolls them (``None``: zeros).  Returns the action images
+        [N, a, a], a new tensor."""
+        torch = _torch()
+        self._require_policy()
+        o = self._action_tensor(obs)
+        po, pa = self._history_tensor(past_obs, "past_obs", False), self._history_tensor(past_act, "past_act", False)
+        act = torch.empty_like(o)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        L.check(self._shard.lib.aoenv_policy_forward(self._shard.h, p(o), p(po), p(pa), p(act), C.c_void_p(self._stream())))
+        return self._out(act)
+
+    def policy_rollout(self, i0: int, n_steps: int, sigma=0.0, past=None, seed=None, sigma_env=None):
+        """A policy episode as a replay-ready trajectory, on the device (the loop of MAIN/PO4AO/mbrl.py:64-89 after the warm-up):
+        for the frames ``i0 .. i0 + n_steps - 1``  ``action = policy(obs, cat([past_obs, past_act])) + sample_noise(sigma)``, then
+        ``step(i, action)`` and the roll of the two windows (:80-81).  Returns ``(Rollout, (past_obs, past_act))``: the trajectory
+        as ``rollout`` returns it, and the windows [N, H-1, a, a] (oldest first, new tensors) to pass as ``past`` to the next call;
+        ``past=None`` starts from zeros (:60-62).  ``sigma``, ``seed``, ``sigma_env`` and the env-state bookkeeping as ``rollout``;
+        at ``sigma == 0`` (the reference's behaviour) every action is bit for bit ``policy_action`` of its windows."""
+        self._require_policy()
+        po, pa = (self._history_tensor(None if past is None else past[j], name, True) for j, name in ((0, "past[0]"), (1, "past[1]")))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        tr = self._recorded_rollout(self._shard.lib.aoenv_run_policy_rollout, i0, n_steps, sigma, 0.0, seed, sigma_env, (p(po), p(pa)))
+        if self.output == "numpy":
+            po, pa = (t.detach().to("cpu", dtype=_torch().float64).numpy()[0] for t in (po, pa))
+        return tr, (po, pa)
 
     # -- checkpoint / resume (SURVEY.md section 5: env state = screens, sub-pixel accumulators, ring RNG, dm coefs) --------
     def get_state(self) -> dict:

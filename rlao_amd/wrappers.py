@@ -74,6 +74,20 @@ class TorchWrapper:
         tr = self._env.rollout(i0, n_steps, sigma, gain=gain, seed=seed, sigma_env=sigma_env)
         return type(tr)(*(torch.as_tensor(t).float() for t in tr))
 
+    def set_policy(self, policy, F=True, clamp=1.0, path=0):
+        return self._env.set_policy(policy, F=F, clamp=clamp, path=path)
+
+    def policy_action(self, obs, past_obs=None, past_act=None):
+        """``BatchedAOEnv.policy_action`` in this wrapper's return convention: a float32 tensor."""
+        return _torch().as_tensor(self._env.policy_action(obs, past_obs, past_act)).float()
+
+    def policy_rollout(self, i0, n_steps, sigma=0.0, past=None, seed=None, sigma_env=None):
+        """``BatchedAOEnv.policy_rollout`` in this wrapper's return convention: float32 tensors (the windows too: on a float64
+        shard pass the env's own windows to the next call where the last bits matter)."""
+        torch = _torch()
+        tr, past = self._env.policy_rollout(i0, n_steps, sigma=sigma, past=past, seed=seed, sigma_env=sigma_env)
+        return type(tr)(*(torch.as_tensor(t).float() for t in tr)), tuple(torch.as_tensor(t).float() for t in past)
+
 
 class TimeDelayEnv:
     """Control delay of ``delay`` frames: the env receives the action issued ``delay`` steps earlier."""
@@ -128,6 +142,11 @@ class TimeDelayEnv:
         raise NotImplementedError(
             "TimeDelayEnv cannot run rollout(): the library loop applies action k in step k, and this wrapper exists to apply it "
             f"{self.d} step(s) later; step the wrapper frame by frame, or call rollout() on the env it wraps")
+
+    def policy_rollout(self, *args, **kw):
+        raise NotImplementedError(
+            "TimeDelayEnv cannot run policy_rollout(): the library loop applies action k in step k, and this wrapper exists to apply it "
+            f"{self.d} step(s) later; step the wrapper frame by frame, or call policy_rollout() on the env it wraps")
 
 
 class Box:
