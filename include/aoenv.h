@@ -122,6 +122,9 @@ enum AoBuf {
                                 dm.coefs = dm_prev * leak + action and copies it back to dm_prev; aoenv_set_coefs (dm.coefs = ...
                                 from outside) leaves it alone, as in the reference (MAIN/OOPAOEnv/OOPAOEnv.py:314, 508-509), so
                                 the trainers' episode prologue `env.dm.coefs = 0` (MAIN/PO4AO/mbrl.py:50) does not clear it */
+    AOENV_B_COEFS_SEEN,      /* [n_env][A]     the command the last stepped measurement saw under a disturbance (aoenv_set_disturbance):
+                                dm.coefs + B v(tau), what the reference calls dm.coefs = vibration_state + correction_state
+                                (MAIN/OOPAOEnv/vibrationEnv.py:197-202).  Zero until a disturbed step has written it; not loop state */
     AOENV_B_COUNT
 };
 
@@ -277,6 +280,32 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
  * NULL / K == 0: no filter (n = z: the reference's F = 1 before set_params).  Refused with nothing changed: K out of range,
  * non-finite entries.  The stream is waited for once. */
 int aoenv_set_noise_filter(AoEnv* env, const double* h_factors, int K, void* stream);
+
+/* Replaces: the command-space disturbance of the reference's vibration envs (MAIN/OOPAOEnv/vibrationEnv.py:119-123, 146-167,
+ * 197-202: three sine lines each on tip and tilt with random phases per episode, dm.coefs = vibration_state + correction_state, so
+ * that the integrator state holds the correction alone; SinEnv.py / modalAOSinEnv.py, CRL_twoSin.py, twoSin_hpOptim.py are of the
+ * same family), for the loops that run inside the library, every env with its own lines.  The model is rlao_amd/csrc/disturb.hpp:
+ * for env e, mode m < M, line j < J at the integer measurement time tau
+ *     x = fma(freq[e][m][j], (double)tau, phase[e][m][j]);   v[e][m] = sum_j amp[e][m][j] sin(2 pi (x - floor(x)))     (float64)
+ *     seen[e][a] = coefs[e][a] + sum_m modes[a][m] (T)v[e][m]                                             (env dtype, fma chain)
+ * every sum in index order, whatever the shard size or the env's place in it.  While a disturbance is set, aoenv_step,
+ * aoenv_run_integrator, aoenv_run_rollout and aoenv_run_policy_rollout -- and only those -- launch one kernel in front of each step that
+ * writes `seen` into AOENV_B_COEFS_SEEN with that step's tau = t0 + i + 1 (i the frame index; the reference shows vibration[:, t]
+ * with t incremented before use), and the step's measurement shows THAT command on the mirror, on the fused and the batched path, for
+ * both sensors and dtypes.  The step goes on writing the pure command to AOENV_B_COEFS / AOENV_B_DM_PREV.  aoenv_measure,
+ * aoenv_reset_soft, the calibration and aoenv_compute_psf after a bare aoenv_measure never see the disturbance, because a calibration
+ * must not: unlike vibrationEnv.reset, whose first observation shows sample 0, the first disturbed observation here is that of step 0.
+ * With every amp == 0 `seen` equals dm.coefs in value; with no disturbance set there is no extra launch and no changed argument.
+ * t0 lets a vibration run on across episodes.  Everything is copied before the call returns; the stream is waited for once.
+ * The configuration is NOT loop state: it is in neither aoenv_get_buff nor the checkpoint buffers, and a caller that restores a
+ * state sets it again.  Refused, with nothing changed: n_modes / n_lines out of range, a null array, a non-finite entry, a negative amp. */
+typedef struct AoDisturbance {
+    int32_t n_modes, n_lines;      /* M in [1, 64], J in [1, 8] */
+    int64_t t0;                    /* tau = t0 + i + 1 at the measurement of frame i */
+    const double *h_modes;         /* [A][M] dimensionless, e.g. columns of M2C_CL; A covers both DMs of a two-DM shard */
+    const double *h_amp, *h_freq, *h_phase;   /* [n_env][M][J] each: metres of command, cycles per frame, cycles */
+} AoDisturbance;
+int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream);   /* NULL cfg: forget it */
 
 /* Replaces: the exploration episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89), kept on the device and recorded:
  *     action = gain * obs + env.sample_noise(sigma);  next_obs, _, reward, strehl, done, _ = env.step(i, action)

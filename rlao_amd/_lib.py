@@ -17,7 +17,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
  C_SH_SUBAP_IDX, C_SH_REF, C_WFS_UNITS, C_RECON, C_PYR_MASK, C_PYR_TT, C_RECON_FACTORS) = range(17)
 # enum AoBuf
 (B_SCREEN, B_OPD_ATM, B_COEFS, B_PHASE, B_FRAME, B_SIGNAL, B_TOTAL, B_RESIDUAL, B_WFS_MAX, B_XI, B_MT_STATE,
- B_COUNTERS, B_DM_PREV) = range(13)
+ B_COUNTERS, B_DM_PREV, B_COEFS_SEEN) = range(14)
 
 
 (OPT_FAST_WFS, OPT_MFMA_GEMM, OPT_FAST_TRIG, OPT_STORE_ATM_OPD, OPT_FUSED_TAIL, OPT_FUSED_STEP, OPT_DEFER_RING, OPT_COEFS_IMAGE,
@@ -55,6 +55,11 @@ class AoPolicy(C.Structure):
                     (n, C.c_void_p) for n in ("h_w1", "h_b1", "h_w2", "h_b2", "h_w3", "h_b3", "h_proj")]
 
 
+class AoDisturbance(C.Structure):
+    _fields_ = [("n_modes", C.c_int32), ("n_lines", C.c_int32), ("t0", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("h_modes", "h_amp", "h_freq", "h_phase")]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "aoenv_last_error": (C.c_char_p, []),
@@ -80,6 +85,7 @@ EXPORTS = {
     "aoenv_run_integrator": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_noise_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "aoenv_set_disturbance": (C.c_int, [C.c_void_p, C.POINTER(AoDisturbance), C.c_void_p]),
     "aoenv_run_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "aoenv_set_policy": (C.c_int, [C.c_void_p, C.POINTER(AoPolicy), C.c_void_p]),

@@ -361,6 +361,22 @@ size_t rollout_action_lds(int n_valid_act, int n_filter, size_t esz);
 template <typename T>
 int launch_rollout_action(const RolloutActionArgs<T>& a, int n_env, hipStream_t st);
 
+// the command a stepped measurement sees under a disturbance (disturb_kernels.hip; the model is disturb.hpp):
+// seen = coefs + B v(tau), one launch in front of the step
+template <typename T>
+struct DisturbArgs {
+    const T* coefs;          // [E][A] dm.coefs, the pure command
+    T* seen;                 // [E][A] AOENV_B_COEFS_SEEN
+    const T* modes_t;        // [M][A] B transposed
+    const double* amp;       // [E][M][J] metres of command
+    const double* freq;      // [E][M][J] cycles per frame
+    const double* phase;     // [E][M][J] cycles
+    int n_valid_act, n_modes, n_lines;
+    int64_t tau;             // measurement time of this step, t0 + i + 1
+};
+template <typename T>
+int launch_disturb_apply(const DisturbArgs<T>& a, int n_env, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "detector.hpp"
+#include "disturb.hpp"
 #include "policy.hpp"
 #include "sh_device.hpp"
 
@@ -112,6 +113,19 @@ struct AoEnv {
     void* opd_atm = nullptr;
     void* coefs = nullptr;
     void* dm_prev = nullptr;                // [E][A] env.dm_prev, the integrator state (not touched by aoenv_set_coefs)
+    // command-space disturbance (aoenv_set_disturbance, disturb.hpp): in front of every stepped measurement k_disturb_apply writes
+    // coefs + B v(tau) into coefs_seen and the step reads its mirror command there; everything else reads and writes coefs
+    void* coefs_seen = nullptr;             // [E][A] AOENV_B_COEFS_SEEN
+    void* step_cmd = nullptr;               // coefs_seen for the duration of a disturbed step, null otherwise
+    void* cmd() const { return step_cmd ? step_cmd : coefs; }   // the command the phase kernels show on the mirror
+    struct Disturb {
+        bool set = false;
+        int M = 0, J = 0;
+        int64_t t0 = 0;
+        void* modes_t = nullptr;            // [M][A] B transposed, env dtype
+        double* par = nullptr;              // amp, freq, phase: [E][M][J] float64 each, one after the other
+        size_t modes_cap = 0, par_cap = 0;  // elements the two are sized for
+    } disturb;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -559,11 +573,11 @@ int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int sto
     if (env->use_coefs_img && env->c.dm_separable) {               // ELT-size DMs: once per env instead of once per tile
         if constexpr (std::is_same<T, float>::value) {
             if (env->dm_rows)                                       // Gy C on the matrix cores, in operand layout
-                AO_TRY(launch_dm_rows(env->as<float>(env->coefs), env->act_idx, env->gya, env->dm_rows, env->E, env->R, env->nAct, env->A,
+                AO_TRY(launch_dm_rows(env->as<float>(env->cmd()), env->act_idx, env->gya, env->dm_rows, env->E, env->R, env->nAct, env->A,
                                       env->ga_stride, st));
         }
         if (env->coefs_img)
-            AO_TRY(launch_coefs_image<T>(env->as<T>(env->coefs), env->act_idx, env->as<T>(env->coefs_img), env->E, env->nAct, env->A, st));
+            AO_TRY(launch_coefs_image<T>(env->as<T>(env->cmd()), env->act_idx, env->as<T>(env->coefs_img), env->E, env->nAct, env->A, st));
     }
     PhaseArgs pa;
     PhaseBuffers<T> pb;
@@ -651,9 +665,9 @@ template <typename T>
 int refresh_dense_dm(AoEnv* env, hipStream_t st) {
     if (env->c.dm_separable) return 0;
     if (sizeof(T) == 4 && env->use_mfma)                           // one K slice: the product lands in dm_opd directly
-        return launch_gemm_nt_mfma(reinterpret_cast<const float*>(env->coefs), reinterpret_cast<const float*>(env->modes),
+        return launch_gemm_nt_mfma(reinterpret_cast<const float*>(env->cmd()), reinterpret_cast<const float*>(env->modes),
                                    reinterpret_cast<float*>(env->dm_opd), env->E, env->R * env->R, env->A, env->A, env->A, 1, st);
-    return launch_gemm_nt<T>(env->as<T>(env->coefs), env->as<T>(env->modes), env->as<T>(env->dm_opd), env->E,
+    return launch_gemm_nt<T>(env->as<T>(env->cmd()), env->as<T>(env->modes), env->as<T>(env->dm_opd), env->E,
                              env->R * env->R, env->A, env->A, env->A, env->R * env->R, st);
 }
 
@@ -775,7 +789,7 @@ void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_
     pa.n_env = env->E;
     pb = PhaseBuffers<T>{};
     pb.opd_atm = env->as<T>(env->opd_atm);
-    pb.coefs = env->as<T>(env->coefs);
+    pb.coefs = env->as<T>(env->cmd());
     pb.coefs_img = env->use_coefs_img && env->coefs_img ? env->as<T>(env->coefs_img) : nullptr;
     pb.s1a = env->use_coefs_img && env->c.dm_separable ? env->dm_rows : nullptr;
     pb.dm_opd = env->c.dm_separable ? nullptr : env->as<T>(env->dm_opd);
@@ -849,20 +863,50 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     return 0;
 }
 
+// the measurement of frame i under a disturbance: seen = coefs + B v(t0 + i + 1) in a launch of its own; until the guard goes
+// the phase kernels (and the dense DM's surface) read the command there
+struct SeenCommand {
+    AoEnv* env;
+    ~SeenCommand() { env->step_cmd = nullptr; }
+};
+template <typename T>
+int apply_disturbance(AoEnv* env, int i, hipStream_t st) {
+    const AoEnv::Disturb& d = env->disturb;
+    const size_t n = (size_t)env->E * d.M * d.J;
+    DisturbArgs<T> a{};
+    a.coefs = env->as<T>(env->coefs);
+    a.seen = env->as<T>(env->coefs_seen);
+    a.modes_t = env->as<T>(d.modes_t);
+    a.amp = d.par;
+    a.freq = d.par + n;
+    a.phase = d.par + 2 * n;
+    a.n_valid_act = env->A;
+    a.n_modes = d.M;
+    a.n_lines = d.J;
+    a.tau = d.t0 + (int64_t)i + 1;
+    AO_TRY(launch_disturb_apply<T>(a, env->E, st));
+    env->step_cmd = env->coefs_seen;
+    return refresh_dense_dm<T>(env, st);                           // (a dense DM's surface is formed ahead of the phase kernel)
+}
+
 template <typename T>
 int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
            double gain, bool observable, hipStream_t st) {
     const bool fused_step = fused_step_ok<T>(env);
+    SeenCommand seen{env};                                         // (error paths: no later call sees the side buffer)
+    if (env->disturb.set) AO_TRY(apply_disturbance<T>(env, i, st));
     AO_TRY(advance_atmosphere<T>(env, fused_step, st));
     env->atm_user_defined = false;
     if (fused_step) {
         AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, observable, st));
+        env->step_cmd = nullptr;
         if (d_frame)
             AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                                   hipMemcpyDeviceToDevice, st));
         return 0;
     }
     AO_TRY(run_phase<T>(env, 1, env->store_opd_atm ? 1 : 0, st));
+    env->step_cmd = nullptr;                                       // the integration below, and a dense DM's next surface: the pure command
     // one workgroup per env re-reads the factors from L2: wins while launch latency dominates (measured: 19.5 us vs
     // 32.5 us at 256 envs, 96 us vs 75 us at 2048), the batched MFMA GEMM path takes over for large shards
     const bool fused = env->c.wfs_type == AOENV_WFS_SH && env->use_fused_tail && env->n_modes > 0 && env->E <= 1024;
@@ -922,6 +966,7 @@ int buf_info(AoEnv* env, int which, BufInfo* b) {
         case AOENV_B_MT_STATE: *b = {nullptr, (size_t)env->L * E * (kMtN + 1) * 4}; return 0;     // packed on the host
         case AOENV_B_COUNTERS: *b = {nullptr, 16}; return 0;
         case AOENV_B_DM_PREV: *b = {env->dm_prev, E * env->A * z}; return 0;
+        case AOENV_B_COEFS_SEEN: *b = {env->coefs_seen, E * env->A * z}; return 0;
         default: return fail("unknown buffer id %d", which);
     }
 }
@@ -1082,6 +1127,7 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
     A_((void**)&e->pupil, R2);
     A_(&e->opd_atm, E * R2 * z);
     A_(&e->coefs, E * e->A * z);
+    A_(&e->coefs_seen, E * e->A * z);                              // zero until a disturbed step writes it
     A_(&e->dm_prev, E * e->A * z);                                 // self.dm_prev = self.dm.coefs.copy() = 0 (OOPAOEnv.py:313-314)
     A_(&e->phase, E * R2 * z);
     A_(&e->scal, E * 4 * z);
@@ -1926,6 +1972,51 @@ int aoenv_set_noise_filter(AoEnv* env, const double* h_factors, int K, void* str
     AO_TRY(upload_real(env, env->noise_fr, h_factors, n));
     AO_TRY(upload_real(env, env->noise_fl_t, t.data(), n));
     env->noise_K = K;
+    return 0;
+}
+
+int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!cfg) {
+        env->disturb.set = false;                                  // (the tables stay allocated for the next one)
+        return 0;
+    }
+    const int M = cfg->n_modes, J = cfg->n_lines, A = env->A;
+    if (M < 1 || M > kDisturbMaxModes) return fail("aoenv_set_disturbance: n_modes %d outside [1, %d]", M, kDisturbMaxModes);
+    if (J < 1 || J > kDisturbMaxLines) return fail("aoenv_set_disturbance: n_lines %d outside [1, %d]", J, kDisturbMaxLines);
+    if (!cfg->h_modes || !cfg->h_amp || !cfg->h_freq || !cfg->h_phase) return fail("aoenv_set_disturbance: null modes / amp / freq / phase");
+    const size_t nb = (size_t)A * M, np = (size_t)env->E * M * J;
+    for (size_t i = 0; i < nb; ++i)
+        if (!std::isfinite(cfg->h_modes[i])) return fail("aoenv_set_disturbance: modes[%zu] is not finite", i);
+    const struct { const double* p; const char* name; } arrays[] = {{cfg->h_amp, "amp"}, {cfg->h_freq, "freq"}, {cfg->h_phase, "phase"}};
+    for (const auto& a : arrays)
+        for (size_t i = 0; i < np; ++i)
+            if (!std::isfinite(a.p[i])) return fail("aoenv_set_disturbance: %s[%zu] is not finite", a.name, i);
+    for (size_t i = 0; i < np; ++i)
+        if (cfg->h_amp[i] < 0) return fail("aoenv_set_disturbance: amp[%zu] is negative", i);
+    AO_HIP(hipStreamSynchronize(st));                              // a loop in flight reads the tables in place
+    AoEnv::Disturb& d = env->disturb;
+    if (nb > d.modes_cap) {
+        void* p = nullptr;
+        AO_TRY(dmalloc(env, &p, nb * env->esz, false));
+        d.modes_t = p; d.modes_cap = nb;
+    }
+    if (np > d.par_cap) {
+        void* p = nullptr;
+        AO_TRY(dmalloc(env, &p, 3 * np * sizeof(double), false));
+        d.par = static_cast<double*>(p); d.par_cap = np;
+    }
+    std::vector<double> t(nb);                                     // B [A][M] -> [M][A]
+    for (int a = 0; a < A; ++a)
+        for (int m = 0; m < M; ++m) t[(size_t)m * A + a] = cfg->h_modes[(size_t)a * M + m];
+    d.set = false;                                                 // (a failed copy leaves no half-written disturbance in use)
+    AO_TRY(upload_real(env, d.modes_t, t.data(), nb));
+    AO_HIP(hipMemcpy(d.par, cfg->h_amp, np * sizeof(double), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(d.par + np, cfg->h_freq, np * sizeof(double), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(d.par + 2 * np, cfg->h_phase, np * sizeof(double), hipMemcpyHostToDevice));
+    d.M = M; d.J = J; d.t0 = cfg->t0;
+    d.set = true;
     return 0;
 }
 

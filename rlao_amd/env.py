@@ -136,6 +136,93 @@ def resolve_r0_per_env(r0, env_ids, n_envs: int, current) -> np.ndarray:
     return full
 
 
+DISTURB_MAX_MODES, DISTURB_MAX_LINES = 64, 8                       # kDisturbMaxModes, kDisturbMaxLines (rlao_amd/csrc/disturb.hpp)
+
+
+def resolve_disturbance(modes, amp, freq, phase, t0, env_ids, n_envs: int, n_valid_act: int, sampling_time: float, m2c, current) -> dict:
+    """The disturbance of every env after a ``set_disturbance`` call, as the host arrays the library is handed:
+    ``dict(modes [A, M], amp [n_envs, M, J] (metres), freq [n_envs, M, J] (CYCLES PER FRAME), phase [n_envs, M, J] (cycles), t0)``,
+    all float64 and contiguous.  ``modes``: ``[A, M]``, or an int ``M`` for the first ``M`` columns of ``m2c`` (``M2C_CL``), or --
+    with ``env_ids`` and a disturbance in force -- None for the table in force.  ``freq`` arrives in Hz and is multiplied by
+    ``sampling_time``.  ``amp`` / ``freq`` / ``phase`` are ``[M, J]`` (every env the same) or per env: ``[n_envs, M, J]``, with
+    ``env_ids`` (anything ``normalize_env_ids`` takes) one block per listed env in the order of ``env_ids`` (a mask: ascending);
+    ``phase=None`` is zeros.  With ``env_ids`` the other envs keep the rows of ``current`` (an earlier result, whose M and J the
+    call must share) or, without one, carry no lines (amp 0).  Raises ``ValueError`` for wrong shapes, M outside [1, 64], J
+    outside [1, 8], values that are not finite and negative amplitudes.  Pure host code."""
+    n_envs, A = int(n_envs), int(n_valid_act)
+    if modes is None:
+        if env_ids is None or current is None:
+            raise ValueError("modes=None needs env_ids and a disturbance in force")
+        B = current["modes"]
+    elif isinstance(modes, (int, np.integer)) and not isinstance(modes, bool):
+        M = int(modes)
+        if m2c is None or not 1 <= M <= np.shape(m2c)[1]:
+            raise ValueError(f"modes={M}: M2C_CL has {0 if m2c is None else np.shape(m2c)[1]} columns")
+        B = np.asarray(m2c, dtype=np.float64)[:, :M]
+    else:
+        if hasattr(modes, "detach"):
+            modes = modes.detach().cpu().numpy()
+        try:
+            B = np.asarray(modes, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("modes must be numeric") from None
+    if B.ndim != 2 or B.shape[0] != A:
+        raise ValueError(f"modes must have shape (A={A}, M), got {B.shape}")
+    M = B.shape[1]
+    if not 1 <= M <= DISTURB_MAX_MODES:
+        raise ValueError(f"M = {M} modes outside [1, {DISTURB_MAX_MODES}]")
+    given = None if env_ids is None else normalize_env_ids(env_ids, n_envs, return_order=True)[1]
+    k = n_envs if given is None else int(given.size)
+
+    def block(x, name, J):
+        if hasattr(x, "detach"):
+            x = x.detach().cpu().numpy()
+        try:
+            v = np.asarray(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be numeric") from None
+        if v.ndim not in (2, 3) or v.shape[-2] != M or (J is not None and v.shape[-1] != J) or (v.ndim == 3 and v.shape[0] != k):
+            raise ValueError(f"{name} must have shape (M={M}, J) or ({k}, M={M}, J), got {v.shape}")
+        return np.broadcast_to(v, (k,) + v.shape[-2:])
+
+    a = block(amp, "amp", None)
+    J = a.shape[-1]
+    if not 1 <= J <= DISTURB_MAX_LINES:
+        raise ValueError(f"J = {J} lines outside [1, {DISTURB_MAX_LINES}]")
+    f = block(freq, "freq", J) * float(sampling_time)
+    ph = np.zeros((k, M, J)) if phase is None else block(phase, "phase", J)
+    if not (np.isfinite(B).all() and np.isfinite(a).all() and np.isfinite(f).all() and np.isfinite(ph).all()):
+        raise ValueError("modes, amp, freq and phase must be finite")
+    if (a < 0).any():
+        raise ValueError("amp must be >= 0 (a sign belongs into the phase: half a cycle)")
+    out = {"amp": np.zeros((n_envs, M, J)), "freq": np.zeros((n_envs, M, J)), "phase": np.zeros((n_envs, M, J))}
+    if given is not None and current is not None:
+        if current["amp"].shape != (n_envs, M, J):
+            raise ValueError(f"env_ids: the disturbance in force has (M, J) = {current['amp'].shape[1:]}, this call ({M}, {J})")
+        out = {key: current[key].copy() for key in out}
+    rows = slice(None) if given is None else given
+    out["amp"][rows], out["freq"][rows], out["phase"][rows] = a, f, ph
+    out["modes"] = np.ascontiguousarray(B, dtype=np.float64).copy()
+    out["t0"] = int(t0)
+    return out
+
+
+def disturbance_value(cfg: dict, i: int) -> np.ndarray:
+    """``B v(t0 + i + 1)`` of a ``resolve_disturbance`` result, float64 ``[n_envs, A]``: the model of rlao_amd/csrc/disturb.hpp
+    on the host.  The phase ``x = fma(freq, tau, phase)`` is formed with ONE rounding, as there (exact rational arithmetic, then
+    the nearest float64: at tau = 10^9 a product rounded on its own is already off by 1e-7 cycles); its reduction, the sine, the
+    product with the amplitude and the sums are NumPy float64 in the model's order."""
+    from fractions import Fraction
+    tau = int(cfg["t0"]) + int(i) + 1
+    f, ph = cfg["freq"], cfg["phase"]
+    x = np.array([float(Fraction(a) * tau + Fraction(b)) for a, b in zip(f.ravel().tolist(), ph.ravel().tolist())]).reshape(f.shape)
+    term = cfg["amp"] * np.sin(2.0 * np.pi * (x - np.floor(x)))
+    v = np.zeros(term.shape[:-1])
+    for j in range(term.shape[-1]):                                 # (index order, like the device's loop)
+        v = v + term[..., j]
+    return v @ cfg["modes"].T
+
+
 def _wall_clock_seed() -> int:
     """The seed of ``generateNewPhaseScreen(seed=None)``: the second of the day (OOPAO/Atmosphere.py:561-563)."""
     import time
@@ -389,9 +476,19 @@ class _DmProxy:
     def coefs(self):
         return self._e._fetch(L.B_COEFS, (self._e.nValidAct,))
 
+    @property
+    def coefs_seen(self):
+        """The command the last stepped measurement saw under a disturbance (``AOENV_B_COEFS_SEEN``): ``dm.coefs`` of before that
+        step plus ``B v(tau)``; a new device tensor ``[n_envs, A]``.  Zero until a disturbed step has run."""
+        e = self._e
+        out = e._shard.download(L.B_COEFS_SEEN, (e.n_envs, e.nValidAct), e._stream())
+        return _torch().as_tensor(out, device=e.device)
+
     @coefs.setter
     def coefs(self, val):
         e = self._e
+        if hasattr(val, "detach"):                                  # a tensor, wherever it lives (dm.coefs_seen of a twin)
+            val = val.detach().cpu().numpy()
         if np.isscalar(val):
             if val != 0:
                 print("Error: wrong value for the coefficients")
@@ -589,6 +686,7 @@ class BatchedAOEnv:
         self._per_env_clock = False
         self._wind_pixels = 1                                      # ceiling of the per-env winds [px / frame] (set_wind_ceiling)
         self._r0_env = None                                        # [n_envs] Fried parameters once per-env r0 is set
+        self._disturb = None                                       # resolve_disturbance()'s arrays while a disturbance is set
 
     # -- construction --------------------------------------------------------------------------------
     def set_params_file(self, param_file, oopao_path):
@@ -671,7 +769,7 @@ class BatchedAOEnv:
 
         # -- the loop shard -----------------------------------------------------------------------------
         self._shard = self._make_shard(self.n_envs, self.dtype, n_layer=p.nLayer, max_group=1)
-        self._r0_env = self._wind_env = None                        # a new shard: one r0, one wind, the shared clock
+        self._r0_env = self._wind_env = self._disturb = None         # a new shard: one r0, one wind, the shared clock, no disturbance
         self._per_env_clock = False
         self._wind_pixels = 1
         sh = self._shard
@@ -902,6 +1000,38 @@ class BatchedAOEnv:
         full = resolve_r0_per_env(r0, env_ids, self.n_envs, self.param.r0 if self._r0_env is None else self._r0_env)
         self._shard.set_r0_env(full, self.param.r0, self._stream())
         self._r0_env = full
+
+    def set_disturbance(self, modes, amp, freq, phase=None, t0=0, env_ids=None):
+        """A disturbance in command space that ``step``, ``run_integrator``, ``rollout`` and ``policy_rollout`` see and the
+        controller must reject: the vibration lines of MAIN/OOPAOEnv/vibrationEnv.py:119-123, 146-167, 197-202, every env with its
+        own.  At the measurement of frame ``i`` the mirror shows ``dm.coefs + modes @ v(t0 + i + 1)`` with
+        ``v[m] = sum_j amp[m, j] sin(2 pi (freq[m, j] samplingTime tau + phase[m, j]))``; ``dm.coefs``, ``dm_prev`` and the checkpoint
+        keep the pure command (``aoenv_set_disturbance``).  ``modes``: ``[A, M]`` (dimensionless, M <= 64) or an int ``M`` for the
+        first M columns of ``M2C_CL``; ``amp`` [m of command], ``freq`` [Hz], ``phase`` [cycles, None: zeros]: ``[M, J]`` for every
+        env or ``[n_envs, M, J]`` (J <= 8).  ``env_ids`` (a list or a mask): the blocks belong to the listed envs, in that order, and
+        the other envs keep theirs (none yet: no lines); ``modes`` may then be None for the table in force.  ``t0``: the frame
+        count in front of frame 0, so that a vibration runs on across episodes.  ``measure``, ``reset_soft`` and the calibration
+        never see it: the first disturbed observation is that of step 0 (``vibrationEnv.reset`` shows sample 0 at once).  Not part
+        of ``get_state``: after ``set_state`` call this again."""
+        full = resolve_disturbance(modes, amp, freq, phase, t0, env_ids, self.n_envs, self.nValidAct, self.param.samplingTime,
+                                   self.M2C_CL, self._disturb)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        cfg = L.AoDisturbance(n_modes=full["modes"].shape[1], n_lines=full["amp"].shape[2], t0=full["t0"], h_modes=ptr(full["modes"]),
+                              h_amp=ptr(full["amp"]), h_freq=ptr(full["freq"]), h_phase=ptr(full["phase"]))
+        L.check(self._shard.lib.aoenv_set_disturbance(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        self._disturb = full
+
+    def clear_disturbance(self):
+        """No disturbance: every call does exactly what it did before ``set_disturbance``."""
+        L.check(self._shard.lib.aoenv_set_disturbance(self._shard.h, None, C.c_void_p(self._stream())))
+        self._disturb = None
+
+    def disturbance(self, i: int) -> np.ndarray:
+        """``modes @ v(t0 + i + 1)``, what the measurement of frame ``i`` sees on top of ``dm.coefs``: float64 NumPy
+        ``[n_envs, A]``, computed on the host (``disturbance_value``); zeros while none is set."""
+        if self._disturb is None:
+            return np.zeros((self.n_envs, self.nValidAct))
+        return disturbance_value(self._disturb, i)
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset
