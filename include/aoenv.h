@@ -307,6 +307,37 @@ typedef struct AoDisturbance {
 } AoDisturbance;
 int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream);   /* NULL cfg: forget it */
 
+/* Replaces: TimeDelayEnv (MAIN/PO4AO/util_simple.py:25-52, the contract is :46-52: append the action, apply action_buffer[0], drop
+ * it), which both trainer mains put around the env with delay = 1 (MAIN/mbrl_main.py:46, MAIN/mbrl_main_network.py:41,
+ * MAIN/PO4AO/mbrl_funcsRAZOR.py:32-33), and the action_buffer every gymnasium env of the reference carries (OOPAOEnv_VPG.py:562-566,
+ * modalAOEnv.py:150-154, IM_delayEnv.py:164-165, vibrationEnv.py) -- "can also be done inside OOPAO or OOPAO_env", as the docstring
+ * of TimeDelayEnv says -- for the loops that run inside the library.
+ * With a delay of d frames the library keeps the d actions issued but not yet applied, oldest first: the delay line.  A step that is
+ * given (aoenv_step) or forms (aoenv_run_integrator, aoenv_run_rollout, aoenv_run_policy_rollout) action a_k appends it, applies the
+ * oldest entry and drops it: step k of an episode applies a_(k-d), or zero for k < d.  Nothing else in the step changes: the order of
+ * effects, dm_prev and the leak, telemetry, the return accumulator, the disturbance (tau = t0 + i + 1 whatever the delay).  The
+ * recorded trajectories keep the action ISSUED in step k, and so do the policy windows (d_past_act), as mbrl.py:80-81 rolls them.
+ * The line is a ring of d + 1 image slots (rlao_amd/csrc/delay.hpp).  aoenv_step copies the caller's action into it in one launch
+ * in front of the step (the tensor may be reused at once); aoenv_run_integrator writes gain * obs there with the same kernel (one
+ * multiply in the env dtype: the bits a caller forms) and steps as aoenv_step does, its fused-gain epilogue being the path of
+ * delay 0; the recorded rollouts use their trajectory as the line -- step k is handed trajectory slot k - d, or a pending row of
+ * the ring for k < d, no launch per step -- and one launch at the end of the call copies the newest min(n_steps, d) actions into
+ * the ring, so that the line is what n_steps appends would have left, for n_steps < d and across calls of any kind too.
+ * aoenv_reset_envs zeroes the rows of the listed envs in every slot; aoenv_reset_soft, aoenv_measure, aoenv_new_screens* and
+ * aoenv_set_coefs leave the line alone.
+ * aoenv_set_delay sets the delay and zeroes the line; with the delay in force it is the "clear" of TimeDelayEnv.reset /
+ * reset_soft (util_simple.py:36-44).  The work is enqueued on `stream`, which is waited for only by the first call with a delay
+ * > 0 (the ring is allocated then, for every delay).  delay == 0: every call does exactly what it did without the feature, no
+ * extra launch and no changed argument.  Refused, with nothing changed: a null env, a delay outside [0, AOENV_MAX_DELAY]. */
+#define AOENV_MAX_DELAY 8
+int aoenv_set_delay(AoEnv* env, int delay, void* stream);
+int aoenv_get_delay(AoEnv* env, int* delay);
+/* The delay line as loop state (TimeDelayEnv.action_buffer, util_simple.py:29-31): host arrays of the env dtype,
+ * [delay][n_env][nAct][nAct] in logical order, oldest first, whatever the ring's position.  Both synchronise the stream as
+ * aoenv_download / aoenv_upload_state do.  Refused: a null pointer, bytes other than that size, delay == 0. */
+int aoenv_get_delay_line(AoEnv* env, void* h_dst, size_t bytes, void* stream);
+int aoenv_set_delay_line(AoEnv* env, const void* h_src, size_t bytes, void* stream);
+
 /* Replaces: the exploration episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89), kept on the device and recorded:
  *     action = gain * obs + env.sample_noise(sigma);  next_obs, _, reward, strehl, done, _ = env.step(i, action)
  * for the frames [i0, i0 + n_steps), every observation, action, reward and Strehl ratio written into the caller's trajectory buffers
@@ -418,7 +449,8 @@ int aoenv_set_return_accumulator(AoEnv* env, void* d_return);
 
 /* State access (get_state / set_state = checkpoint / resume of the env; also the stage boundaries
  * compared by the parity tests).  The complete loop state is {AOENV_B_SCREEN, aoenv_get_buff, AOENV_B_MT_STATE,
- * AOENV_B_COEFS, AOENV_B_COUNTERS} plus the caller's last observation; aoenv_upload_state(AOENV_B_SCREEN) takes the
+ * AOENV_B_COEFS, AOENV_B_DM_PREV, AOENV_B_COUNTERS}, under a control delay {aoenv_get_delay, aoenv_get_delay_line} (no AoBuf: the
+ * line has functions of its own), plus the caller's last observation; aoenv_upload_state(AOENV_B_SCREEN) takes the
  * logical layer.mapShift (as aoenv_download returns it) and re-derives the clip range.  `which` is an AoBuf.  aoenv_buffer returns the device pointer and size in bytes;
  * aoenv_download copies to a host buffer of the env dtype and synchronises the stream. */
 int aoenv_buffer(AoEnv* env, int which, void** d_ptr, size_t* bytes);

@@ -23,6 +23,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
 (OPT_FAST_WFS, OPT_MFMA_GEMM, OPT_FAST_TRIG, OPT_STORE_ATM_OPD, OPT_FUSED_TAIL, OPT_FUSED_STEP, OPT_DEFER_RING, OPT_COEFS_IMAGE,
  OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD, OPT_ENV_WIND_PIXELS) = range(11)
 OPT_FORCE_PATH = 99
+MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
 PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN = 256, 512, 1024
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
@@ -86,6 +87,10 @@ EXPORTS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_noise_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_set_disturbance": (C.c_int, [C.c_void_p, C.POINTER(AoDisturbance), C.c_void_p]),
+    "aoenv_set_delay": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "aoenv_get_delay": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "aoenv_get_delay_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aoenv_set_delay_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aoenv_run_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "aoenv_set_policy": (C.c_int, [C.c_void_p, C.POINTER(AoPolicy), C.c_void_p]),

@@ -377,6 +377,18 @@ struct DisturbArgs {
 template <typename T>
 int launch_disturb_apply(const DisturbArgs<T>& a, int n_env, hipStream_t st);
 
+// the delay line of aoenv_set_delay (delay_kernels.hip; the index arithmetic is delay.hpp): a ring of image slots, each
+// [E][nAct^2] at a stride of slot_stride elements, a multiple of 16 bytes from a 16-byte aligned base
+// push: slot `slot` = src (scale == 0) or (T)scale * src, one launch in front of a delayed step; n = E nAct^2
+template <typename T>
+int launch_delay_push(T* ring, size_t slot_stride, int slot, const T* src, size_t n, double scale, hipStream_t st);
+// refill behind a recorded loop: copy c < m takes trajectory slot first_traj + c (n elements each) into ring slot (first_slot + c) % n_slots
+template <typename T>
+int launch_delay_refill(T* ring, size_t slot_stride, int n_slots, int first_slot, const T* traj, int first_traj, int m, size_t n, hipStream_t st);
+// aoenv_reset_envs: the rows of the listed envs zeroed in every slot
+template <typename T>
+int launch_delay_zero_rows(T* ring, size_t slot_stride, int n_slots, const int* env_idx, int n_idx, int img, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

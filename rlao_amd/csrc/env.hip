@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "delay.hpp"
 #include "detector.hpp"
 #include "disturb.hpp"
 #include "policy.hpp"
@@ -126,6 +127,12 @@ struct AoEnv {
         double* par = nullptr;              // amp, freq, phase: [E][M][J] float64 each, one after the other
         size_t modes_cap = 0, par_cap = 0;  // elements the two are sized for
     } disturb;
+    // control delay (aoenv_set_delay, delay.hpp): the d actions issued but not yet applied, in a ring of d + 1 image slots
+    // ([E][nAct^2] each at a stride padded to 16 bytes); allocated for kMaxDelay + 1 slots by the first delay > 0
+    DelayLine delay;
+    void* delay_ring = nullptr;
+    size_t delay_stride = 0;                // elements between slots
+    void* delay_slot(int slot) const { return static_cast<char*>(delay_ring) + (size_t)slot * delay_stride * esz; }
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -887,6 +894,38 @@ int apply_disturbance(AoEnv* env, int i, hipStream_t st) {
     AO_TRY(launch_disturb_apply<T>(a, env->E, st));
     env->step_cmd = env->coefs_seen;
     return refresh_dense_dm<T>(env, st);                           // (a dense DM's surface is formed ahead of the phase kernel)
+}
+
+// A delayed step (delay.hpp): the issued action -- the caller's image, or scale * src with scale != 0 (the integrator's gain * obs)
+// -- goes into the ring in a launch of its own, and the step applies the oldest pending one from there.  The caller moves the
+// index on (delay_after) once the step is enqueued.
+template <typename T>
+int delay_push(AoEnv* env, const void* src, double scale, hipStream_t st, const void** applied) {
+    const size_t n = (size_t)env->E * env->nAct * env->nAct;
+    AO_TRY(launch_delay_push<T>(env->as<T>(env->delay_ring), env->delay_stride, delay_write_slot(env->delay), static_cast<const T*>(src), n,
+                                scale, st));
+    *applied = env->delay_slot(delay_apply_slot(env->delay));
+    return 0;
+}
+
+// step k of a recorded loop: the action it applies -- its own (no delay), trajectory slot k - d, or a pending row of the ring
+template <typename T>
+const T* delay_loop_action(const AoEnv* env, const T* d_action, int k) {
+    const size_t n = (size_t)env->E * env->nAct * env->nAct;
+    if (env->delay.d == 0) return d_action + (size_t)k * n;
+    const DelaySource s = delay_loop_source(env->delay, k);
+    return s.trajectory ? d_action + (size_t)s.slot * n : static_cast<const T*>(env->delay_slot(s.slot));
+}
+
+// behind a recorded loop of n_steps: the newest min(n_steps, d) actions into the ring, the index moved on
+template <typename T>
+int delay_loop_end(AoEnv* env, const T* d_action, int n_steps, hipStream_t st) {
+    if (env->delay.d == 0) return 0;
+    const DelayRefill r = delay_refill(env->delay, n_steps);
+    AO_TRY(launch_delay_refill<T>(env->as<T>(env->delay_ring), env->delay_stride, delay_slots(env->delay), r.first_slot, d_action, r.first_traj,
+                                  r.m, (size_t)env->E * env->nAct * env->nAct, st));
+    env->delay = delay_after(env->delay, n_steps);
+    return 0;
 }
 
 template <typename T>
@@ -1790,6 +1829,9 @@ static int reset_on_device(AoEnv* env, const int* d_idx, int n, const uint32_t* 
     if (d_idx) {
         AO_TRY(launch_reset_env_rows<T>(d_idx, n, env->as<T>(env->coefs), env->as<T>(env->dm_prev), env->A, env->env_clk[env->clk_cur],
                                         env->env_taps, env->L, env->E, st));
+        if (env->delay.d > 0)                                      // their pending actions too (TimeDelayEnv.reset_envs clears those rows)
+            AO_TRY(launch_delay_zero_rows<T>(env->as<T>(env->delay_ring), env->delay_stride, delay_slots(env->delay), d_idx, n,
+                                             env->nAct * env->nAct, st));
         AO_TRY(refresh_dense_dm<T>(env, st));
     }
     AO_TRY(draw_screens<T>(env, d_idx, n, d_screen_seeds, d_scale, r0, L0, pixel_size, tmp, st));
@@ -1925,7 +1967,12 @@ int aoenv_step(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_fra
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return AO_DISPATCH(env, step_t, env, i, d_action, d_obs, d_frame, d_reward, d_strehl, 0.0, true, st);
+    if (env->delay.d == 0) return AO_DISPATCH(env, step_t, env, i, d_action, d_obs, d_frame, d_reward, d_strehl, 0.0, true, st);
+    const void* applied = nullptr;                                 // the caller's tensor may be reused at once: it is copied
+    AO_TRY(AO_DISPATCH(env, delay_push, env, d_action, 0.0, st, &applied));
+    AO_TRY(AO_DISPATCH(env, step_t, env, i, applied, d_obs, d_frame, d_reward, d_strehl, 0.0, true, st));
+    env->delay = delay_after(env->delay, 1);
+    return 0;
 }
 
 int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_obs, void* d_frame, void* d_reward,
@@ -1939,9 +1986,21 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
     hipStream_t st = static_cast<hipStream_t>(stream);
     // only the last step's residual phase and camera frame can be read afterwards (aoenv_buffer, aoenv_download, aoenv_compute_psf,
     // d_frame, checkpoints: all of them between calls): the fused step leaves the stores of the other steps out
-    for (int k = 0; k < n_steps; ++k)
-        AO_TRY(AO_DISPATCH(env, step_t, env, i0 + k, d_obs /*unused*/, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward,
-                           d_strehl, gain, k == n_steps - 1, st));
+    if (env->delay.d == 0) {
+        for (int k = 0; k < n_steps; ++k)
+            AO_TRY(AO_DISPATCH(env, step_t, env, i0 + k, d_obs /*unused*/, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward,
+                               d_strehl, gain, k == n_steps - 1, st));
+        return 0;
+    }
+    // under a delay the action formed now is applied d steps later: gain * obs goes into the ring (one small launch per step, one
+    // multiply in the env dtype as k_rollout_action forms it at sigma 0) and the step is the explicit-action step of aoenv_step
+    for (int k = 0; k < n_steps; ++k) {
+        const void* applied = nullptr;
+        AO_TRY(AO_DISPATCH(env, delay_push, env, d_obs, gain, st, &applied));
+        AO_TRY(AO_DISPATCH(env, step_t, env, i0 + k, applied, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward, d_strehl, 0.0,
+                           k == n_steps - 1, st));
+        env->delay = delay_after(env->delay, 1);
+    }
     return 0;
 }
 
@@ -2020,6 +2079,63 @@ int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream) {
     return 0;
 }
 
+// ---- the control delay (delay.hpp) ------------------------------------------------------------------------------------------------
+static_assert(kMaxDelay == AOENV_MAX_DELAY, "delay.hpp and aoenv.h disagree");
+int aoenv_set_delay(AoEnv* env, int delay, void* stream) {
+    AO_CHECK_ENV(env);
+    if (delay < 0 || delay > AOENV_MAX_DELAY) return fail("aoenv_set_delay: delay %d outside [0, %d]", delay, AOENV_MAX_DELAY);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (delay > 0) {
+        if (!env->delay_ring) {                                    // storage grows once: every delay fits from then on
+            const size_t per16 = 16 / env->esz, n = (size_t)env->E * env->nAct * env->nAct;
+            const size_t stride = (n + per16 - 1) / per16 * per16;
+            AO_HIP(hipStreamSynchronize(st));
+            void* p = nullptr;
+            AO_TRY(dmalloc(env, &p, (size_t)(kMaxDelay + 1) * stride * env->esz, false));
+            env->delay_ring = p;
+            env->delay_stride = stride;
+        }
+        AO_HIP(hipMemsetAsync(env->delay_ring, 0, (size_t)(delay + 1) * env->delay_stride * env->esz, st));
+    }
+    env->delay = DelayLine{delay, 0};
+    return 0;
+}
+
+int aoenv_get_delay(AoEnv* env, int* delay) {
+    if (!env || !delay) return fail("aoenv_get_delay: null argument");
+    *delay = env->delay.d;
+    return 0;
+}
+
+// the line on the host in logical order, [d][E][nAct^2]: pending row j is ring slot delay_pending_slot(j)
+static int delay_line_check(AoEnv* env, const void* h, size_t bytes, const char* who) {
+    if (!h) return fail("%s: null host pointer", who);
+    if (env->delay.d == 0) return fail("%s: no delay is set (aoenv_set_delay)", who);
+    const size_t want = (size_t)env->delay.d * env->E * env->nAct * env->nAct * env->esz;
+    if (bytes != want) return fail("%s: got %zu bytes, expected %zu", who, bytes, want);
+    return 0;
+}
+
+int aoenv_get_delay_line(AoEnv* env, void* h_dst, size_t bytes, void* stream) {
+    AO_CHECK_ENV(env);
+    AO_TRY(delay_line_check(env, h_dst, bytes, "aoenv_get_delay_line"));
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    const size_t row = (size_t)env->E * env->nAct * env->nAct * env->esz;
+    for (int j = 0; j < env->delay.d; ++j)
+        AO_HIP(hipMemcpy(static_cast<char*>(h_dst) + (size_t)j * row, env->delay_slot(delay_pending_slot(env->delay, j)), row, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int aoenv_set_delay_line(AoEnv* env, const void* h_src, size_t bytes, void* stream) {
+    AO_CHECK_ENV(env);
+    AO_TRY(delay_line_check(env, h_src, bytes, "aoenv_set_delay_line"));
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    const size_t row = (size_t)env->E * env->nAct * env->nAct * env->esz;
+    for (int j = 0; j < env->delay.d; ++j)
+        AO_HIP(hipMemcpy(env->delay_slot(delay_pending_slot(env->delay, j)), static_cast<const char*>(h_src) + (size_t)j * row, row, hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C++" {
 template <typename T>
 static int run_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_action, void* d_reward, void* d_strehl, void* d_frame,
@@ -2046,11 +2162,13 @@ static int run_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_
         a.counter = counter + (uint32_t)k;
         AO_TRY(launch_rollout_action<T>(a, env->E, st));
         // the explicit-action step of aoenv_step; only the last step's residual phase and frame can be read afterwards
-        AO_TRY(step_t<T>(env, cfg->i0 + k, a.action, static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
+        // (under a delay the trajectory is the delay line: the action of step k - d, or a pending row of the ring; delay.hpp)
+        AO_TRY(step_t<T>(env, cfg->i0 + k, delay_loop_action<T>(env, static_cast<const T*>(d_action), k),
+                         static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
                          d_reward ? static_cast<T*>(d_reward) + (size_t)k * E : scratch,
                          d_strehl ? static_cast<T*>(d_strehl) + (size_t)k * E : scratch + E, 0.0, last, st));
     }
-    return 0;
+    return delay_loop_end<T>(env, static_cast<const T*>(d_action), cfg->n_steps, st);
 }
 }  // extern "C++"
 
@@ -2254,10 +2372,12 @@ static int run_policy_rollout_t(AoEnv* env, const AoRollout* cfg, void* d_obs, v
         aa.action = static_cast<T*>(d_action) + (size_t)k * E * img;
         aa.counter = counter + (uint32_t)k;
         AO_TRY(policy_eval_t<T>(env, in, aa, st));
-        AO_TRY(step_t<T>(env, cfg->i0 + k, aa.action, static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
+        AO_TRY(step_t<T>(env, cfg->i0 + k, delay_loop_action<T>(env, static_cast<const T*>(d_action), k),
+                         static_cast<T*>(d_obs) + (size_t)(k + 1) * E * img, last ? d_frame : nullptr,
                          d_reward ? static_cast<T*>(d_reward) + (size_t)k * E : scratch,
                          d_strehl ? static_cast<T*>(d_strehl) + (size_t)k * E : scratch + E, 0.0, last, st));
     }
+    AO_TRY(delay_loop_end<T>(env, static_cast<const T*>(d_action), cfg->n_steps, st));
     // the windows n_steps iterations of mbrl.py:80-81 leave (the trajectory is complete: stream order)
     AO_TRY(launch_policy_roll<T>(static_cast<T*>(d_past_obs), static_cast<const T*>(d_obs), cfg->n_steps, env->policy.H, env->E, (int)img, st));
     return launch_policy_roll<T>(static_cast<T*>(d_past_act), static_cast<const T*>(d_action), cfg->n_steps, env->policy.H, env->E, (int)img, st);

@@ -667,7 +667,8 @@ class BatchedAOEnv:
         self.gainCL = None
         self.net_gain = 0.5
         self.leak = 0.99
-        self.delay = 1
+        # (the reference's unused constant `self.delay = 1`, OOPAOEnv.py:55, is the read-only property `delay` here: the control delay
+        # the library applies, 0 until set_delay)
         self.F = 1
         self.reconstructor = None
         self.nActuator = None
@@ -1033,6 +1034,42 @@ class BatchedAOEnv:
             return np.zeros((self.n_envs, self.nValidAct))
         return disturbance_value(self._disturb, i)
 
+    # -- the control delay inside the library (TimeDelayEnv, MAIN/PO4AO/util_simple.py:25-52) ----------------------------------
+    def set_delay(self, d: int):
+        """A control delay of ``d`` frames (0 .. 8) for every loop the library runs: ``step``, ``run_integrator``, ``rollout`` and
+        ``policy_rollout`` apply in step k the action issued in step k - d, zero for k < d -- what ``TimeDelayEnv(env, d)`` does
+        around ``step`` (util_simple.py:46-52; both trainer mains run with delay 1), as state of the library (``aoenv_set_delay``),
+        so that the device loops honour it.  The recorded trajectories and the policy windows keep the actions ISSUED.  The call
+        zeroes the delay line; with the current ``d`` it is the clear of a new episode, which ``reset_soft()`` does by itself.
+        ``set_delay(0)``: no delay, every call does exactly what it did before.  Use this INSTEAD of wrapping the env: a
+        ``TimeDelayEnv`` around an env with a library delay adds the two."""
+        L.check(self._shard.lib.aoenv_set_delay(self._shard.h, int(d), C.c_void_p(self._stream())))
+
+    @property
+    def delay(self) -> int:
+        """The control delay in force, in frames (``set_delay``)."""
+        d = C.c_int(0)
+        L.check(self._shard.lib.aoenv_get_delay(self._shard.h, C.byref(d)))
+        return int(d.value)
+
+    def _delay_line_host(self, d: int) -> np.ndarray:
+        line = np.empty((d, self.n_envs, self.nActuator, self.nActuator), dtype=np.float32 if self.dtype == "f32" else np.float64)
+        L.check(self._shard.lib.aoenv_get_delay_line(self._shard.h, line.ctypes.data_as(C.c_void_p), line.nbytes, C.c_void_p(self._stream())))
+        return line
+
+    def delay_line(self):
+        """The actions issued but not yet applied, oldest first (``TimeDelayEnv.action_buffer``): a new tensor ``[d, N, a, a]``
+        (``output='numpy'``: a float64 array ``[d, a, a]``); ``d == 0``: empty."""
+        torch = _torch()
+        d = self.delay
+        if d == 0:
+            line = torch.empty((0, self.n_envs, self.nActuator, self.nActuator), device=self.device, dtype=self.tdtype)
+        else:
+            line = torch.as_tensor(self._delay_line_host(d)).to(self.device)
+        if self.output == "numpy":
+            return line.detach().to("cpu", dtype=torch.float64).numpy()[:, 0]
+        return line
+
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset
         return int(seed) + idx * self.env_seed_stride
@@ -1130,8 +1167,12 @@ class BatchedAOEnv:
         return t
 
     def reset_soft(self):
-        """MAIN/OOPAOEnv/OOPAOEnv.py:82-86."""
+        """MAIN/OOPAOEnv/OOPAOEnv.py:82-86.  Under a library delay (``set_delay``) the delay line is cleared too, as
+        ``TimeDelayEnv.reset_soft`` refills its buffer (MAIN/PO4AO/util_simple.py:41-44)."""
         self.action_buffer = []
+        d = self.delay
+        if d > 0:
+            self.set_delay(d)
         # a NEW tensor, like step(): the observation handed out by the previous step (a trainer may have kept it) is not written to
         obs = _torch().empty_like(self._obs)
         L.check(self._shard.lib.aoenv_reset_soft(self._shard.h, C.c_void_p(obs.data_ptr()), C.c_void_p(self._stream())))
@@ -1202,7 +1243,8 @@ class BatchedAOEnv:
     def run_integrator(self, i0: int, n_steps: int, gain=None):
         """On-device closed loop of MAIN/integrator_oopao_razor.py:66-91: ``action = gainCL * obs`` fused into
         the step epilogue; returns the last (obs, reward, strehl).  ``reset_soft()`` (or a previous step) must
-        have produced the current observation."""
+        have produced the current observation.  Under a library delay (``set_delay``) ``gainCL * obs`` goes into the delay line
+        instead (one small launch per step) and the step applies the action formed ``delay`` steps earlier."""
         g = float(self.gainCL if gain is None else gain)
         # the loop runs in place on the observation: on private copies, never on tensors step() / reset_soft() have handed out
         self._obs = self._obs.clone()
@@ -1362,7 +1404,11 @@ class BatchedAOEnv:
         n_envs) continues the episode bit for bit."""
         sh, p, at = self._shard, self.param, self._atm_tables
         st = self._stream()
+        d = self.delay
+        # (the keys of a control delay only while one is set: the state of an env without one is what it always was)
+        line = {"delay": d, "delay_line": self._delay_line_host(d)} if d > 0 else {}
         return {
+            **line,
             "screen": self._download_screens(),
             "buff": None if self._per_env_clock else sh.get_buff(p.nLayer).copy(),
             "clock_env": sh.get_clock_env(p.nLayer, self.n_envs) if self._per_env_clock else None,
@@ -1414,6 +1460,13 @@ class BatchedAOEnv:
         sh.upload_state(L.B_SIGNAL, state["signal"], st)
         sh.upload_state(L.B_COUNTERS, state["counters"], st, dtype=np.uint32)
         self.explore_seed = int(state.get("explore_seed", self.explore_seed))   # (a checkpoint from before rollout() has none)
+        d = int(state.get("delay", 0))                               # (a state without the keys: no delay)
+        self.set_delay(d)
+        if d > 0:
+            line = np.ascontiguousarray(state["delay_line"], dtype=np.float32 if self.dtype == "f32" else np.float64)
+            if line.shape != (d, self.n_envs, self.nActuator, self.nActuator):
+                raise ValueError(f"delay_line must have shape ({d}, {self.n_envs}, {self.nActuator}, {self.nActuator}), got {line.shape}")
+            L.check(sh.lib.aoenv_set_delay_line(sh.h, line.ctypes.data_as(C.c_void_p), line.nbytes, C.c_void_p(st)))
         self._obs = _torch().as_tensor(state["obs"]).to(device=self.device, dtype=self.tdtype).clone()   # (never into a handed-out tensor)
 
     def _download_screens(self):
