@@ -42,9 +42,12 @@ __global__ void __launch_bounds__(256) k_detector(T* __restrict__ frame, T* __re
                 lit = valid2d[(r / p) * n_subap + c4 / p] != 0;  // (a quad never straddles lenslets it matters for: p % 4 == 0 or sh6)
             }
         }
+        // A Shack-Hartmann lenslet outside the pupil holds no light: the spots kernels of the other lenslet sizes write the valid
+        // lenslets only, so what the frame holds there is this kernel's own counts of the frame before -- not photons.
+        const bool dark_quad = valid2d && !lit;
         f32x4d v;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) v[s] = in[s] ? (float)fr[pix[s]] : 0.f;
+        for (int s = 0; s < 4; ++s) v[s] = (in[s] && !dark_quad) ? (float)fr[pix[s]] : 0.f;
         detector_quad<true>(v, pix, pix[0], (uint32_t)e, d, rtab, pa);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -125,10 +128,10 @@ int launch_detector(T* frame, T* wfs_max, const uint8_t* valid2d, int n_env, int
                     const PoissonAlias& pa, hipStream_t st) {
     if (d.active && d.photon_noise && (!pa.tab || pa.lmax < palias::kCoarseStep)) return fail("camera: the photon-noise tables are missing");
     if (!d.active) return 0;
-    if (valid2d) hipLaunchKernelGGL(k_zero<T>, dim3(cdiv(n_env, 256)), dim3(256), 0, st, wfs_max, n_env);
     const int sh6 = (valid2d && n_subap > 0 && cam == 6 * n_subap) ? 1 : 0;
-    if (valid2d && !sh6 && (cam / n_subap) % 4 != 0)
+    if (valid2d && !sh6 && (cam / n_subap) % 4 != 0)                // (refused before anything is launched: wfs_max stays the spots')
         return fail("camera noise on a Shack-Hartmann frame needs 6 or a multiple of 4 pixels per lenslet, got %d", cam / n_subap);
+    if (valid2d) hipLaunchKernelGGL(k_zero<T>, dim3(cdiv(n_env, 256)), dim3(256), 0, st, wfs_max, n_env);
     if constexpr (sizeof(T) == 4) {
         if (sh6) {
             const int n_runs = cdiv(n_subap * n_subap * 3, 512);

@@ -600,8 +600,10 @@ int apply_detector(AoEnv* env, bool sh, hipStream_t st) {
     if (!env->det.active) return 0;
     env->det.frame_counter += 1;
     AO_PROF(env, DETECTOR, st);
-    return launch_detector<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sh ? env->valid2d : nullptr, env->E,
-                              env->c.cam_res, env->nSub, env->det, env->alias(), st);
+    const int rc = launch_detector<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sh ? env->valid2d : nullptr, env->E,
+                                      env->c.cam_res, env->nSub, env->det, env->alias(), st);
+    if (rc) env->det.frame_counter -= 1;                           // a refused frame is no frame of the noise streams
+    return rc;
 }
 
 // Shack-Hartmann spots, then the camera on the frame (self*self.cam, OOPAO/ShackHartmann.py:539-576).  [Round 3 measured the camera

@@ -36,18 +36,27 @@ def host_normals(exe, seed, env0, n_env, c0, n_c, A, env=None):
     return z.reshape(n_env, n_c, A).copy(), out.stderr.decode("utf-8", "replace")
 
 
-def numpy_normals(seed, env0, n_env, c0, n_c, A):
-    """The stream restated: Philox4x32-7 in uint64 arithmetic, Box-Muller in float64.  z[n_env][n_c][A] float64."""
-    nq = (A + 3) // 4
+def philox4x32_7(c0, c1, c2, c3, seed):
+    """Philox4x32-7 in uint64 arithmetic: the four output words (uint64 arrays holding 32-bit values) of the counters c0 .. c3
+    (broadcast against each other) under the 64-bit key `seed`.  The one copy of the round function: the exploration stream below
+    and the camera streams of tests/_camera_ref.py both draw from it."""
     M = np.uint64(0xFFFFFFFF)
-    q, e, c = np.meshgrid(np.arange(nq, dtype=np.uint64), np.arange(env0, env0 + n_env, dtype=np.uint64),
-                          np.arange(c0, c0 + n_c, dtype=np.uint64), indexing="ij")
-    x = [q.ravel(), e.ravel() & M, c.ravel() & M, np.full(q.size, PURPOSE, dtype=np.uint64)]
+    x = [np.ascontiguousarray(a) & M for a in np.broadcast_arrays(*(np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3)))]
+    seed = int(seed)
     k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
     for _ in range(7):
         p0, p1 = np.uint64(0xD2511F53) * x[0], np.uint64(0xCD9E8D57) * x[2]
         x = [(p1 >> np.uint64(32)) ^ x[1] ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ x[3] ^ k1, p0 & M]
         k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return x
+
+
+def numpy_normals(seed, env0, n_env, c0, n_c, A):
+    """The stream restated: Philox4x32-7 in uint64 arithmetic, Box-Muller in float64.  z[n_env][n_c][A] float64."""
+    nq = (A + 3) // 4
+    q, e, c = np.meshgrid(np.arange(nq, dtype=np.uint64), np.arange(env0, env0 + n_env, dtype=np.uint64),
+                          np.arange(c0, c0 + n_c, dtype=np.uint64), indexing="ij")
+    x = philox4x32_7(q.ravel(), e.ravel(), c.ravel(), PURPOSE, seed)
     u = [((w >> np.uint64(9)).astype(np.float64) + 0.5) / 8388608.0 for w in x]
     z = np.empty((4, q.size))
     for h in range(2):

@@ -1,7 +1,10 @@
 """GPU: the WFS camera model (rlao_amd/csrc/detector.hpp) against the oracle's restatement of OOPAO/Detector.py.
 
 The reference seeds its noise generators from the wall clock (Detector.py:127-130), so noisy frames are comparable in
-distribution only; the deterministic part (QE, saturation, ADC) is compared count for count."""
+distribution only; the deterministic part (QE, saturation, ADC) is compared count for count.
+
+The device's own streams are reproducible, and tests/test_gpu_camera_streams.py holds every camera kernel path and setting to a NumPy
+restatement of them count for count (tests/_camera_ref.py); this module keeps the comparisons with the oracle's sampler."""
 import numpy as np
 import pytest
 

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 from scipy import stats
 
+from _camera_ref import alias_poisson, assert_uniform as _assert_uniform, pit as _pit
+
 FINE, COARSE_STEP, HEADER = 0.25, 32.0, 4
 
 
@@ -62,46 +64,11 @@ def test_tables_reproduce_the_poisson_probabilities(table):
 
 
 def _sample_numpy(t, lam, rs):
-    """The device arithmetic of poisson_alias() / alias_draw() in NumPy (float32 where the kernel is), on the same tables."""
+    """The device arithmetic of poisson_alias() / alias_draw() in NumPy (tests/_camera_ref.py), the three words of every draw from
+    `rs`."""
     lam = np.asarray(lam, dtype=np.float32)
     wf, wr, wc = (rs.randint(0, 2 ** 32, size=lam.shape, dtype=np.uint64) for _ in range(3))
-    c = np.floor(lam * np.float32(1 / 32))
-    r = (lam - np.float32(32) * c).astype(np.float32)
-    j = np.minimum(np.floor(r * np.float32(4)), 127)
-    dl = np.maximum(r - np.float32(0.25) * j, 0).astype(np.float32)
-
-    def draw(row, w):
-        base = t[HEADER + 2 * row].astype(np.int64)
-        d = t[HEADER + 2 * row + 1].astype(np.int64)
-        n, kmin = d & 0xFFFF, d >> 16
-        prod = w * n.astype(np.uint64)
-        cell, frac = (prod >> np.uint64(32)).astype(np.int64), (prod & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        en = t[base + cell].astype(np.int64)
-        return kmin + np.where((frac >> 9) < (en >> 9), cell, en & 511)
-
-    k = draw(j.astype(np.int64), wf) + draw(128 + c.astype(np.int64), wc)
-    u = ((wr >> np.uint64(9)).astype(np.float32) + np.float32(0.5)) * np.float32(1 / 8388608)
-    p = np.exp(-dl).astype(np.float32)
-    cdf = p.copy()
-    for s in range(7):
-        k = k + (u > cdf)
-        p = (p * (dl * np.float32(1.0 / (s + 1)))).astype(np.float32)
-        cdf = (cdf + p).astype(np.float32)
-    return k
-
-
-def _pit(x, lam, rs):
-    """Randomised probability-integral transform: uniform on (0, 1) iff x ~ Poisson(lam), whatever lam each sample has."""
-    return stats.poisson.cdf(x - 1, lam) + rs.uniform(size=np.shape(x)) * stats.poisson.pmf(x, lam)
-
-
-def _assert_uniform(u, what):
-    n = u.size
-    h = np.histogram(u, bins=64, range=(0, 1))[0]
-    chi2 = float(((h - n / 64) ** 2 / (n / 64)).sum())
-    ks = float(stats.kstest(u.ravel(), "uniform").statistic) * np.sqrt(n)
-    assert chi2 < stats.chi2.ppf(1 - 1e-6, 63), (what, chi2)      # 63 dof: 99.9999 % point = 137
-    assert ks < 2.2, (what, ks)                                   # P(sqrt(n) D > 2.2) = 1.2e-4
+    return alias_poisson(t, lam, wf, wr, wc)
 
 
 LAMBDAS = (0.01, 0.2, 0.26, 3.7, 9.99, 31.9, 32.0, 33.3, 100.5, 511.9, 1023.9)
