@@ -307,6 +307,36 @@ typedef struct AoDisturbance {
 } AoDisturbance;
 int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream);   /* NULL cfg: forget it */
 
+/* Replaces: a mis-registered deformable mirror per run (OOPAO/DeformableMirror.py:326-351: the actuator positions from
+ * misReg.shiftX, shiftY, rotationAngle, radialScaling, tangentialScaling; :494-514: the Gaussian widths from the two scalings;
+ * MAIN/OOPAOEnv/OOPAOEnv.py:214-226 feeds param['MisReg_shiftX' | 'MisReg_shiftY' | 'MisReg_rotationAngle'] into the mirror), for
+ * every env of a shard at once: a tolerance study over n_env offsets is one shard and one calibration.
+ * The model: a shift or a scaling along the axes keeps the influence function of actuator (iy, ix) a product
+ * gy[:, iy] (x) gx[:, ix], so the surface of env e stays Gy_e C_e Gx_e^T and only the operand tables differ from env to env.
+ * h_gx, h_gy: [n_env][R][n_act] float64, per env the meaning and element order of AOENV_C_DM_GX / _GY (a two-DM shard: the composite
+ * [gx1 | gx2]).  Each env's pair is written in every layout the shared tables have (rlao_amd/csrc/dm_tables.hpp): gx, gy and the
+ * transpose of gx in the env dtype, and the two float32 matrix-core operand tables, zero padded to R rounded up to 128.  Device
+ * memory of a per-env set: n_env times
+ *     (2 R n_act + (n_act pad 4)(R pad 128)) sizeof(dtype) + 2 (R pad 128) 4 ga_stride sizeof(float),  ga_stride = max(8, n_act / 4 pad 4)
+ * (the transpose, the second term, is kept as the shared one is, though no kernel reads either at present)
+ * -- 64 KB per env at R = 120, n_act = 21 in float32.  Every kernel that forms the DM surface from the factors (the fused step kernel,
+ * the phase kernels of every path, k_dm_rows) offsets its table pointers by env x stride; the stride is 0 while the tables are
+ * shared, and the addresses, loads and results are then those of a shard that never made the call.  Everything that steps or
+ * measures follows without a new argument: aoenv_step, aoenv_measure, aoenv_reset_soft, aoenv_run_integrator, both recorded
+ * rollouts, a disturbance (`seen` goes through the env's own mirror), a delay; aoenv_compute_psf through the phase it reads.  The
+ * reconstructor stays that of the calibrated mirror: that is the experiment.
+ * Both pointers NULL: back to the shared tables (AOENV_C_DM_GX / _GY as uploaded), the per-env ones are freed.
+ * Everything is copied before the call returns; the stream is waited for once, because a step in flight reads the tables in place.
+ * The tables are configuration, as the disturbance is: not loop state, not in the checkpoint buffers; aoenv_reset_envs and
+ * aoenv_new_screens* leave them alone.
+ * Refused, with nothing changed: exactly one of the two pointers null, a non-finite entry, a shard with dm_separable == 0 (a dense
+ * mirror has no factors), an allocation that fails (the message states the bytes).
+ * A rotation or an anamorphosis angle is not a product of two factors and has no entry here.
+ * aoenv_get_dm_env fills h_gx, h_gy [n_env][R][n_act] with the values as held: rounded to the env dtype, widened to float64.
+ * It fails while the tables are shared. */
+int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* stream);
+int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream);
+
 /* Replaces: TimeDelayEnv (MAIN/PO4AO/util_simple.py:25-52, the contract is :46-52: append the action, apply action_buffer[0], drop
  * it), which both trainer mains put around the env with delay = 1 (MAIN/mbrl_main.py:46, MAIN/mbrl_main_network.py:41,
  * MAIN/PO4AO/mbrl_funcsRAZOR.py:32-33), and the action_buffer every gymnasium env of the reference carries (OOPAOEnv_VPG.py:562-566,

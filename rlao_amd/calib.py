@@ -66,6 +66,9 @@ class AOParams:
     nModes: int = 50                     # Zernike modes kept from the M2C (MAIN/OOPAOEnv/OOPAOEnv.py:260)
     nMeasurements: int = 6               # MAIN/OOPAOEnv/OOPAOEnv.py:285
     fov: float = 0.0
+    MisReg_shiftX: float = 0.0           # mis-registration of the (calibrated) mirror [m], MAIN/OOPAOEnv/OOPAOEnv.py:214-226
+    MisReg_shiftY: float = 0.0
+    MisReg_rotationAngle: float = 0.0    # [deg]; only 0 is built: a rotated actuator grid is not a product of two factors
     extra: dict = field(default_factory=dict)
 
     @property
@@ -225,12 +228,53 @@ class AtmosphereTables:
 # ------------------------------------------------------------------------------------------------------
 # Deformable mirror
 # ------------------------------------------------------------------------------------------------------
-class DMTables:
-    """Cartesian Fried-geometry DM with Gaussian influence functions and zero mis-registration
-    (OOPAO/DeformableMirror.py:286-305 valid actuators, :494-514 influence model).  With no rotation /
-    anamorphosis the influence function of actuator (iy, ix) is gy[:, iy] (x) gx[:, ix]."""
+ROTATION_REFUSAL = ("a rotated actuator grid is not a product of two factors gy (x) gx: the separable-DM kernels cannot show it "
+                    "(MisReg_rotationAngle / rotation_angle must be 0)")
 
-    def __init__(self, p: AOParams, pitch: float | None = None, n_subap: int | None = None):
+
+def _dm_axes(p: AOParams, ns: int, shift_x=0, shift_y=0, radial_scaling=0, tangential_scaling=0):
+    """``(pix, centre_x, centre_y, width_x, width_y)`` of a mis-registered Cartesian DM on the pixel grid: the ONE place that holds
+    the reference's mapping of the scalings (``dm_factors`` has the citations) -- positions: tangential along x, radial along y;
+    widths: radial along x, tangential along y."""
+    R, D = p.resolution, p.diameter
+    x = np.linspace(-D / 2, D / 2, ns + 1)
+    pix = np.linspace(0, 1, R) * R
+    width = (R / ns) / np.sqrt(2 * np.log(1.0 / p.mechanicalCoupling))
+    centre_x = R / 2 + (x * (1 + tangential_scaling) - shift_x) * R / D
+    centre_y = R / 2 + (x * (1 + radial_scaling) - shift_y) * R / D
+    return pix, centre_x, centre_y, (1 + radial_scaling) * width, (1 + tangential_scaling) * width
+
+
+def dm_factors(p: AOParams, shift_x=0, shift_y=0, radial_scaling=0, tangential_scaling=0, n_subap: int | None = None,
+               pitch: float | None = None):
+    """The separable influence factors ``(gx, gy)``, float64 ``[R, nAct]`` each, of a Cartesian DM mis-registered by a shift [m]
+    and the two scalings (dimensionless) -- OOPAO/DeformableMirror.py:326-351 (positions) and :485-511 (anamorphosis, widths) at
+    ``anamorphosisAngle = 0`` and ``rotationAngle = 0``, every quirk kept:
+      * ``anamorphosis()`` is called with ``(tangentialScaling, radialScaling)`` in the slots named ``(mRad, mNorm)`` (:331), so the x
+        positions scale by ``1 + tangentialScaling`` and the y positions by ``1 + radialScaling`` (:487-490 at angle 0);
+      * the width along x is ``cx`` with ``1 + radialScaling``, the width along y ``cy`` with ``1 + tangentialScaling`` (:497-498);
+      * the shift is subtracted, ``xIF = x - shiftX`` (:337-338);
+      * ``u0 = R / 2 + xIF R / D`` (:345-346) on the pixel grid ``linspace(0, 1, R) R`` (:502).
+    The influence function of actuator (iy, ix) is ``gy[:, iy] (x) gx[:, ix]`` (:506-510 with theta = 0: b = 0).  ``pitch`` is
+    accepted for symmetry with ``DMTables``; the factors do not depend on it (the width is R / n_subap pixels, :497)."""
+    ns = p.nSubaperture if n_subap is None else int(n_subap)
+    pix, cx, cy, wx, wy = _dm_axes(p, ns, shift_x, shift_y, radial_scaling, tangential_scaling)
+    gx = np.exp(-((pix[:, None] - cx[None, :]) ** 2) / (2 * wx ** 2))     # [R, nAct]
+    gy = np.exp(-((pix[:, None] - cy[None, :]) ** 2) / (2 * wy ** 2))
+    return gx, gy
+
+
+class DMTables:
+    """Cartesian Fried-geometry DM with Gaussian influence functions (OOPAO/DeformableMirror.py:286-305 valid actuators, :494-514
+    influence model), mis-registered by the shifts of the parameter file (``MisReg_shiftX`` / ``MisReg_shiftY``,
+    MAIN/OOPAOEnv/OOPAOEnv.py:214-226) -- this is the mirror the loop is calibrated on; ``shift_x`` ... are added to them.  With no
+    rotation / anamorphosis angle the influence function of actuator (iy, ix) is gy[:, iy] (x) gx[:, ix] (``dm_factors``); a
+    non-zero ``MisReg_rotationAngle`` raises ``NotImplementedError``."""
+
+    def __init__(self, p: AOParams, pitch: float | None = None, n_subap: int | None = None, shift_x=0, shift_y=0,
+                 radial_scaling=0, tangential_scaling=0):
+        if float(p.MisReg_rotationAngle) != 0:
+            raise NotImplementedError(ROTATION_REFUSAL)
         R, D = p.resolution, p.diameter
         ns = p.nSubaperture if n_subap is None else int(n_subap)      # a second DM has its own actuator pitch
         self.nAct = nAct = ns + 1
@@ -243,21 +287,21 @@ class DMTables:
         self.nValidAct = int(self.act_idx.size)
         self.dm_mask = self.validAct.reshape(nAct, nAct)
         self.xvalid, self.yvalid = np.nonzero(self.dm_mask)                 # MAIN/OOPAOEnv/OOPAOEnv.py:231-232
-        centre = R / 2 + x * R / D
-        width = (R / ns) / np.sqrt(2 * np.log(1.0 / p.mechanicalCoupling))
-        pix = np.linspace(0, 1, R) * R
-        self.gx = np.exp(-((pix[:, None] - centre[None, :]) ** 2) / (2 * width ** 2))     # [R, nAct]
-        self.gy = self.gx.copy()
+        self.misreg = dict(shift_x=float(p.MisReg_shiftX) + shift_x, shift_y=float(p.MisReg_shiftY) + shift_y,
+                           radial_scaling=radial_scaling, tangential_scaling=tangential_scaling)
+        self._p, self._ns = p, ns
+        self.gx, self.gy = dm_factors(p, n_subap=ns, pitch=pitch, **self.misreg)     # [R, nAct]
         self._R = R
-        self._centre, self._a, self._pix = centre, 1.0 / (2 * width ** 2), pix
 
     def dense_modes(self) -> np.ndarray:
-        """dm.modes [R*R, nValidAct], evaluated with the reference's own expression (:506-511)."""
-        XX, YY = np.meshgrid(self._pix, self._pix)
-        x0 = self._centre[self.act_idx % self.nAct]
-        y0 = self._centre[self.act_idx // self.nAct]
-        a = self._a
-        return np.exp(-(a * (XX.reshape(-1, 1) - x0[None, :]) ** 2 + a * (YY.reshape(-1, 1) - y0[None, :]) ** 2))
+        """dm.modes [R*R, nValidAct]: the outer products gy[:, iy] (x) gx[:, ix] of ``dm_factors`` as ONE exponential per pixel,
+        the reference's own expression (:506-511 with theta = 0)."""
+        pix, cx, cy, wx, wy = _dm_axes(self._p, self._ns, **self.misreg)
+        ax, ay = 1.0 / (2 * wx ** 2), 1.0 / (2 * wy ** 2)
+        XX, YY = np.meshgrid(pix, pix)
+        x0 = cx[self.act_idx % self.nAct]
+        y0 = cy[self.act_idx // self.nAct]
+        return np.exp(-(ax * (XX.reshape(-1, 1) - x0[None, :]) ** 2 + ay * (YY.reshape(-1, 1) - y0[None, :]) ** 2))
 
 
 class CompositeDM:

@@ -215,6 +215,10 @@ struct PhaseBuffers {
     const float* gxa;      // gx as float32 MFMA operands, ga_index() layout: [Rpad128 / 16][ga_stride / 4][64 lanes][4]
     const float* gya;      // the same for gy
     int ga_stride;         // k steps per lane (n_act / 4 rounded up to a multiple of 4)
+    // per-env mirrors (aoenv_set_dm_env): env e reads gx / gy at + e * g_env and gxa / gya at + e * ga_env (elements); all 0 while
+    // the shard shares one mirror, and the kernels then form the addresses they always did.  gxt_env is the block size of the
+    // per-env gxt tables: like gxt itself it is filled by the host and read by no kernel at present
+    size_t g_env, gxt_env, ga_env;
     const float* s1a;      // [E] x the same layout: Gy C (k_dm_rows), or nullptr: the kernel forms its rows itself
     const int* act_idx;    // [A]
     const uint8_t* pupil;  // [R*R]
@@ -227,8 +231,9 @@ int phase_tiles(int R, int n_act, size_t esz);
 template <typename T>
 int launch_coefs_image(const T* coefs, const int* act_idx, T* img, int n_env, int n_act, int n_valid_act, hipStream_t st);
 // float32, separable DM: Gy C of every env in MFMA operand layout, once per step (see k_dm_rows)
-int launch_dm_rows(const float* coefs, const int* act_idx, const float* gya, float* s1a, int n_env, int R, int n_act, int n_valid_act,
-                   int ga_stride, hipStream_t st);
+// (ga_env: floats between the envs' gya tables, 0 = one table for the shard)
+int launch_dm_rows(const float* coefs, const int* act_idx, const float* gya, size_t ga_env, float* s1a, int n_env, int R, int n_act,
+                   int n_valid_act, int ga_stride, hipStream_t st);
 template <typename T>
 struct KArgs {                 // kernel argument block of the phase kernels
     PhaseArgs pa;
@@ -325,6 +330,7 @@ struct StepArgs {
     const float* amp_pupil;      // [R*R] WFS field amplitude inside the pupil, -1 outside (pupil and amp in one load)
     const float* gxa;            // [128][4][8] gx[x][q + 4 s] at [x][q][s], zero padded: MFMA operands as two 16-byte loads
     const float* gya;            // [128][4][8] gy[y][q + 4 s]
+    size_t ga_env;               // floats between the envs' tables (aoenv_set_dm_env), 0 = one pair for the shard
     DetectorCfg det;             // WFS camera (active = 0: ideal)
     PoissonAlias pa;             // its photon-noise tables (poisson_alias.hpp)
     // ring extrusion whose scatter was deferred to this kernel (add_row part 3, OOPAO/Atmosphere.py:309-310):

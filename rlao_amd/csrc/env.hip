@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "delay.hpp"
+#include "dm_tables.hpp"
 #include "detector.hpp"
 #include "disturb.hpp"
 #include "policy.hpp"
@@ -150,6 +151,16 @@ struct AoEnv {
     float* gxa = nullptr;                   // gx / gy re-laid out as MFMA operand tables (ga_index(), common.hpp), zero padded to Rpad128
     float* gya = nullptr;
     int ga_stride = 8;                      // k steps per (row, q), a multiple of 4 (16-byte loads), >= ceil(nAct / 4)
+    // per-env mirrors (aoenv_set_dm_env): E blocks of every layout of the shared tables (dm_tables.hpp) in ONE allocation of its own
+    // (not in `allocs`: returning to the shared tables frees it); the kernels are handed these pointers and the block sizes as
+    // per-env strides while `on`, the shared tables and stride 0 otherwise
+    struct DmEnv {
+        bool on = false;
+        void* base = nullptr;
+        void *gx = nullptr, *gy = nullptr, *gxt = nullptr;
+        float *gxa = nullptr, *gya = nullptr;
+    } dm_env;
+    DmLayout dm_layout() const { DmLayout l; l.R = R; l.n_act = nAct; l.ga_stride = ga_stride; return l; }
     std::vector<uint8_t> h_pupil;           // host copies, to rebuild amp_pupil
     std::vector<double> h_amp;
     bool amp_pupil_dirty = true;
@@ -580,7 +591,8 @@ int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int sto
     if (env->use_coefs_img && env->c.dm_separable) {               // ELT-size DMs: once per env instead of once per tile
         if constexpr (std::is_same<T, float>::value) {
             if (env->dm_rows)                                       // Gy C on the matrix cores, in operand layout
-                AO_TRY(launch_dm_rows(env->as<float>(env->cmd()), env->act_idx, env->gya, env->dm_rows, env->E, env->R, env->nAct, env->A,
+                AO_TRY(launch_dm_rows(env->as<float>(env->cmd()), env->act_idx, env->dm_env.on ? env->dm_env.gya : env->gya,
+                                      env->dm_env.on ? env->dm_layout().ga_elems() : 0, env->dm_rows, env->E, env->R, env->nAct, env->A,
                                       env->ga_stride, st));
         }
         if (env->coefs_img)
@@ -802,12 +814,17 @@ void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_
     pb.coefs_img = env->use_coefs_img && env->coefs_img ? env->as<T>(env->coefs_img) : nullptr;
     pb.s1a = env->use_coefs_img && env->c.dm_separable ? env->dm_rows : nullptr;
     pb.dm_opd = env->c.dm_separable ? nullptr : env->as<T>(env->dm_opd);
-    pb.gx = env->as<T>(env->gx);
-    pb.gy = env->as<T>(env->gy);
-    pb.gxt = env->as<T>(env->gxt);
-    pb.gxa = env->gxa;
-    pb.gya = env->gya;
+    const AoEnv::DmEnv& de = env->dm_env;                          // every env its own mirror: its tables, a block apart
+    const DmLayout dl = env->dm_layout();
+    pb.gx = env->as<T>(de.on ? de.gx : env->gx);
+    pb.gy = env->as<T>(de.on ? de.gy : env->gy);
+    pb.gxt = env->as<T>(de.on ? de.gxt : env->gxt);
+    pb.gxa = de.on ? de.gxa : env->gxa;
+    pb.gya = de.on ? de.gya : env->gya;
     pb.ga_stride = env->ga_stride;
+    pb.g_env = de.on ? dl.g_elems() : 0;
+    pb.gxt_env = de.on ? dl.gxt_elems() : 0;
+    pb.ga_env = de.on ? dl.ga_elems() : 0;
     pb.act_idx = env->act_idx;
     pb.pupil = env->pupil;
     pb.phase = env->as<T>(env->phase);
@@ -848,8 +865,9 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.fac_m2c_t = env->as<float>(env->fac_m2c_t);
     a.slot_of = env->slot_of;
     a.amp_pupil = env->amp_pupil;
-    a.gxa = env->gxa;
-    a.gya = env->gya;
+    a.gxa = pb.gxa;                                                // (the env's own tables under aoenv_set_dm_env)
+    a.gya = pb.gya;
+    a.ga_env = pb.ga_env;
     if (env->det.active) env->det.frame_counter += 1;              // every measurement is a new frame of the noise streams
     a.det = env->det;
     a.pa = env->alias();
@@ -1182,7 +1200,7 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
     A_((void**)&e->valid2d, (size_t)e->nSub * e->nSub);
     A_((void**)&e->slot_of, (size_t)e->nSub * e->nSub * sizeof(short));
     A_((void**)&e->amp_pupil, R2 * sizeof(float));
-    e->ga_stride = std::max(8, ((cdiv(e->nAct, 4) + 3) / 4) * 4);
+    e->ga_stride = dm_ga_stride(e->nAct);
     A_((void**)&e->gxa, (size_t)(cdiv(e->R, 128) * 128) * 4 * e->ga_stride * sizeof(float));
     A_((void**)&e->gya, (size_t)(cdiv(e->R, 128) * 128) * 4 * e->ga_stride * sizeof(float));
     if (e->A > 1024 && !rc) { rc = alloc_dm_rows(e); e->use_coefs_img = true; }
@@ -1255,6 +1273,7 @@ int aoenv_destroy(AoEnv* env) {
     DeviceGuard ao_device_guard(env->device);
     for (auto& e : env->prof_ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (void* p : env->allocs) (void)hipFree(p);
+    if (env->dm_env.base) (void)hipFree(env->dm_env.base);
     delete env;
     return 0;
 }
@@ -1296,19 +1315,16 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
         case AOENV_C_DM_GY:
             AO_TRY(need((size_t)env->R * env->nAct * 8));
             AO_TRY(upload_real(env, kind == AOENV_C_DM_GX ? env->gx : env->gy, d, (size_t)env->R * env->nAct));
-            {                                                      // MFMA operand layout (float32 kernels): zero padded
-                const int st_ = env->ga_stride;
-                std::vector<float> t((size_t)(cdiv(env->R, 128) * 128) * 4 * st_, 0.f);
-                for (int x = 0; x < env->R; ++x)
-                    for (int k = 0; k < env->nAct; ++k) t[ga_index(x, k, st_)] = (float)d[(size_t)x * env->nAct + k];
+            {                                                      // the other layouts of the table (dm_tables.hpp)
+                const DmLayout dl = env->dm_layout();
+                std::vector<float> t(dl.ga_elems());               // MFMA operand layout (float32 kernels): zero padded
+                dm_fill_ga(dl, d, t.data());
                 AO_HIP(hipMemcpy(kind == AOENV_C_DM_GX ? env->gxa : env->gya, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-            }
-            if (kind == AOENV_C_DM_GX) {
-                const int nap = (env->nAct + 3) & ~3, rp = cdiv(env->R, 128) * 128;
-                std::vector<double> t((size_t)nap * rp, 0.0);
-                for (int x = 0; x < env->R; ++x)
-                    for (int ix = 0; ix < env->nAct; ++ix) t[(size_t)ix * rp + x] = d[(size_t)x * env->nAct + ix];
-                AO_TRY(upload_real(env, env->gxt, t.data(), t.size()));
+                if (kind == AOENV_C_DM_GX) {
+                    std::vector<double> tt(dl.gxt_elems());
+                    dm_fill_gxt<double>(dl, d, tt.data());
+                    AO_TRY(upload_real(env, env->gxt, tt.data(), tt.size()));
+                }
             }
             break;
         case AOENV_C_DM_MODES:
@@ -2079,6 +2095,86 @@ int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream) {
     d.M = M; d.J = J; d.t0 = cfg->t0;
     d.set = true;
     return 0;
+}
+
+// ---- per-env mirrors (dm_tables.hpp) -----------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+template <typename T>
+int set_dm_env_t(AoEnv* env, const double* h_gx, const double* h_gy, hipStream_t st) {
+    const DmLayout dl = env->dm_layout();
+    const size_t E = (size_t)env->E;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t bg = al(E * dl.g_elems() * sizeof(T)), bt = al(E * dl.gxt_elems() * sizeof(T)), ba = al(E * dl.ga_elems() * sizeof(float));
+    const size_t bytes = 2 * bg + bt + 2 * ba;
+    DmHostTables<T> h;
+    dm_relayout<T>(dl, env->E, h_gx, h_gy, h);
+    AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the tables in place
+    AoEnv::DmEnv& de = env->dm_env;
+    if (!de.base) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("aoenv_set_dm_env: no device memory for %zu bytes of per-env DM tables (%d envs x %zu)", bytes, env->E, dl.bytes(sizeof(T)));
+        }
+        char* c = static_cast<char*>(p);
+        de.base = p;
+        de.gx = c;
+        de.gy = c + bg;
+        de.gxt = c + 2 * bg;
+        de.gxa = reinterpret_cast<float*>(c + 2 * bg + bt);
+        de.gya = reinterpret_cast<float*>(c + 2 * bg + bt + ba);
+    }
+    de.on = false;                                                 // (a failed copy leaves no half-written mirror in use)
+    AO_HIP(hipMemcpy(de.gx, h.gx.data(), h.gx.size() * sizeof(T), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(de.gy, h.gy.data(), h.gy.size() * sizeof(T), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(de.gxt, h.gxt.data(), h.gxt.size() * sizeof(T), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(de.gxa, h.gxa.data(), h.gxa.size() * sizeof(float), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(de.gya, h.gya.data(), h.gya.size() * sizeof(float), hipMemcpyHostToDevice));
+    de.on = true;
+    return 0;
+}
+template <typename T>
+int get_dm_env_t(AoEnv* env, double* h_gx, double* h_gy) {
+    const size_t n = (size_t)env->E * env->dm_layout().g_elems();
+    std::vector<T> t(n);
+    const struct { const void* src; double* dst; } both[] = {{env->dm_env.gx, h_gx}, {env->dm_env.gy, h_gy}};
+    for (const auto& b : both) {
+        AO_HIP(hipMemcpy(t.data(), b.src, n * sizeof(T), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) b.dst[i] = (double)t[i];
+    }
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_gx != !h_gy) return fail("aoenv_set_dm_env: one of gx / gy is null (both, or neither for the shared tables)");
+    if (h_gx && !env->c.dm_separable) return fail("aoenv_set_dm_env: this shard's DM is dense (dm_separable == 0): it has no factors");
+    if (!h_gx) {
+        if (env->dm_env.base) {
+            AO_HIP(hipStreamSynchronize(st));
+            (void)hipFree(env->dm_env.base);                       // (waits for the device)
+        }
+        env->dm_env = AoEnv::DmEnv{};
+        return 0;
+    }
+    const size_t n = (size_t)env->E * env->R * env->nAct;
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(h_gx[i])) return fail("aoenv_set_dm_env: gx[%zu] is not finite", i);
+        if (!std::isfinite(h_gy[i])) return fail("aoenv_set_dm_env: gy[%zu] is not finite", i);
+    }
+    return env->c.dtype == AOENV_F32 ? set_dm_env_t<float>(env, h_gx, h_gy, st) : set_dm_env_t<double>(env, h_gx, h_gy, st);
+}
+
+int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_gx || !h_gy) return fail("aoenv_get_dm_env: null destination");
+    if (!env->dm_env.on) return fail("aoenv_get_dm_env: the shard shares one mirror (aoenv_set_dm_env has not been called)");
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return env->c.dtype == AOENV_F32 ? get_dm_env_t<float>(env, h_gx, h_gy) : get_dm_env_t<double>(env, h_gx, h_gy);
 }
 
 // ---- the control delay (delay.hpp) ------------------------------------------------------------------------------------------------

@@ -48,6 +48,8 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
     const int lx = threadIdx.x, ly = threadIdx.y, tid = ly * 64 + lx;
     const size_t pix0 = (size_t)e * R * R;
     const bool separable = (a.pb.dm_opd == nullptr);
+    const T* gx = a.pb.gx + (size_t)e * a.pb.g_env;          // the env's own mirror (aoenv_set_dm_env), stride 0 = the shard's
+    const T* gy = a.pb.gy + (size_t)e * a.pb.g_env;
 
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && a.pa.store_phase) a.pb.wfs_max[e] = (T)0;
 
@@ -64,13 +66,13 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
         // Gx^T of this tile's columns (global reads run along ix then x: contiguous)
         for (int i = tid; i < txe * nA; i += 256) {
             const int x = i / nA, ix = i - x * nA;
-            gxt[ix * TX + x] = a.pb.gx[(size_t)(x0 + x) * nA + ix];
+            gxt[ix * TX + x] = gx[(size_t)(x0 + x) * nA + ix];
         }
         __syncthreads();
         // s1[y][ix] = sum_iy gy[y0 + y][iy] * C[iy][ix]
         for (int i = tid; i < tye * nA; i += 256) {
             const int y = i / nA, ix = i - y * nA;
-            const T* g = a.pb.gy + (size_t)(y0 + y) * nA;
+            const T* g = gy + (size_t)(y0 + y) * nA;
             T acc = (T)0;
             for (int iy = 0; iy < nA; ++iy) acc += g[iy] * cimg[iy * nA + ix];
             s1[y * nA + ix] = acc;
@@ -250,6 +252,8 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
     const int tid = threadIdx.x, lx = tid & 63, ly = tid >> 6;      // ly = wave
     const int lc = lx & 15, lq = lx >> 4;                            // MFMA lane decomposition
     const size_t pix0 = (size_t)e * R * R;
+    const float* gxa = a.pb.gxa + (size_t)e * a.pb.ga_env;           // the env's own mirror (aoenv_set_dm_env), stride 0 = the shard's
+    const float* gya = a.pb.gya + (size_t)e * a.pb.ga_env;
 
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && a.pa.store_phase) a.pb.wfs_max[e] = 0.f;
 
@@ -278,8 +282,8 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
     // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
     // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
     if (!rows_given) {
-        if (nAp <= 32) s1_tiles_mfma<8>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-        else s1_tiles_mfma<32>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
+        if (nAp <= 32) s1_tiles_mfma<8>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
+        else s1_tiles_mfma<32>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
     }
 
     // lane's pixels: sub-tile tt (x = 16 (2 ly + tt) + lc), rows y = 4 lq + r
@@ -373,7 +377,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
         f32x4 dmv = {0.f, 0.f, 0.f, 0.f};
         const float* ap = s1 + lc * SS + lq;                      // A[i = lane & 15][k = lane >> 4]            (LDS)
         // B[k = lane >> 4 + 4 s][j = lane & 15 -> column] = gx[x][k]: the operand table gives a lane its k steps as 16-byte loads
-        const f32x4* bsrc = reinterpret_cast<const f32x4*>(a.pb.gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
+        const f32x4* bsrc = reinterpret_cast<const f32x4*>(gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
         if (rows_given) {
             f32x4 bq[NQ];
 #pragma unroll
@@ -464,6 +468,8 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     const int tid = threadIdx.x, lx = tid & 63, ly = tid >> 6;      // ly = wave
     const int lc = lx & 15, lq = lx >> 4;                            // MFMA lane decomposition
     const size_t pix0 = (size_t)e * R * R;
+    const float* gxa = a.pb.gxa + (size_t)e * a.pb.ga_env;           // the env's own mirror (aoenv_set_dm_env), stride 0 = the shard's
+    const float* gya = a.pb.gya + (size_t)e * a.pb.ga_env;
 
     if (blockIdx.y == 0 && tid == 0 && a.pa.store_phase) a.pb.wfs_max[e] = 0.f;
 
@@ -492,8 +498,8 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
     // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
     if (!rows_given) {
-        if (nAp <= 32) s1_tiles_mfma<8>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-        else s1_tiles_mfma<32>(a.pb.gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
+        if (nAp <= 32) s1_tiles_mfma<8>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
+        else s1_tiles_mfma<32>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
     }
 
     double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
@@ -627,7 +633,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
         // D[x][y] = sum_k gx[x][k] (Gy C)[y][k]: gx is the A operand (i = lane & 15 -> column of the 16-column sub-tile) and the
         // Gy C row the B operand, so that the matrix cores' output layout (rows 4 (lane >> 4) + r, column lane & 15) hands a
         // lane FOUR CONSECUTIVE pixels of ONE row: every global access below is a 16-byte one
-        const f32x4* bsrc = reinterpret_cast<const f32x4*>(a.pb.gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
+        const f32x4* bsrc = reinterpret_cast<const f32x4*>(gxa) + (size_t)((x0 >> 4) + 2 * ly + tt) * nq * 64 + lx;
         if (rows_given) {
             f32x4 bq[NQ];
 #pragma unroll
@@ -749,8 +755,8 @@ __global__ void __launch_bounds__(256) k_coefs_image(const T* __restrict__ coefs
 // is scattered into LDS once, wave w takes the row tiles w and w + 4, all column tiles.
 template <int KS>
 __global__ void __launch_bounds__(256) k_dm_rows(const float* __restrict__ coefs, const int* __restrict__ act_idx,
-                                                 const float* __restrict__ gya, float* __restrict__ s1a, int R, int nA,
-                                                 int n_valid_act, int ga_stride) {
+                                                 const float* __restrict__ gya, size_t ga_env, float* __restrict__ s1a, int R,
+                                                 int nA, int n_valid_act, int ga_stride) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     float* cimg = reinterpret_cast<float*>(lds_raw);         // [nA][nA]
     const int e = blockIdx.y, y0 = 128 * blockIdx.x, Rp = 128 * gridDim.x;
@@ -776,7 +782,7 @@ __global__ void __launch_bounds__(256) k_dm_rows(const float* __restrict__ coefs
     __syncthreads();
     for (int rt = wave; rt < 8; rt += 4) {
         float av[KS];
-        const f32x4* src = reinterpret_cast<const f32x4*>(gya) + (size_t)((y0 >> 4) + rt) * (ga_stride >> 2) * 64 + lx;
+        const f32x4* src = reinterpret_cast<const f32x4*>(gya + (size_t)e * ga_env) + (size_t)((y0 >> 4) + rt) * (ga_stride >> 2) * 64 + lx;
 #pragma unroll
         for (int q4 = 0; q4 < KS / 4; ++q4) {
             const f32x4 t = src[4 * q4 < ga_stride ? 64 * q4 : 0];
@@ -805,14 +811,14 @@ __global__ void __launch_bounds__(256) k_dm_rows(const float* __restrict__ coefs
         }
     }
 }
-int launch_dm_rows(const float* coefs, const int* act_idx, const float* gya, float* s1a, int n_env, int R, int n_act, int n_valid_act,
-                   int ga_stride, hipStream_t st) {
+int launch_dm_rows(const float* coefs, const int* act_idx, const float* gya, size_t ga_env, float* s1a, int n_env, int R, int n_act,
+                   int n_valid_act, int ga_stride, hipStream_t st) {
     const size_t lds = sizeof(float) * (size_t)n_act * n_act;
     dim3 grid(cdiv(R, 128), n_env);
     if (n_act <= 32)
-        hipLaunchKernelGGL(k_dm_rows<8>, grid, dim3(256), lds, st, coefs, act_idx, gya, s1a, R, n_act, n_valid_act, ga_stride);
+        hipLaunchKernelGGL(k_dm_rows<8>, grid, dim3(256), lds, st, coefs, act_idx, gya, ga_env, s1a, R, n_act, n_valid_act, ga_stride);
     else if (n_act <= 128)
-        hipLaunchKernelGGL(k_dm_rows<32>, grid, dim3(256), lds, st, coefs, act_idx, gya, s1a, R, n_act, n_valid_act, ga_stride);
+        hipLaunchKernelGGL(k_dm_rows<32>, grid, dim3(256), lds, st, coefs, act_idx, gya, ga_env, s1a, R, n_act, n_valid_act, ga_stride);
     else
         return -1;
     AO_HIP(hipGetLastError());

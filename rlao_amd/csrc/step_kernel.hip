@@ -124,13 +124,13 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     f32x4s gx_raw[2][2], gy_raw[2];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
-        const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gxa) + (2 * cg + tt) * 2 * 64 + (tid & 63);   // ga_index(), stride 8
+        const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gxa + e * a.ga_env) + (2 * cg + tt) * 2 * 64 + (tid & 63);   // ga_index(), stride 8
         gx_raw[tt][0] = src[0];
         gx_raw[tt][1] = src[64];
     }
     const int rt = w >> 1, ct = w & 1;                           // s1 tile of this wave: rows 16 rt.., command columns 16 ct..
     {
-        const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gya) + rt * 2 * 64 + (tid & 63);   // gy[16 rt + lc][lq + 4 step]
+        const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gya + e * a.ga_env) + rt * 2 * 64 + (tid & 63);   // gy[16 rt + lc][lq + 4 step]
         gy_raw[0] = src[0];
         gy_raw[1] = src[64];
     }

@@ -2,7 +2,7 @@
 
 Episodes are independent, so the only exchange is one all-gather of the per-env episode
 returns / mean Strehl at episode end (RCCL over xGMI via torch.distributed backend "nccl"; "gloo" on CPU
-for the tests).  Per-env settings (``set_wind_per_env``, ``set_r0_per_env``) are local to a shard: each rank passes the values of
+for the tests).  Per-env settings (``set_wind_per_env``, ``set_r0_per_env``, ``set_dm_misregistration``) are local to a shard: each rank passes the values of
 its own envs, ``values[lo:hi]`` of ``shard_bounds``."""
 from __future__ import annotations
 

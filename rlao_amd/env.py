@@ -239,6 +239,43 @@ def _layer_seeds(env_seeds, n_layer: int):
     return per_layer(1), per_layer(1000)
 
 
+MISREG_KEYS = ("shift_x", "shift_y", "radial_scaling", "tangential_scaling")
+
+
+def resolve_dm_misregistration(values: dict, env_ids, n_envs: int, current) -> dict:
+    """The mis-registration of every env after a ``set_dm_misregistration`` call: a dict of four ``[n_envs]`` float64 arrays
+    (``MISREG_KEYS``).  ``values``: the four arguments of the call, each a scalar or an array of length ``n_envs`` (with
+    ``env_ids``, anything ``normalize_env_ids`` takes: ``len(env_ids)``, in the order of ``env_ids``, a mask ascending).
+    ``current``: the dict in force, or None (every env the calibrated mirror: zeros).  Envs not listed keep what they have.  Raises
+    ``ValueError`` for unknown keys, wrong shapes, non-numeric or non-finite values and a scaling at or below -1 (a mirror of
+    zero or negative size).  Pure host code."""
+    n_envs = int(n_envs)
+    unknown = set(values) - set(MISREG_KEYS)
+    if unknown:
+        raise ValueError(f"unknown mis-registration parameter(s) {sorted(unknown)}")
+    if env_ids is None:
+        rows = np.arange(n_envs)
+    else:
+        _, rows = normalize_env_ids(env_ids, n_envs, return_order=True)
+    out = {k: (np.zeros(n_envs) if current is None else np.array(current[k], dtype=np.float64)) for k in MISREG_KEYS}
+    for k in MISREG_KEYS:
+        v = values.get(k, 0)
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        try:
+            v = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{k} must be numeric") from None
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != len(rows)):
+            raise ValueError(f"{k} must be a scalar or have shape ({len(rows)},), got {v.shape}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"{k} must be finite")
+        if k.endswith("scaling") and (v <= -1).any():
+            raise ValueError(f"{k} must be above -1")
+        out[k][rows] = v
+    return out
+
+
 class Shard:
     """One AoEnv handle of libaoenv (a shard of independent loops on one GPU)."""
 
@@ -378,6 +415,23 @@ class Shard:
         L.check(self.lib.aoenv_get_r0_env(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # per-env mirrors: gx, gy [n_env][R][n_act] float64 (both None: the shared tables again)
+    def set_dm_env(self, gx, gy, stream=0):
+        if gx is None and gy is None:
+            L.check(self.lib.aoenv_set_dm_env(self.h, None, None, C.c_void_p(stream)))
+            return
+        shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.n_act)
+        a, b = (np.ascontiguousarray(t, dtype=np.float64) for t in (gx, gy))
+        if a.shape != shape or b.shape != shape:
+            raise ValueError(f"per-env DM tables must have shape {shape}")
+        L.check(self.lib.aoenv_set_dm_env(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+
+    def get_dm_env(self, stream=0):
+        shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.n_act)
+        gx, gy = np.zeros(shape), np.zeros(shape)
+        L.check(self.lib.aoenv_get_dm_env(self.h, gx.ctypes.data_as(C.c_void_p), gy.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        return gx, gy
+
 
 # ----------------------------------------------------------------------------------------------------
 # reach-through proxies (only the uses listed in SURVEY.md 8b)
@@ -505,6 +559,14 @@ class _DmProxy:
     @property
     def modes(self):
         return self._e._dm_tables.dense_modes()
+
+    def factors_per_env(self):
+        """``(gx, gy)`` of every env as the library holds them (``aoenv_get_dm_env``): float64 ``[n_envs, R, nAct]``, the uploaded
+        values rounded to the env dtype; None while the envs share the calibrated mirror."""
+        e = self._e
+        if not e._dm_per_env:
+            return None
+        return e._shard.get_dm_env(e._stream())
 
 
 class _Cam:
@@ -688,6 +750,8 @@ class BatchedAOEnv:
         self._wind_pixels = 1                                      # ceiling of the per-env winds [px / frame] (set_wind_ceiling)
         self._r0_env = None                                        # [n_envs] Fried parameters once per-env r0 is set
         self._disturb = None                                       # resolve_disturbance()'s arrays while a disturbance is set
+        self._dm_per_env = False                                   # every env its own mirror (set_dm_tables_per_env / set_dm_misregistration)
+        self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
 
     # -- construction --------------------------------------------------------------------------------
     def set_params_file(self, param_file, oopao_path):
@@ -773,6 +837,7 @@ class BatchedAOEnv:
         self._r0_env = self._wind_env = self._disturb = None         # a new shard: one r0, one wind, the shared clock, no disturbance
         self._per_env_clock = False
         self._wind_pixels = 1
+        self._dm_per_env, self._dm_misreg = False, None              # ... and one mirror, the calibrated one
         sh = self._shard
         at = self._atm_tables
         sh.upload_ring_tables(at)
@@ -1033,6 +1098,97 @@ class BatchedAOEnv:
         if self._disturb is None:
             return np.zeros((self.n_envs, self.nValidAct))
         return disturbance_value(self._disturb, i)
+
+    # -- every env its own mirror (aoenv_set_dm_env) ---------------------------------------------------------------------------
+    def _dm_factors_of(self, m: dict):
+        """(gx, gy) [R, nAct] of the calibrated mirror mis-registered by ``m`` on top of its own ``MisReg_*`` (both mirrors of a
+        two-DM env alike)."""
+        dmt, p = self._dm_tables, self.param
+        parts = [dmt.dm1, dmt.dm2] if hasattr(dmt, "dm2") else [dmt]
+        kw = [dict(d.misreg) for d in parts]
+        for k_ in kw:
+            for key, v in m.items():
+                k_[key] = k_[key] + float(v)
+        fac = [calib.dm_factors(p, n_subap=d.nAct - 1, **k_) for d, k_ in zip(parts, kw)]
+        return np.hstack([f[0] for f in fac]), np.hstack([f[1] for f in fac])
+
+    def set_dm_misregistration(self, shift_x=0, shift_y=0, radial_scaling=0, tangential_scaling=0, env_ids=None, rotation_angle=0):
+        """Every env its own mis-registered mirror (OOPAO/DeformableMirror.py:326-351, 494-514): ``shift_x`` / ``shift_y`` [m] and
+        ``radial_scaling`` / ``tangential_scaling`` (dimensionless), scalars or arrays ``[n_envs]`` (with ``env_ids``, a list or a
+        mask: ``[len(env_ids)]`` in that order).  The values are RELATIVE TO THE CALIBRATED MIRROR, i.e. added to its ``MisReg_*``
+        parameters, and absolute per env: a call replaces the listed envs' four values (an argument left out is 0), envs not
+        listed keep what they have.  The reconstructor, the modal basis and the calibration stay those of the calibrated mirror:
+        env e then runs like a loop whose mirror moved after calibration -- a shift-tolerance sweep is one shard and one
+        calibration.  A two-DM env applies the values to both mirrors.  ``step``, ``measure``, ``reset_soft``, ``run_integrator``,
+        both rollouts, a disturbance and a delay all see the env's own mirror (``aoenv_set_dm_env``); ``reset_envs`` and new
+        screens leave it in place.  ``rotation_angle`` exists only to say why it is not built: a non-zero value raises
+        ``NotImplementedError`` -- a rotated actuator grid is not a product of two factors.  Bad arguments raise before anything
+        is touched.  Not part of ``get_state``: after ``set_state`` call this again."""
+        if np.any(np.asarray(rotation_angle, dtype=np.float64) != 0):
+            raise NotImplementedError(calib.ROTATION_REFUSAL)
+        if self._dm_per_env and self._dm_misreg is None and env_ids is not None:
+            raise ValueError("arbitrary per-env tables are in force (set_dm_tables_per_env): pass every env, or clear_dm_per_env() first")
+        full = resolve_dm_misregistration(dict(shift_x=shift_x, shift_y=shift_y, radial_scaling=radial_scaling,
+                                               tangential_scaling=tangential_scaling), env_ids, self.n_envs, self._dm_misreg)
+        cache = {}
+        pairs = []
+        for e in range(self.n_envs):
+            key = tuple(float(full[k][e]) for k in MISREG_KEYS)
+            if key not in cache:
+                cache[key] = self._dm_factors_of(dict(zip(MISREG_KEYS, key)))
+            pairs.append(cache[key])
+        self._shard.set_dm_env(np.stack([g[0] for g in pairs]), np.stack([g[1] for g in pairs]), self._stream())
+        self._dm_per_env, self._dm_misreg = True, full
+
+    def set_dm_tables_per_env(self, gx, gy, env_ids=None):
+        """The general form: any separable mirror per env.  ``gx``, ``gy``: float64 ``[n_envs, R, nAct]`` (with ``env_ids``:
+        ``[len(env_ids), R, nAct]`` in that order, the other envs keeping what they have -- the calibrated mirror if none yet),
+        the meaning of ``calib.DMTables.gx`` / ``gy`` (a two-DM env: the composite ``[gx1 | gx2]``).  A dead actuator is a zero
+        column, an actuator gain a scaled one.  ``dm_misregistration`` is None from then on.  Bad arguments raise before anything is
+        touched.  Not part of ``get_state``."""
+        R, nA = self.R, self.nActuator
+        if env_ids is None:
+            rows = np.arange(self.n_envs)
+        else:
+            _, rows = normalize_env_ids(env_ids, self.n_envs, return_order=True)
+        tabs = []
+        for name, t in (("gx", gx), ("gy", gy)):
+            if hasattr(t, "detach"):
+                t = t.detach().cpu().numpy()
+            try:
+                t = np.asarray(t, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be numeric") from None
+            if t.shape != (len(rows), R, nA):
+                raise ValueError(f"{name} must have shape ({len(rows)}, {R}, {nA}), got {t.shape}")
+            if not np.isfinite(t).all():
+                raise ValueError(f"{name} must be finite")
+            tabs.append(t)
+        if len(rows) == self.n_envs:
+            full = [np.empty((self.n_envs, R, nA)) for _ in tabs]
+        elif self._dm_per_env:
+            full = list(self._shard.get_dm_env(self._stream()))     # (values as held: a second rounding to the env dtype changes nothing)
+        else:
+            full = [np.tile(np.asarray(t, dtype=np.float64), (self.n_envs, 1, 1)) for t in (self._dm_tables.gx, self._dm_tables.gy)]
+        for f, t in zip(full, tabs):
+            f[rows] = t
+        self._shard.set_dm_env(full[0], full[1], self._stream())
+        self._dm_per_env, self._dm_misreg = True, None
+
+    def clear_dm_per_env(self):
+        """Every env the calibrated mirror again: every call does exactly what it did before the per-env tables were set."""
+        self._shard.set_dm_env(None, None, self._stream())
+        self._dm_per_env, self._dm_misreg = False, None
+
+    @property
+    def dm_misregistration(self):
+        """``dict(shift_x, shift_y, radial_scaling, tangential_scaling)`` of ``[n_envs]`` float64 arrays, relative to the calibrated
+        mirror (zeros while the envs share it); None once arbitrary tables were set (``set_dm_tables_per_env``)."""
+        if self._dm_per_env and self._dm_misreg is None:
+            return None
+        if self._dm_misreg is None:
+            return {k: np.zeros(self.n_envs) for k in MISREG_KEYS}
+        return {k: v.copy() for k, v in self._dm_misreg.items()}
 
     # -- the control delay inside the library (TimeDelayEnv, MAIN/PO4AO/util_simple.py:25-52) ----------------------------------
     def set_delay(self, d: int):
@@ -1401,7 +1557,8 @@ class BatchedAOEnv:
     # -- checkpoint / resume (env state = screens, sub-pixel accumulators, ring RNG, dm coefs) --------
     def get_state(self) -> dict:
         """Everything the next ``step`` depends on, as host arrays: restoring it with ``set_state`` (same geometry, same
-        n_envs) continues the episode bit for bit."""
+        n_envs) continues the episode bit for bit.  Configuration a caller restores itself, because it is not loop state: the
+        disturbance (``set_disturbance``) and the per-env mirrors (``set_dm_misregistration`` / ``set_dm_tables_per_env``)."""
         sh, p, at = self._shard, self.param, self._atm_tables
         st = self._stream()
         d = self.delay

@@ -65,6 +65,19 @@ class TorchWrapper:
     def reset_envs(self, env_ids, seed=None, r0=None):
         return _torch().as_tensor(_reset_envs(self._env, env_ids, seed, r0), dtype=_torch().float32)
 
+    def set_dm_misregistration(self, *args, **kw):
+        return self._env.set_dm_misregistration(*args, **kw)
+
+    def set_dm_tables_per_env(self, gx, gy, env_ids=None):
+        return self._env.set_dm_tables_per_env(gx, gy, env_ids)
+
+    def clear_dm_per_env(self):
+        return self._env.clear_dm_per_env()
+
+    @property
+    def dm_misregistration(self):
+        return self._env.dm_misregistration
+
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
 
@@ -128,6 +141,19 @@ class TimeDelayEnv:
         obs = _reset_envs(self._env, env_ids, seed, r0)
         self.action_buffer = _with_rows_cleared(self.action_buffer, rows)
         return obs
+
+    def set_dm_misregistration(self, *args, **kw):
+        return self._env.set_dm_misregistration(*args, **kw)
+
+    def set_dm_tables_per_env(self, gx, gy, env_ids=None):
+        return self._env.set_dm_tables_per_env(gx, gy, env_ids)
+
+    def clear_dm_per_env(self):
+        return self._env.clear_dm_per_env()
+
+    @property
+    def dm_misregistration(self):
+        return self._env.dm_misregistration
 
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
@@ -249,6 +275,19 @@ class HistoryEnv:
         self.t = 0
         self._push(obs)
         return self._out(), {}
+
+    def set_dm_misregistration(self, *args, **kw):
+        return self._env.set_dm_misregistration(*args, **kw)
+
+    def set_dm_tables_per_env(self, gx, gy, env_ids=None):
+        return self._env.set_dm_tables_per_env(gx, gy, env_ids)
+
+    def clear_dm_per_env(self):
+        return self._env.clear_dm_per_env()
+
+    @property
+    def dm_misregistration(self):
+        return self._env.dm_misregistration
 
     def set_r0_per_env(self, r0, env_ids=None):
         """Every env its own Fried parameter (``BatchedAOEnv.set_r0_per_env``); histories and delayed actions go on."""
