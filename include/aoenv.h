@@ -368,6 +368,65 @@ int aoenv_get_delay(AoEnv* env, int* delay);
 int aoenv_get_delay_line(AoEnv* env, void* h_dst, size_t bytes, void* stream);
 int aoenv_set_delay_line(AoEnv* env, const void* h_src, size_t bytes, void* stream);
 
+/* Replaces: the modal environments of the reference (MAIN/OOPAOEnv/modalAOEnv.py, modalAOSinEnv.py, OOPAOEnvModal.py, driven by the
+ * trainers under MAIN/RL/ and MAIN/VPG/), whose action is a vector of nModes modal coefficients and whose observation is the modal
+ * reconstruction:
+ *     dm.coefs = dm_prev * leak + (M2C_tt @ a) * 1e-6                    (modalAOEnv.py:150-157)
+ *     obs = -(reconstructor_tt @ wfs.signal) * 1e6                       (:165-171; reconstructor_tt = CalibrationVault(D @ M2C[:, :nModes]).M,
+ *                                                                         :410, 447-449)
+ *     reward = -||obs||^2                                                (:190)
+ * as a second surface BESIDE the actuator images of aoenv_step: nothing of the zonal calls changes.  The model is
+ * rlao_amd/csrc/modal.hpp.  With K modes, A valid actuators and T the env dtype:
+ *     expansion   img[e][act_px[k]] = sum_m m2c[k][m] a[e][m]    micrometres of command; an fma chain in T over m in index order; every
+ *                                                                pixel that is no actuator is 0 (vec_to_img); the bits depend on
+ *                                                                neither the shard size nor the env's place in it
+ *     projection  o[e][m] = -1e6 sum_{j < n_signal} cm[m][j] signal[e][j],   reward[e] = -sum_m o[e][m]^2 (summed in float64)
+ *     integrator  a[e][m] = g[e][m] * o_prev[e][m]               one multiply in T
+ * aoenv_set_modal hands over the basis: both tables are converted to the env dtype (m2c is kept transposed, [K][A]) and the internal
+ * action image [n_env][nAct^2] and the modal scratch are allocated; everything is copied before the call returns and the stream is
+ * waited for once.  A NULL cfg forgets the basis and the gains and frees all of it.  Like the disturbance, the basis is
+ * configuration: it is NOT loop state, it is in no checkpoint buffer, and a caller that restores a state sets it again.  A new basis
+ * forgets the gains of the previous one.  Refused, with nothing changed: n_modes outside [1, A], a null table, a non-finite entry. */
+typedef struct AoModal {
+    int32_t n_modes;               /* K in [1, A] */
+    const double* h_m2c;           /* [A][K] metres of command per unit coefficient BEFORE the step's 1e-6 (M2C_CL[:, :K]) */
+    const double* h_cm;            /* [K][n_signal] modal command matrix (calib_tt.M) */
+} AoModal;
+int aoenv_set_modal(AoEnv* env, const AoModal* cfg, void* stream);
+/* The gains of the modal integrator: h_gain [K], or [n_env][K] with per_env != 0 (a gain sweep is then ONE shard; an env whose gains
+ * are 0 runs open loop).  Needs a basis.  The stream is waited for once.  Refused, with nothing changed: no basis, a null pointer,
+ * a non-finite or negative entry. */
+int aoenv_set_modal_gain(AoEnv* env, const double* h_gain, int per_env, void* stream);
+/* aoenv_reset_soft (a measurement's reconstruction: no disturbance, the delay line left alone) followed by the projection:
+ * d_obs [n_env][K].  The zonal observation goes to internal scratch. */
+int aoenv_reset_soft_modal(AoEnv* env, void* d_obs, void* stream);
+/* env.step(action) of the modal envs (modalAOEnv.py:139-200).  d_action [n_env][K] modal coefficients, d_obs [n_env][K] out,
+ * d_reward [n_env] out: -||o||^2 (may be NULL); d_frame / d_strehl as in aoenv_step.
+ * One launch in front of the step forms the action image (k_modal_action) -- under a control delay straight into the delay line's
+ * write slot, in place of the copy aoenv_step makes, otherwise into the internal image; the caller's tensor may be reused at once.
+ * The step is then EXACTLY the explicit-action step of aoenv_step on that image: the same order of effects (the atmosphere
+ * advances, the sensor sees the command latched by the previous call, then the command is updated), the same telemetry,
+ * disturbance, delay and per-env mirror, fused or batched as aoenv_step would run it; d_strehl is the step's own.  The zonal
+ * observation the step produces goes to internal scratch.  One launch behind the step writes d_obs and d_reward (two launches on
+ * the GEMM path of the projection, taken above a size threshold or with AOENV_PATH_MODAL_GEMM); the return accumulator, if
+ * attached, receives THIS reward, not the zonal one.
+ * Order of effects against the reference: modalAOEnv.step updates the command, measures, then advances the atmosphere (:150-200)
+ * with an action_buffer of d entries; the library advances, measures the command of the previous call, then updates.  The loop
+ * latency is the same when aoenv_set_delay is d - 1: the reference's default d = 1 is delay 0 here.  The only difference is that
+ * the reference's step 0 measures the frame of reset a second time.  (INTEGRATION.md works this through.)
+ * aoenv_get_delay_line / aoenv_set_delay_line keep returning IMAGES: the line holds expanded actions.  aoenv_run_rollout,
+ * aoenv_run_policy_rollout and the policy stay zonal.
+ * Refused: no basis, a null action / obs, a frame index outside [0, n_loop), missing constants. */
+int aoenv_step_modal(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
+                     void* stream);
+/* The modal integrator kept on the device, the baseline a learned modal controller is compared with: n_steps iterations of
+ * a = g * o;  o, reward, strehl = step_modal(i0 + k, a), with the gain multiply fused into the expansion launch.  d_obs
+ * [n_env][K] is in/out.  Bit for bit what n_steps calls of aoenv_step_modal give on a = g * o formed by the caller in the env
+ * dtype.  Needs aoenv_set_modal_gain.  Only the last step's frame and residual phase can be read afterwards, as after
+ * aoenv_run_integrator. */
+int aoenv_run_integrator_modal(AoEnv* env, int i0, int n_steps, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
+                               void* stream);
+
 /* Replaces: the exploration episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89), kept on the device and recorded:
  *     action = gain * obs + env.sample_noise(sigma);  next_obs, _, reward, strehl, done, _ = env.step(i, action)
  * for the frames [i0, i0 + n_steps), every observation, action, reward and Strehl ratio written into the caller's trajectory buffers
@@ -522,14 +581,19 @@ enum AoOption {
                                  lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
                                  whose winds stay below one pixel per frame nothing: the same launches */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 also keeps the shard off the fused step kernel; other bits are rejected */
+                                 other than AOENV_PATH_MODAL_GEMM also keeps the shard off the fused step kernel; other bits are
+                                 rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
 enum AoPath {
     AOENV_PATH_PHASE_DWORD = 256,      /* float32 phase kernel with dword accesses instead of the 16-byte one (R % 4 == 0) */
     AOENV_PATH_GENERIC = 512,          /* the Stockham Pyramid passes at nRes 528 / 288, the tiled 16-byte phase kernel instead of its
                                           one-layer band form */
-    AOENV_PATH_PYR_ROUND_ROBIN = 1024  /* nRes 528 / 288 Pyramid column pass: blocks dealt round-robin over the XCDs */
+    AOENV_PATH_PYR_ROUND_ROBIN = 1024, /* nRes 528 / 288 Pyramid column pass: blocks dealt round-robin over the XCDs */
+    AOENV_PATH_MODAL_GEMM = 2048       /* the projection of the modal surface (aoenv_step_modal) as a batched GEMM plus a finish kernel
+                                          whatever its size, instead of the per-env kernel below the threshold.  It touches nothing
+                                          inside the step, so unlike the other bits it leaves the shard on the fused step kernel: the
+                                          loop state is the same bit for bit, only the order of the projection's sum differs */
 };
 int aoenv_set_option(AoEnv* env, int option, int value);
 

@@ -25,7 +25,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
 OPT_FORCE_PATH = 99
 MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
-PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN = 256, 512, 1024
+PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM = 256, 512, 1024, 2048
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
                 "gemm_recon", "recon_finish", "pyramid", "sh_tail", "env_step", "detector")
 
@@ -61,6 +61,10 @@ class AoDisturbance(C.Structure):
         (n, C.c_void_p) for n in ("h_modes", "h_amp", "h_freq", "h_phase")]
 
 
+class AoModal(C.Structure):
+    _fields_ = [("n_modes", C.c_int32), ("h_m2c", C.c_void_p), ("h_cm", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "aoenv_last_error": (C.c_char_p, []),
@@ -87,6 +91,13 @@ EXPORTS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_noise_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_set_disturbance": (C.c_int, [C.c_void_p, C.POINTER(AoDisturbance), C.c_void_p]),
+    "aoenv_set_modal": (C.c_int, [C.c_void_p, C.POINTER(AoModal), C.c_void_p]),
+    "aoenv_set_modal_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "aoenv_reset_soft_modal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_step_modal": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "aoenv_run_integrator_modal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "aoenv_set_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_delay": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

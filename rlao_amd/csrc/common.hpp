@@ -395,6 +395,41 @@ int launch_delay_refill(T* ring, size_t slot_stride, int n_slots, int first_slot
 template <typename T>
 int launch_delay_zero_rows(T* ring, size_t slot_stride, int n_slots, const int* env_idx, int n_idx, int img, hipStream_t st);
 
+// the modal control surface of aoenv_set_modal (modal_kernels.hip; the model and the summation orders are modal.hpp)
+// action: image[e][act_idx[k]] = sum_m m2c_t[m][k] c[e][m], c = coef or gain * coef; every other pixel 0.  `image` is [E][img] from
+// any base: the internal image, or the delay line's write slot
+template <typename T>
+struct ModalActionArgs {
+    const T* m2c_t;        // [K][A] M2C transposed
+    const int* act_idx;    // [A] pixel of actuator k (AOENV_C_ACT_IDX)
+    const T* coef;         // [E][K] the caller's action, or the previous observation when `gain` is set
+    const T* gain;         // null, [K] (gain_env == 0) or [E][K] (gain_env == K)
+    size_t gain_env;
+    T* image;
+    int n_modes, n_valid_act, img;
+};
+template <typename T>
+int launch_modal_action(const ModalActionArgs<T>& a, int n_env, hipStream_t st);
+// projection: obs[e][m] = -1e6 sum_j cm[m][j] signal[e][j], reward[e] = -sum_m obs^2 (also added to ret[e]); reward / ret may be null.
+// launch_modal_obs forms the products itself (one workgroup per env; it needs modal_obs_fits), launch_modal_finish takes them from
+// `slabs` [splits][E][K], the output of a batched GEMM
+template <typename T>
+struct ModalObsArgs {
+    const T* cm;           // [K][n_signal]
+    const T* signal;       // [E][n_signal]
+    const T* slabs;
+    int splits;
+    T* obs;                // [E][K]
+    T* reward;             // [E]
+    T* ret;                // [E]
+    int n_modes, n_signal;
+};
+bool modal_obs_fits(int n_modes, int n_signal, size_t esz);
+template <typename T>
+int launch_modal_obs(const ModalObsArgs<T>& a, int n_env, hipStream_t st);
+template <typename T>
+int launch_modal_finish(const ModalObsArgs<T>& a, int n_env, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

@@ -13,6 +13,7 @@
 #include "dm_tables.hpp"
 #include "detector.hpp"
 #include "disturb.hpp"
+#include "modal.hpp"
 #include "policy.hpp"
 #include "sh_device.hpp"
 
@@ -134,6 +135,21 @@ struct AoEnv {
     void* delay_ring = nullptr;
     size_t delay_stride = 0;                // elements between slots
     void* delay_slot(int slot) const { return static_cast<char*>(delay_ring) + (size_t)slot * delay_stride * esz; }
+    // modal control surface (aoenv_set_modal, modal.hpp): configuration like the disturbance, in ONE allocation of its own (not in
+    // `allocs`: a NULL basis frees it)
+    struct Modal {
+        bool set = false, have_gain = false;
+        int K = 0;
+        size_t gain_env = 0;                // 0: one gain row for every env, K: a row per env
+        void* base = nullptr;
+        void* m2c_t = nullptr;              // [K][A] M2C transposed
+        void* cm = nullptr;                 // [K][nSig] modal command matrix
+        void* gain = nullptr;               // [E][K] (the first row alone when gain_env == 0)
+        void* image = nullptr;              // [E][nAct^2] the expanded action of a step without delay
+        void* zobs = nullptr;               // [E][nAct^2] the zonal observation the step kernel writes
+        void* zscal = nullptr;              // [2][E] its reward, and a Strehl row nobody asked for
+        void* slabs = nullptr;              // [splits][E][K] products of the GEMM path
+    } modal;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -780,7 +796,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && env->force_path == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~AOENV_PATH_MODAL_GEMM) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -1002,6 +1018,89 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
         AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                               hipMemcpyDeviceToDevice, st));
     return 0;
+}
+
+// ---- the modal control surface (modal.hpp, modal_kernels.hip) ---------------------------------------------------------------------
+// K n_signal above which the projection leaves the per-env kernel (every env re-reads cm from L2, every lane runs a chain of
+// n_signal / 64 dependent fmas) for the batched GEMM plus the finish kernel.  profiles/modal_timing.json ("threshold"), measured by
+// scripts/time_modal.py: at the C2 shape (256 envs, 632 slopes) the per-env kernel wins up to K = 50 (31 600: 7.5 us against 10.1)
+// and loses from K = 100 (63 200: 11.4 against 10.2), the lines cross near 53 000; at the C4 shape (512 envs, 10 048 slopes) the
+// GEMM path wins at every K measured from 5 (50 240: 55 us against 32) to 300 (3 014 400: 819 us against 61).  The macro is for
+// that script's A/B build alone, which times the per-env kernel above the threshold too (make FLAGS_env=-D..., AOENV_LIB).
+#ifndef AOENV_MODAL_GEMM_THRESHOLD
+#define AOENV_MODAL_GEMM_THRESHOLD ((size_t)40000)
+#endif
+constexpr size_t kModalGemmThreshold = AOENV_MODAL_GEMM_THRESHOLD;
+
+// o = -1e6 cm signal and the reward from AOENV_B_SIGNAL as it stands; `ret` is the return accumulator to add the reward to, or null
+template <typename T>
+int modal_project(AoEnv* env, void* d_obs, void* d_reward, void* ret, hipStream_t st) {
+    const AoEnv::Modal& mo = env->modal;
+    ModalObsArgs<T> a{};
+    a.cm = env->as<T>(mo.cm);
+    a.signal = env->as<T>(env->signal);
+    a.obs = static_cast<T*>(d_obs);
+    a.reward = static_cast<T*>(d_reward);
+    a.ret = static_cast<T*>(ret);
+    a.n_modes = mo.K;
+    a.n_signal = env->nSig;
+    const bool gemm = (env->force_path & AOENV_PATH_MODAL_GEMM) || (size_t)mo.K * env->nSig > kModalGemmThreshold ||
+                      !modal_obs_fits(mo.K, env->nSig, sizeof(T));
+    if (!gemm) return launch_modal_obs<T>(a, env->E, st);
+    int splits = 1;
+    AO_TRY(gemm_dispatch<T>(env, a.signal, a.cm, env->as<T>(mo.slabs), env->E, mo.K, env->nSig, &splits, st));
+    a.slabs = env->as<T>(mo.slabs);
+    a.splits = splits;
+    return launch_modal_finish<T>(a, env->E, st);
+}
+
+// for the duration of a modal step the return accumulator is detached from the step kernel -- it receives the modal reward from the
+// projection instead -- and is back in place whichever way the scope is left
+struct DetachedReturn {
+    AoEnv* env;
+    void* ret;
+    explicit DetachedReturn(AoEnv* e) : env(e), ret(e->ret_acc) { e->ret_acc = nullptr; }
+    ~DetachedReturn() { env->ret_acc = ret; }
+    DetachedReturn(const DetachedReturn&) = delete;
+    DetachedReturn& operator=(const DetachedReturn&) = delete;
+};
+
+// One modal step: the action image from d_coef (the caller's coefficients, or with use_gain the previous observation times the
+// gains) in one launch -- under a delay into the line's write slot, where aoenv_step would copy the caller's image -- then the
+// explicit-action step of aoenv_step on it, then the projection.  The return accumulator is detached for the step itself: it
+// receives the modal reward.
+template <typename T>
+int step_modal_t(AoEnv* env, int i, const void* d_coef, bool use_gain, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
+                 bool observable, hipStream_t st) {
+    AoEnv::Modal& mo = env->modal;
+    ModalActionArgs<T> a{};
+    a.m2c_t = env->as<T>(mo.m2c_t);
+    a.act_idx = env->act_idx;
+    a.coef = static_cast<const T*>(d_coef);
+    a.gain = use_gain ? env->as<T>(mo.gain) : nullptr;
+    a.gain_env = mo.gain_env;
+    a.n_modes = mo.K;
+    a.n_valid_act = env->A;
+    a.img = env->nAct * env->nAct;
+    const bool delayed = env->delay.d > 0;
+    a.image = static_cast<T*>(delayed ? env->delay_slot(delay_write_slot(env->delay)) : mo.image);
+    const void* applied = delayed ? env->delay_slot(delay_apply_slot(env->delay)) : mo.image;
+    AO_TRY(launch_modal_action<T>(a, env->E, st));
+    T* zs = env->as<T>(mo.zscal);
+    void* ret = nullptr;
+    {
+        DetachedReturn detached(env);
+        ret = detached.ret;
+        AO_TRY(step_t<T>(env, i, applied, mo.zobs, d_frame, zs, d_strehl ? d_strehl : zs + env->E, 0.0, observable, st));
+    }
+    if (delayed) env->delay = delay_after(env->delay, 1);
+    return modal_project<T>(env, d_obs, d_reward, ret, st);
+}
+
+template <typename T>
+int reset_soft_modal_t(AoEnv* env, void* d_obs, hipStream_t st) {
+    AO_TRY(run_recon<T>(env, nullptr, env->as<T>(env->modal.zobs), nullptr, nullptr, -1, 0, 0.0, st));
+    return modal_project<T>(env, d_obs, nullptr, nullptr, st);
 }
 
 struct BufInfo {
@@ -1274,6 +1373,7 @@ int aoenv_destroy(AoEnv* env) {
     for (auto& e : env->prof_ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (void* p : env->allocs) (void)hipFree(p);
     if (env->dm_env.base) (void)hipFree(env->dm_env.base);
+    if (env->modal.base) (void)hipFree(env->modal.base);
     delete env;
     return 0;
 }
@@ -2177,6 +2277,105 @@ int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
     return env->c.dtype == AOENV_F32 ? get_dm_env_t<float>(env, h_gx, h_gy) : get_dm_env_t<double>(env, h_gx, h_gy);
 }
 
+// ---- the modal control surface (modal.hpp) ----------------------------------------------------------------------------------------
+int aoenv_set_modal(AoEnv* env, const AoModal* cfg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AoEnv::Modal& mo = env->modal;
+    if (!cfg) {
+        AO_HIP(hipStreamSynchronize(st));                          // a step in flight reads the tables in place
+        if (mo.base) (void)hipFree(mo.base);
+        mo = AoEnv::Modal{};
+        return 0;
+    }
+    const int K = cfg->n_modes, A = env->A;
+    if (K < 1 || K > A) return fail("aoenv_set_modal: n_modes %d outside [1, A=%d]", K, A);
+    if (!cfg->h_m2c || !cfg->h_cm) return fail("aoenv_set_modal: null m2c / cm");
+    const size_t nm = (size_t)A * K, nc = (size_t)K * env->nSig, E = (size_t)env->E, img = (size_t)env->nAct * env->nAct;
+    for (size_t i = 0; i < nm; ++i)
+        if (!std::isfinite(cfg->h_m2c[i])) return fail("aoenv_set_modal: m2c[%zu] is not finite", i);
+    for (size_t i = 0; i < nc; ++i)
+        if (!std::isfinite(cfg->h_cm[i])) return fail("aoenv_set_modal: cm[%zu] is not finite", i);
+    const size_t z = env->esz, n_slab = (z == 4 ? (size_t)kMaxSplits : 1) * E * K;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t part[] = {al(nm * z), al(nc * z), al(E * K * z), al(E * img * z), al(E * img * z), al(2 * E * z), al(n_slab * z)};
+    size_t bytes = 0;
+    for (size_t b : part) bytes += b;
+    AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the tables in place
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("aoenv_set_modal: no device memory for %zu bytes of modal tables and scratch", bytes);
+    }
+    if (mo.base) (void)hipFree(mo.base);
+    mo = AoEnv::Modal{};
+    mo.base = p;
+    void** field[] = {&mo.m2c_t, &mo.cm, &mo.gain, &mo.image, &mo.zobs, &mo.zscal, &mo.slabs};
+    char* c = static_cast<char*>(p);
+    for (int k = 0; k < 7; ++k) { *field[k] = c; c += part[k]; }
+    AO_HIP(hipMemset(p, 0, bytes));
+    std::vector<double> t(nm);                                     // M2C [A][K] -> [K][A]
+    for (int a = 0; a < A; ++a)
+        for (int m = 0; m < K; ++m) t[(size_t)m * A + a] = cfg->h_m2c[(size_t)a * K + m];
+    AO_TRY(upload_real(env, mo.m2c_t, t.data(), nm));
+    AO_TRY(upload_real(env, mo.cm, cfg->h_cm, nc));
+    mo.K = K;
+    mo.set = true;
+    return 0;
+}
+
+int aoenv_set_modal_gain(AoEnv* env, const double* h_gain, int per_env, void* stream) {
+    AO_CHECK_ENV(env);
+    AoEnv::Modal& mo = env->modal;
+    if (!mo.set) return fail("aoenv_set_modal_gain: no modal basis is set (aoenv_set_modal)");
+    if (!h_gain) return fail("aoenv_set_modal_gain: null gains");
+    const size_t n = (size_t)(per_env ? env->E : 1) * mo.K;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(h_gain[i]) || h_gain[i] < 0) return fail("aoenv_set_modal_gain: gain[%zu] is not finite or negative", i);
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // a loop in flight reads the gains in place
+    mo.have_gain = false;                                          // (a failed copy leaves no half-written gains in use)
+    AO_TRY(upload_real(env, mo.gain, h_gain, n));
+    mo.gain_env = per_env ? (size_t)mo.K : 0;
+    mo.have_gain = true;
+    return 0;
+}
+
+int aoenv_reset_soft_modal(AoEnv* env, void* d_obs, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->modal.set) return fail("aoenv_reset_soft_modal: no modal basis is set (aoenv_set_modal)");
+    if (!d_obs) return fail("aoenv_reset_soft_modal: null obs");
+    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    return AO_DISPATCH(env, reset_soft_modal_t, env, d_obs, static_cast<hipStream_t>(stream));
+}
+
+int aoenv_step_modal(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
+                     void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->modal.set) return fail("aoenv_step_modal: no modal basis is set (aoenv_set_modal)");
+    if (!d_action || !d_obs) return fail("aoenv_step_modal: null action / obs");
+    if (i < 0 || i >= env->c.n_loop) return fail("frame index %d outside [0, n_loop=%d)", i, env->c.n_loop);
+    AO_TRY(require_step_constants(env, true));
+    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    return AO_DISPATCH(env, step_modal_t, env, i, d_action, false, d_obs, d_frame, d_reward, d_strehl, true, static_cast<hipStream_t>(stream));
+}
+
+int aoenv_run_integrator_modal(AoEnv* env, int i0, int n_steps, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
+                               void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->modal.set) return fail("aoenv_run_integrator_modal: no modal basis is set (aoenv_set_modal)");
+    if (!env->modal.have_gain) return fail("aoenv_run_integrator_modal: no modal gains are set (aoenv_set_modal_gain)");
+    if (!d_obs) return fail("aoenv_run_integrator_modal: null obs");
+    if (i0 < 0 || n_steps < 0 || i0 + n_steps > env->c.n_loop) return fail("frames [%d, %d) outside [0, n_loop=%d)", i0, i0 + n_steps, env->c.n_loop);
+    AO_TRY(require_step_constants(env, true));
+    if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (only the last step's residual phase and camera frame can be read afterwards, as after aoenv_run_integrator)
+    for (int k = 0; k < n_steps; ++k)
+        AO_TRY(AO_DISPATCH(env, step_modal_t, env, i0 + k, d_obs, true, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward, d_strehl,
+                           k == n_steps - 1, st));
+    return 0;
+}
+
 // ---- the control delay (delay.hpp) ------------------------------------------------------------------------------------------------
 static_assert(kMaxDelay == AOENV_MAX_DELAY, "delay.hpp and aoenv.h disagree");
 int aoenv_set_delay(AoEnv* env, int delay, void* stream) {
@@ -2785,7 +2984,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             env->wind_pixels = value;
             return 0;
         case AOENV_OPT_FORCE_PATH:
-            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN))
+            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

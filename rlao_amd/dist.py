@@ -2,8 +2,9 @@
 
 Episodes are independent, so the only exchange is one all-gather of the per-env episode
 returns / mean Strehl at episode end (RCCL over xGMI via torch.distributed backend "nccl"; "gloo" on CPU
-for the tests).  Per-env settings (``set_wind_per_env``, ``set_r0_per_env``, ``set_dm_misregistration``) are local to a shard: each rank passes the values of
-its own envs, ``values[lo:hi]`` of ``shard_bounds``."""
+for the tests).  Per-env settings (``set_wind_per_env``, ``set_r0_per_env``, ``set_dm_misregistration``, the per-env rows of ``set_modal_gain``) are local to a
+shard: each rank passes the values of its own envs, ``values[lo:hi]`` of ``shard_bounds``.  The modal surface (``set_modal``,
+``step_modal``, ``run_integrator_modal``) works per shard as ``step`` does: every rank sets the same basis on its own shard."""
 from __future__ import annotations
 
 import os

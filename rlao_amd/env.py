@@ -207,6 +207,86 @@ def resolve_disturbance(modes, amp, freq, phase, t0, env_ids, n_envs: int, n_val
     return out
 
 
+def resolve_modal(n_modes, m2c, cm, n_valid_act: int, n_signal: int, m2c_cl=None, imat=None) -> dict:
+    """The modal basis of a ``set_modal`` call as the host arrays the library is handed: ``dict(m2c [A, K], cm [K, n_signal])``,
+    float64 and contiguous.  ``m2c=None``: the first ``n_modes`` columns of ``m2c_cl`` (``M2C_CL``; ``n_modes=None``: all of them);
+    otherwise ``[A, K']``, cut to its first ``n_modes`` columns when that is given.  ``cm=None``: the modal command matrix
+    ``calib.reconstructor_from_imat(imat, m2c, True)[2]``, the reference's ``CalibrationVault(D @ M2C[:, :nModes]).M``
+    (MAIN/OOPAOEnv/modalAOEnv.py:410, 447-449).  Raises ``ValueError`` for wrong shapes, K outside [1, A] and values that are not
+    finite.  Pure host code."""
+    A, nS = int(n_valid_act), int(n_signal)
+
+    def arr(x, name):
+        if hasattr(x, "detach"):
+            x = x.detach().cpu().numpy()
+        try:
+            return np.asarray(x, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be numeric") from None
+
+    if n_modes is not None and (isinstance(n_modes, bool) or not isinstance(n_modes, (int, np.integer))):
+        raise ValueError(f"n_modes must be an int, got {n_modes!r}")
+    if m2c is None:
+        if m2c_cl is None:
+            raise ValueError("m2c=None needs the env's M2C_CL (set_params)")
+        B = arr(m2c_cl, "M2C_CL")
+    else:
+        B = arr(m2c, "m2c")
+    if B.ndim != 2 or B.shape[0] != A:
+        raise ValueError(f"m2c must have shape (A={A}, K), got {B.shape}")
+    K = B.shape[1] if n_modes is None else int(n_modes)
+    if not 1 <= K <= min(A, B.shape[1]):
+        raise ValueError(f"n_modes = {K} outside [1, {min(A, B.shape[1])}] (A = {A} actuators, {B.shape[1]} columns)")
+    B = B[:, :K]
+    if cm is None:
+        if imat is None:
+            raise ValueError("cm=None needs the env's interaction matrix (set_params)")
+        from . import calib
+        M = np.asarray(calib.reconstructor_from_imat(np.asarray(imat, dtype=np.float64), B, True)[2], dtype=np.float64)
+    else:
+        M = arr(cm, "cm")
+    if M.shape != (K, nS):
+        raise ValueError(f"cm must have shape (K={K}, n_signal={nS}), got {M.shape}")
+    if not (np.isfinite(B).all() and np.isfinite(M).all()):
+        raise ValueError("m2c and cm must be finite")
+    return {"m2c": np.ascontiguousarray(B).copy(), "cm": np.ascontiguousarray(M).copy()}
+
+
+def resolve_modal_gain(g, env_ids, n_envs: int, n_modes: int, current=None):
+    """The gains of the modal integrator after a ``set_modal_gain`` call: ``(gain, per_env)`` with ``gain`` float64 ``[K]``
+    (``per_env`` False: every env the same) or ``[n_envs, K]``.  ``g``: a scalar, ``[K]`` or ``[n_envs, K]``; with ``env_ids``
+    (anything ``normalize_env_ids`` takes) a scalar, ``[K]`` or one row per listed env in the order of ``env_ids``, the other envs
+    keeping the rows of ``current`` (an earlier result's ``gain``) or, without one, gain 0: open loop.  Raises ``ValueError`` for
+    wrong shapes and for entries that are not finite or negative.  Pure host code."""
+    n_envs, K = int(n_envs), int(n_modes)
+    if hasattr(g, "detach"):
+        g = g.detach().cpu().numpy()
+    try:
+        v = np.asarray(g, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("gains must be numeric") from None
+    given = None if env_ids is None else normalize_env_ids(env_ids, n_envs, return_order=True)[1]
+    k = n_envs if given is None else int(given.size)
+    if v.ndim > 2 or (v.ndim >= 1 and v.shape[-1] != K) or (v.ndim == 2 and v.shape[0] != k):
+        raise ValueError(f"gains must be a scalar or have shape (K={K},) or ({k}, K={K}), got {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError("gains must be finite")
+    if (v < 0).any():
+        raise ValueError("gains must be >= 0")
+    if given is None and v.ndim < 2:
+        return np.ascontiguousarray(np.broadcast_to(v, (K,))).copy(), False
+    if given is None:
+        return np.ascontiguousarray(v).copy(), True
+    out = np.zeros((n_envs, K))
+    if current is not None:
+        cur = np.asarray(current, dtype=np.float64)
+        if cur.shape[-1] != K:
+            raise ValueError(f"env_ids: the gains in force have K = {cur.shape[-1]}, this call {K}")
+        out[:] = cur
+    out[given] = v
+    return out, True
+
+
 def disturbance_value(cfg: dict, i: int) -> np.ndarray:
     """``B v(t0 + i + 1)`` of a ``resolve_disturbance`` result, float64 ``[n_envs, A]``: the model of rlao_amd/csrc/disturb.hpp
     on the host.  The phase ``x = fma(freq, tau, phase)`` is formed with ONE rounding, as there (exact rational arithmetic, then
@@ -751,6 +831,10 @@ class BatchedAOEnv:
         self._r0_env = None                                        # [n_envs] Fried parameters once per-env r0 is set
         self._disturb = None                                       # resolve_disturbance()'s arrays while a disturbance is set
         self._dm_per_env = False                                   # every env its own mirror (set_dm_tables_per_env / set_dm_misregistration)
+        self._modal = None                                         # resolve_modal()'s arrays while a modal basis is set
+        self._modal_gain = None                                    # resolve_modal_gain()'s array while modal gains are set
+        self._mobs = None                                          # the modal observation run_integrator_modal goes on from
+        self._surface = "zonal"                                    # which surface the last observation came from: "zonal" | "modal"
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
 
     # -- construction --------------------------------------------------------------------------------
@@ -838,6 +922,8 @@ class BatchedAOEnv:
         self._per_env_clock = False
         self._wind_pixels = 1
         self._dm_per_env, self._dm_misreg = False, None              # ... and one mirror, the calibrated one
+        self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
+        self._surface = "zonal"
         sh = self._shard
         at = self._atm_tables
         sh.upload_ring_tables(at)
@@ -1226,6 +1312,127 @@ class BatchedAOEnv:
             return line.detach().to("cpu", dtype=torch.float64).numpy()[:, 0]
         return line
 
+    # -- the modal control surface (MAIN/OOPAOEnv/modalAOEnv.py; aoenv_set_modal) ------------------------------------------------
+    def set_modal(self, n_modes=None, m2c=None, cm=None):
+        """A modal control surface beside the zonal one: ``step_modal`` takes ``[n_envs, K]`` modal coefficients and returns the
+        modal reconstruction, as the reference's modal envs do (MAIN/OOPAOEnv/modalAOEnv.py:150-171, 190):
+        ``dm.coefs = dm_prev * leak + (m2c @ a) * 1e-6``, ``obs = -(cm @ wfs.signal) * 1e6``, ``reward = -||obs||^2``.  Default
+        basis: ``M2C_CL[:, :n_modes]`` (all columns without ``n_modes``) with ``cm`` the modal command matrix
+        ``calib.reconstructor_from_imat(self.imat, m2c, True)[2]`` -- the reference's ``calib_tt.M`` (:410, 447-449).  ``m2c`` [A, K]
+        and ``cm`` [K, nSignal] may be handed over instead.  ``step``, ``run_integrator``, the rollouts and the policy stay zonal
+        and unchanged; delays, disturbances, per-env winds, r0 and mirrors act on a modal step as on a zonal one.  A new basis
+        forgets the gains of ``set_modal_gain``.  Not part of ``get_state``: after ``set_state`` on a new env call this again."""
+        full = resolve_modal(n_modes, m2c, cm, self.nValidAct, self.nSignal, self.M2C_CL, self.imat)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        cfg = L.AoModal(n_modes=full["m2c"].shape[1], h_m2c=ptr(full["m2c"]), h_cm=ptr(full["cm"]))
+        L.check(self._shard.lib.aoenv_set_modal(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        self._modal, self._modal_gain, self._mobs = full, None, None
+
+    def clear_modal(self):
+        """No modal surface: the basis, the gains and the device memory of both are gone."""
+        L.check(self._shard.lib.aoenv_set_modal(self._shard.h, None, C.c_void_p(self._stream())))
+        self._modal = self._modal_gain = self._mobs = None
+
+    @property
+    def n_modal(self) -> int:
+        """The number of modes of the modal surface, 0 while none is set."""
+        return 0 if self._modal is None else int(self._modal["m2c"].shape[1])
+
+    def _require_modal(self):
+        if self._modal is None:
+            raise L.AoEnvError("no modal basis is set: call set_modal() first")
+
+    def _require_surface(self, surface: str, who: str):
+        """The device loops go on from the env's last observation, and the zonal and the modal surface each keep their own: after a
+        step of the other surface that observation is an old one, so the loop is refused instead of continuing from it."""
+        if self._surface != surface:
+            raise L.AoEnvError(f"{who}: the last observation is {self._surface}; restart the loop with "
+                               f"{'reset_soft()' if surface == 'zonal' else 'reset_soft_modal()'} (or a {surface} step) first")
+
+    def set_modal_gain(self, g, env_ids=None):
+        """The gains of ``run_integrator_modal``: a scalar, ``[K]``, or one row per env ``[n_envs, K]`` -- a gain sweep is then one
+        shard.  With ``env_ids`` (a list or a mask) the rows belong to the listed envs, in that order, and the other envs keep
+        theirs (none yet: 0, open loop).  Gains are finite and >= 0."""
+        self._require_modal()
+        cur = self._modal_gain
+        if cur is not None and cur.ndim == 1:
+            cur = np.broadcast_to(cur, (self.n_envs, cur.shape[0]))
+        gain, per_env = resolve_modal_gain(g, env_ids, self.n_envs, self.n_modal, cur)
+        L.check(self._shard.lib.aoenv_set_modal_gain(self._shard.h, gain.ctypes.data_as(C.c_void_p), int(per_env), C.c_void_p(self._stream())))
+        self._modal_gain = gain
+
+    def reset_soft_modal(self):
+        """``reset_soft`` in mode space: the modal reconstruction ``[n_envs, K]`` of the measurement as it stands (no disturbance;
+        a library delay line is cleared, as ``reset_soft`` does)."""
+        self._require_modal()
+        self.action_buffer = []
+        d = self.delay
+        if d > 0:
+            self.set_delay(d)
+        obs = _torch().empty((self.n_envs, self.n_modal), device=self.device, dtype=self.tdtype)
+        L.check(self._shard.lib.aoenv_reset_soft_modal(self._shard.h, C.c_void_p(obs.data_ptr()), C.c_void_p(self._stream())))
+        self._mobs, self._surface = obs, "modal"
+        return self._out(obs)
+
+    def _modal_tensor(self, action):
+        a = _torch().as_tensor(action)
+        if a.dim() == 1:
+            a = a.unsqueeze(0)
+        if tuple(a.shape) != (self.n_envs, self.n_modal):
+            raise ValueError(f"modal action must have shape ({self.n_envs}, {self.n_modal}), got {tuple(a.shape)}")
+        return a.to(device=self.device, dtype=self.tdtype).contiguous()
+
+    def step_modal(self, i, action):
+        """``step`` in mode space (MAIN/OOPAOEnv/modalAOEnv.py:139-200): ``action`` ``[n_envs, K]`` modal coefficients, expanded on
+        the device to the action image the step integrates.  Returns ``(obs, wfs_frame, reward, strehl, done, info)`` as ``step``
+        does, with ``obs`` ``[n_envs, K]`` the modal reconstruction and ``reward = -||obs||^2``; every call hands out new tensors.
+        The order of effects is the library's: the atmosphere advances, the sensor sees the command latched by the previous call,
+        then the command is updated -- the reference's modal env with ``delay = d`` is this with ``set_delay(d - 1)``
+        (INTEGRATION.md)."""
+        self._require_modal()
+        torch = _torch()
+        a = self._modal_tensor(action)
+        N = self.n_envs
+        obs = torch.empty((N, self.n_modal), device=self.device, dtype=self.tdtype)
+        reward = torch.empty((N,), device=self.device, dtype=self.tdtype)
+        strehl = torch.empty((N,), device=self.device, dtype=self.tdtype)
+        view = self.return_frame == "view"
+        fr = torch.empty((N, self.cam_res, self.cam_res), device=self.device, dtype=self.tdtype) if (self.return_frame and not view) else None
+        L.check(self._shard.lib.aoenv_step_modal(
+            self._shard.h, int(i), C.c_void_p(a.data_ptr()), C.c_void_p(obs.data_ptr()),
+            C.c_void_p(fr.data_ptr()) if fr is not None else None, C.c_void_p(reward.data_ptr()),
+            C.c_void_p(strehl.data_ptr()), C.c_void_p(self._stream())))
+        if view:
+            fr = self._frame_alias()
+        self._mobs, self._reward, self._strehl, self._frame = obs, reward, strehl, fr
+        self._surface = "modal"
+        self.SR.append(strehl)
+        if self.output == "numpy":
+            s = float(strehl[0])
+            return (self._out(obs), None if fr is None else self._out(fr), float(reward[0]), s, False, {"strehl": s})
+        if self._done is None:
+            self._done = torch.zeros(N, dtype=torch.bool, device=self.device)
+        return obs, fr, reward, strehl, self._done, {"strehl": strehl}
+
+    def run_integrator_modal(self, i0: int, n_steps: int):
+        """The modal integrator on the device, one gain per mode (and per env): ``n_steps`` iterations of ``a = g * obs;
+        obs, reward, strehl = step_modal(i0 + k, a)`` with the gains of ``set_modal_gain``, bit for bit what that loop gives;
+        returns the last (obs, reward, strehl).  ``reset_soft_modal()`` (or a previous modal step) must have produced the current
+        observation: after a zonal ``step`` / ``run_integrator`` / rollout the call is refused, as ``run_integrator`` and the rollouts
+        are after a modal step -- each surface goes on from its own last observation only."""
+        self._require_modal()
+        if self._modal_gain is None:
+            raise L.AoEnvError("no modal gains are set: call set_modal_gain() first")
+        if self._mobs is None:
+            raise L.AoEnvError("no modal observation yet: call reset_soft_modal() first")
+        self._require_surface("modal", "run_integrator_modal")
+        self._mobs = self._mobs.clone()                             # in place on a private copy, as run_integrator
+        self._reward, self._strehl = _torch().empty_like(self._reward), _torch().empty_like(self._strehl)
+        L.check(self._shard.lib.aoenv_run_integrator_modal(
+            self._shard.h, int(i0), int(n_steps), C.c_void_p(self._mobs.data_ptr()), None,
+            C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._strehl.data_ptr()), C.c_void_p(self._stream())))
+        return self._mobs, self._reward, self._strehl
+
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset
         return int(seed) + idx * self.env_seed_stride
@@ -1332,7 +1539,7 @@ class BatchedAOEnv:
         # a NEW tensor, like step(): the observation handed out by the previous step (a trainer may have kept it) is not written to
         obs = _torch().empty_like(self._obs)
         L.check(self._shard.lib.aoenv_reset_soft(self._shard.h, C.c_void_p(obs.data_ptr()), C.c_void_p(self._stream())))
-        self._obs = obs
+        self._obs, self._surface = obs, "zonal"
         return self._out(obs)
 
     def reset(self):
@@ -1367,6 +1574,7 @@ class BatchedAOEnv:
         if view:
             fr = self._frame_alias()
         self._obs, self._reward, self._strehl, self._frame = obs, reward, strehl, fr
+        self._surface = "zonal"
         self.SR.append(strehl)
         if self.output == "numpy":
             s = float(strehl[0])
@@ -1402,6 +1610,7 @@ class BatchedAOEnv:
         have produced the current observation.  Under a library delay (``set_delay``) ``gainCL * obs`` goes into the delay line
         instead (one small launch per step) and the step applies the action formed ``delay`` steps earlier."""
         g = float(self.gainCL if gain is None else gain)
+        self._require_surface("zonal", "run_integrator")
         # the loop runs in place on the observation: on private copies, never on tensors step() / reset_soft() have handed out
         self._obs = self._obs.clone()
         self._reward, self._strehl = _torch().empty_like(self._reward), _torch().empty_like(self._strehl)
@@ -1455,6 +1664,7 @@ class BatchedAOEnv:
             sig = torch.as_tensor(sigma_env).to(device=self.device, dtype=self.tdtype).contiguous()
             if tuple(sig.shape) != (N,):
                 raise ValueError(f"sigma_env must have shape ({N},), got {tuple(sig.shape)}")
+        self._require_surface("zonal", "a recorded rollout")
         obs = torch.empty((K + 1, N, A_, A_), device=self.device, dtype=self.tdtype)
         obs[0] = self._obs
         action = torch.empty((K, N, A_, A_), device=self.device, dtype=self.tdtype)
@@ -1625,6 +1835,7 @@ class BatchedAOEnv:
                 raise ValueError(f"delay_line must have shape ({d}, {self.n_envs}, {self.nActuator}, {self.nActuator}), got {line.shape}")
             L.check(sh.lib.aoenv_set_delay_line(sh.h, line.ctypes.data_as(C.c_void_p), line.nbytes, C.c_void_p(st)))
         self._obs = _torch().as_tensor(state["obs"]).to(device=self.device, dtype=self.tdtype).clone()   # (never into a handed-out tensor)
+        self._surface, self._mobs = "zonal", None                    # (the state carries the zonal observation alone)
 
     def _download_screens(self):
         """layer.mapShift of every env: [nLayer, n_envs, S, S], or -- layers on grids of their own -- a list of [n_envs, S_l, S_l]."""

@@ -81,6 +81,23 @@ class TorchWrapper:
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
 
+    def step_modal(self, i, action):
+        """``BatchedAOEnv.step_modal`` in this wrapper's return convention (``step``'s): a float32 modal observation."""
+        torch = _torch()
+        if getattr(self._env, "output", "torch") == "numpy":
+            next_obs, wfsf, reward, strehl, done, info = self._env.step_modal(i, action.cpu().numpy())
+            return (torch.tensor(next_obs, dtype=torch.float32), wfsf, reward, strehl, done,
+                    [(k, torch.tensor(v, dtype=torch.float32)) for k, v in info.items()])
+        next_obs, wfsf, reward, strehl, done, info = self._env.step_modal(i, action)
+        return next_obs.float(), wfsf, reward, strehl, done, [(k, v.float()) for k, v in info.items()]
+
+    def reset_soft_modal(self):
+        return _torch().as_tensor(self._env.reset_soft_modal(), dtype=_torch().float32)
+
+    def run_integrator_modal(self, i0, n_steps):
+        """``BatchedAOEnv.run_integrator_modal`` in this wrapper's return convention: float32 tensors."""
+        return tuple(_torch().as_tensor(t).float() for t in self._env.run_integrator_modal(i0, n_steps))
+
     def rollout(self, i0, n_steps, sigma, gain=None, seed=None, sigma_env=None):
         """``BatchedAOEnv.rollout`` in this wrapper's return convention: float32 tensors."""
         torch = _torch()
@@ -163,6 +180,14 @@ class TimeDelayEnv:
         out = self._env.step(i, self.action_buffer[0])
         del self.action_buffer[0]
         return out
+
+    def step_modal(self, i, action):
+        """Refused: this FIFO holds action images for ``step``.  A modal loop takes its delay from the library --
+        ``env.set_delay(d)`` -- which ``step_modal`` and ``run_integrator_modal`` honour on the device."""
+        raise NotImplementedError("TimeDelayEnv delays step() only: use env.set_delay(d) for step_modal / run_integrator_modal")
+
+    def run_integrator_modal(self, i0, n_steps):
+        raise NotImplementedError("TimeDelayEnv delays step() only: use env.set_delay(d) for step_modal / run_integrator_modal")
 
     def rollout(self, *args, **kw):
         raise NotImplementedError(
