@@ -156,7 +156,8 @@ int aoenv_set_wind(AoEnv* env, const double* h_ratio, int reset_buff);
 
 /* The same setters when every env has its OWN wind (a trainer that draws wind speed / direction per run, e.g.
  * MAIN/integrator_oopao_razor.py:41-44, batched): h_ratio is [n_layer][n_env][2] float64, |ratio| < n pixels per frame on each
- * axis, n the ceiling AOENV_OPT_ENV_WIND_PIXELS (default 1); a larger ratio is refused with nothing changed.
+ * axis, n the ceiling AOENV_OPT_ENV_WIND_PIXELS (default 1); a larger ratio is refused with nothing changed, and so is a shard with
+ * layers on grids of their own (AoCfg.layer_res_l), which has no per-env clocks.
  * The shard switches to per-env clocks for good: accumulators, torus origins and warp taps of every (env, layer) live on
  * the device and are advanced there, by the same arithmetic as the shared host clock (an env stepped by its own clock is
  * bit-identical to a shard stepped with that wind); on every step one launch per layer advances the clocks and prepares the

@@ -176,6 +176,11 @@ def warp_translate(img: np.ndarray, tx: float, ty: float) -> np.ndarray:
 class LayerGeometry:
     """Shared per-geometry constants of one turbulence layer (buildLayer :192-298)."""
 
+    @staticmethod
+    def grid(tel_resolution: int, tel_D: float, altitude: float = 0.0, fov_rad: float = 0.0) -> int:
+        """Pixels across the grid of a layer at `altitude` (:216-218)."""
+        return int(np.ceil((tel_resolution / tel_D) * (tel_D + 2 * np.tan(fov_rad / 2) * altitude))) + 4
+
     def __init__(self, tel_resolution: int, tel_D: float, L0: float, r0_def: float = 0.15,
                  altitude: float = 0.0, fov_rad: float = 0.0):
         self.D_fov = tel_D + 2 * np.tan(fov_rad / 2) * altitude
@@ -297,17 +302,30 @@ class OracleAtmosphere:
 
     def __init__(self, tel_resolution, tel_D, dt, pupil, r0, L0, windSpeed, fractionalR0,
                  windDirection, altitude, fov_rad=0.0, geom_AB=None):
-        """geom_AB = (LayerGeometry, A, B): operators computed by the caller (fov = 0; the ELT-size ones take minutes)."""
+        """geom_AB = (LayerGeometry, A, B): operators computed by the caller (fov = 0; the ELT-size ones take minutes), or a list
+        with one such triple per layer (any fov: every layer's grid must be the one its altitude gives)."""
         self.R, self.D, self.dt, self.pupil = tel_resolution, tel_D, dt, pupil
         self.r0, self.L0 = r0, L0
         self.fractionalR0 = list(fractionalR0)
         self.nLayer = len(self.fractionalR0)
         self.layers = []
-        geom = None
-        if geom_AB is not None and fov_rad == 0:
+        geom, per_layer = None, None
+        if isinstance(geom_AB, list):
+            per_layer = geom_AB
+            if len(per_layer) != self.nLayer:
+                raise ValueError(f"geom_AB: {len(per_layer)} triples for {self.nLayer} layers")
+        elif geom_AB is not None and fov_rad == 0:
             geom, A, B = geom_AB
         for i in range(self.nLayer):
-            if geom is None or fov_rad != 0:
+            if per_layer is not None:
+                geom, A, B = per_layer[i]
+                n = LayerGeometry.grid(tel_resolution, tel_D, altitude[i], fov_rad)
+                A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+                if geom.resolution != n:
+                    raise ValueError(f"geom_AB: layer {i} has a grid of {n} pixels, its geometry one of {geom.resolution}")
+                if A.shape != (geom.outerZ.size, geom.innerZ.size) or B.shape != (geom.outerZ.size, geom.outerZ.size):
+                    raise ValueError(f"geom_AB: operators of layer {i} have shapes {A.shape}, {B.shape}")
+            elif geom is None or fov_rad != 0:
                 geom = LayerGeometry(tel_resolution, tel_D, L0, altitude=altitude[i], fov_rad=fov_rad)
                 A, B = geom.AB(r0)
             self.layers.append(OracleLayer(geom, A, B, windSpeed[i], windDirection[i], self.fractionalR0[i]))

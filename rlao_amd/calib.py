@@ -215,6 +215,18 @@ class AtmosphereTables:
         g0 = self.layers[0]
         self.A, self.B, self.AB = g0.A, g0.B, g0.AB
 
+    def replace_operators(self, pairs):
+        """Operators handed over, one (A, B) per layer (shapes checked by the caller): every layer gets a table of its own, also
+        the layers of one grid size that shared one."""
+        import copy
+        self.layers = [copy.copy(t) for t in self.layers]
+        for t, (A, B) in zip(self.layers, pairs):
+            t.A, t.B = A, B
+            t.AB = np.ascontiguousarray(np.concatenate([A, B], axis=1))
+        self._grids = list(self.layers)
+        g0 = self.layers[0]
+        self.A, self.B, self.AB = g0.A, g0.B, g0.AB
+
     def wind_ratio(self, speeds, directions, dt):
         """pixels per frame along (x, y) for each layer (:209-210, :352-363)."""
         out = np.zeros((len(speeds), 2))

@@ -1574,6 +1574,9 @@ static int pull_env_clocks(AoEnv* env, std::vector<EnvClock>& clk) {
 int aoenv_set_wind_env(AoEnv* env, const double* h_ratio, int reset_buff, void* stream) {
     AO_CHECK_ENV(env);
     if (!h_ratio) return fail("null ratio");
+    if (!env->uniform)
+        return fail("aoenv_set_wind_env: layers on grids of their own (AoCfg.layer_res_l: fov != 0 with altitude layers) have no per-env clocks; "
+                    "one wind for the shard (aoenv_set_wind)");
     const size_t n = (size_t)env->L * env->E;
     for (size_t i = 0; i < 2 * n; ++i)
         if (!(std::fabs(h_ratio[i]) < (double)env->wind_pixels))

@@ -842,6 +842,36 @@ class BatchedAOEnv:
         """Kept for call compatibility (MAIN/PO4AO/mbrl.py:27); the parameters come from ``set_params``."""
         self.param_file, self.oopao_path = param_file, oopao_path
 
+    @staticmethod
+    def _atmosphere_tables(p, atm_AB=None):
+        """calib.AtmosphereTables of ``p``, the ring-extrusion operators handed over in ``atm_AB`` instead of recomputed: A = ZXt^T
+        pinv(ZZt) goes through the pseudo-inverse of a covariance matrix of condition ~1e9, whose result differs between CPUs /
+        LAPACK builds at the 1e-9 .. 1e-7 level (the parity tests inject the recorded operators to separate that from the device
+        arithmetic).  One pair (A, B): the layers share one grid; a list with one pair per layer: they have grids of their own."""
+        at = calib.AtmosphereTables(p)
+        if atm_AB is None:
+            return at
+        if isinstance(atm_AB, list):
+            if at.uniform:
+                raise ValueError("atm_AB: the layers of this atmosphere share one grid and one pair of operators (A, B)")
+            if len(atm_AB) != p.nLayer:
+                raise ValueError(f"atm_AB: {len(atm_AB)} pairs for {p.nLayer} layers")
+            pairs = [tuple(np.asarray(x, dtype=np.float64) for x in ab) for ab in atm_AB]
+            for l, (t, ab) in enumerate(zip(at.layers, pairs)):
+                if len(ab) != 2 or ab[0].shape != t.A.shape or ab[1].shape != t.B.shape:
+                    raise ValueError(f"atm_AB[{l}] must be a pair of shapes {t.A.shape} and {t.B.shape}")
+            at.replace_operators(pairs)                             # (every layer a table of its own, uploaded layer by layer)
+            return at
+        A_, B_ = (np.asarray(x, dtype=np.float64) for x in atm_AB)
+        if not at.uniform:
+            raise ValueError("atm_AB: the layers of this atmosphere have grids (and operators) of their own: one pair per layer")
+        if A_.shape != at.A.shape or B_.shape != at.B.shape:
+            raise ValueError(f"atm_AB must have shapes {at.A.shape} and {at.B.shape}")
+        at.A, at.B = A_, B_
+        at.AB = np.ascontiguousarray(np.concatenate([A_, B_], axis=1))
+        at.layers[0].A, at.layers[0].B, at.layers[0].AB = at.A, at.B, at.AB
+        return at
+
     def set_params(self, args=None, wfs_type="pyramid", modal_basis="zernike", gainCL=0.5, m2c=None, second_dm=None,
                    camera="papyrus", atm_AB=None, **kw):
         """Builds the loop (MAIN/OOPAOEnv/OOPAOEnv.py:93-385).  ``wfs_type`` is "pyramid" (the reference's default,
@@ -854,9 +884,14 @@ class BatchedAOEnv:
         parity configuration: the reference's noisy frames are wall-clock seeded, Detector.py:127-130).  The calibration itself always
         sees ideal spot intensities, as in the reference: the WFS constructor measures its reference slopes before the camera is
         configured, and the interaction-matrix pokes go through the Shack-Hartmann's multi-wave-front branch, which computes the
-        centroids from the intensities without passing them through the detector (OOPAO/ShackHartmann.py:605-672)."""
+        centroids from the intensities without passing them through the detector (OOPAO/ShackHartmann.py:605-672).
+        ``atm_AB``: the ring operators handed over instead of recomputed -- one pair (A, B) when the layers share a grid, a list
+        with one pair per layer when they have grids of their own (``_atmosphere_tables``); a wrong form or shape is refused
+        before anything of the env is touched."""
         if camera not in CAMERAS:
             raise ValueError(f"camera must be one of {sorted(CAMERAS)}")
+        p = calib.params_from_args(args, **kw)
+        at = self._atmosphere_tables(p, atm_AB)                      # (refuses before anything of a live env is touched)
         self.camera = camera
         if wfs_type in ("shackhartmann", "sh"):
             self.wfs_type = "sh"
@@ -866,25 +901,12 @@ class BatchedAOEnv:
             raise ValueError(f"unknown wfs_type {wfs_type!r}")
         torch = _torch()
         self.gainCL = gainCL
-        p = self.param = calib.params_from_args(args, **kw)
+        self.param = p
         self.leak = p.leak
         self.R = p.resolution
         self.pupil = calib.telescope_pupil(self.R, p.centralObstruction)
         self.src_wavelength, self.nPhoton = calib.source(p.opticalBand, p.magnitude)
-        self._atm_tables = calib.AtmosphereTables(p)
-        if atm_AB is not None:
-            # the ring-extrusion operators handed over instead of recomputed: A = ZXt^T pinv(ZZt) goes through the pseudo-inverse
-            # of a covariance matrix of condition ~1e9, whose result differs between CPUs / LAPACK builds at the 1e-9 .. 1e-7 level
-            # (the parity tests inject the recorded operators to separate that from the device arithmetic)
-            A_, B_ = (np.asarray(x, dtype=np.float64) for x in atm_AB)
-            at = self._atm_tables
-            if not at.uniform:
-                raise ValueError("atm_AB: the layers of this atmosphere have grids (and operators) of their own")
-            if A_.shape != at.A.shape or B_.shape != at.B.shape:
-                raise ValueError(f"atm_AB must have shapes {at.A.shape} and {at.B.shape}")
-            at.A, at.B = A_, B_
-            at.AB = np.ascontiguousarray(np.concatenate([A_, B_], axis=1))
-            at.layers[0].A, at.layers[0].B, at.layers[0].AB = at.A, at.B, at.AB
+        self._atm_tables = at
         self._dm_tables = dmt = (calib.DMTables(p) if not second_dm else
                                  calib.CompositeDM(p, int(second_dm["nSubaperture"])))
         self._dm_separable = 1 if dmt.gx is not None else 0
@@ -1441,8 +1463,10 @@ class BatchedAOEnv:
         """atm.generateNewPhaseScreen(seed) for every env; env e uses ``seed + e * env_seed_stride``
         (layer l: screen seed + l, ring RandomState seed + 1000 l -- OOPAO/Atmosphere.py:574-579).
         The screens are drawn on the device (same MT19937 stream and spectrum as the reference, float64 FFT).
-        ``screens`` [n_envs, nLayer, N, N] (rad @ 500 nm, N = resolution + 4): caller-made layer screens uploaded instead
-        (``aoenv_new_screens``); the rings and their RandomStates are still seeded from ``seed``."""
+        ``screens`` [n_envs, nLayer, N, N] (rad @ 500 nm; N = resolution + 4 with fov = 0 or every layer on the ground, in general
+        ``_atm_tables.N`` = ceil(R / D (D + 2 tan(fov / 2) h)) + 4 of the layers' shared altitude h): caller-made layer screens
+        uploaded instead (``aoenv_new_screens``); layers on grids of their own take a list with one array [n_envs, N_l, N_l] per
+        layer, N_l = ``_atm_tables.layer_res[l]``.  The rings and their RandomStates are still seeded from ``seed``."""
         if seed is None:
             seed = _wall_clock_seed()
         p, at = self.param, self._atm_tables

@@ -118,13 +118,14 @@ def run_oracle(base, m2c, modal_cm, seed, steps=STEPS):
     """Three envs (seeds seed + 100 k) of `base` with the controller (m2c, modal_cm): one closed-loop episode.  The actions come from
     the oracle's own observations and are float32 arrays, as the trainers' wrappers hand them over: NumPy then forms img_to_vec(action) *
     1e-6 in float32, and so does the device for a float32-representable action, whatever the shard's dtype."""
-    orcs, rec = [], dict(seed=seed, obs0=[], actions=[], signal=[], obs=[], reward=[], strehl=[], frame=[], gap=[])
+    orcs, rec = [], dict(seed=seed, obs0=[], screen0=[], actions=[], signal=[], obs=[], reward=[], strehl=[], frame=[], gap=[])
     for k in range(N_ENVS):
         o = copy.deepcopy(base, memo={id(x): x for x in (base.dm_modes, base.imat) if x is not None})
         o.M2C = np.asarray(m2c, dtype=np.float64)
         o.modal_cm = np.asarray(modal_cm, dtype=np.float64)
         o.reconstructor = o.M2C @ o.modal_cm
         o.new_episode(seed + SEED_STRIDE * k)
+        rec["screen0"].append([lay.mapShift.copy() for lay in o.atm.layers])
         rec["obs0"].append(o.reset_soft())
         rec["gap"].append(cut_gap(o.wfs.frame))
         orcs.append(o)
@@ -149,7 +150,7 @@ def run_oracle(base, m2c, modal_cm, seed, steps=STEPS):
         rec["actions"].append(act)
         obs = rec["obs"][-1]
     rec["crossings"] = crossings
-    rec["screen"] = [np.stack([lay.mapShift.copy() for lay in o.atm.layers]) for o in orcs]      # [env][layer, S, S]
+    rec["screen"] = [[lay.mapShift.copy() for lay in o.atm.layers] for o in orcs]                # [env][layer][S_l, S_l]
     rec["opd_atm"] = [o.atm.OPD.copy() for o in orcs]
     rec["opd_res"] = [o.tel_OPD.copy() for o in orcs]
     rec["total"] = np.stack([o.total[:steps] for o in orcs], axis=1)
@@ -198,10 +199,11 @@ def _reward(got, want, tol, label):
     np.testing.assert_allclose(got, want, rtol=tol["reward_rel"], atol=tol["obs"])
 
 
-def _replay(env, rec, tol, label, steps=STEPS, envs=range(N_ENVS), compare=None, winds=None):
+def _replay(env, rec, tol, label, steps=STEPS, envs=range(N_ENVS), compare=None, winds=None, screens0=False):
     """A fresh episode of `env` driven by the recorded actions: every step's signal, observation, reward, Strehl and frame, then (a
     full run) the screens, atm.OPD, the residual OPD and the telemetry.  `envs`: which recorded env each env of the shard is;
-    `compare`: the envs of the shard held to the oracle (default: all).  Returns what the shard gave, per step."""
+    `compare`: the envs of the shard held to the oracle (default: all); `screens0`: every layer's whole screen after the reset
+    too.  Returns what the shard gave, per step."""
     import torch
     from rlao_amd import _lib as L
     envs = list(envs)
@@ -216,6 +218,12 @@ def _replay(env, rec, tol, label, steps=STEPS, envs=range(N_ENVS), compare=None,
     out = [obs0]
     for k, r in pairs:
         _close(obs0[k], rec["obs0"][r], "obs", tol, label, err_msg=f"obs after reset, env {k}")
+    if screens0:
+        scr = env._download_screens()
+        for k, r in pairs:
+            for l in range(env.param.nLayer):
+                assert scr[l][k].shape == rec["screen0"][r][l].shape
+                _close(scr[l][k], rec["screen0"][r][l], "screen", tol, label, err_msg=f"screen after reset, env {k} layer {l}")
     for i in range(steps):
         act = torch.as_tensor(rec["actions"][i][envs])
         obs, frame, rew, sr, _, _ = env.step(i, act)
@@ -234,8 +242,11 @@ def _replay(env, rec, tol, label, steps=STEPS, envs=range(N_ENVS), compare=None,
         opd_atm = env._shard.download(L.B_OPD_ATM, (env.n_envs, env.R, env.R))
         phase = env._shard.download(L.B_PHASE, (env.n_envs, env.R, env.R))
         tot, res = env.total[:steps], env.residual[:steps]
+        if env.n_envs == 1:                                          # (a one-env shard hands out vectors)
+            tot, res = tot[:, None], res[:, None]
         for k, r in pairs:
             for l in range(env.param.nLayer):
+                assert scr[l][k].shape == rec["screen"][r][l].shape
                 _close(scr[l][k], rec["screen"][r][l], "screen", tol, label, err_msg=f"screen env {k} layer {l}")
             _close(opd_atm[k] * env.pupil, rec["opd_atm"][r], "opd_m", tol, label, err_msg=f"atm.OPD env {k}")
             _close(phase[k] * env.src_wavelength / (2 * np.pi), rec["opd_res"][r], "opd_m", tol, label, err_msg=f"residual OPD env {k}")

@@ -169,9 +169,10 @@ def test_golden_replay(name, dtype, golden_dir):
     label = f"{name}-{dtype}"
     inject = dtype == "f64-refAB"
     AB = None
-    if inject and "cfg_fov" in g:
-        pytest.skip("layers with operators of their own: the injection takes one pair")
-    if inject:
+    if inject and "cfg_fov" in g:                                  # layers with grids and operators of their own: one pair per layer
+        AB = [(g["A"], g["B"])] + [(g[f"A_l{l}"], g[f"B_l{l}"]) for l in range(1, len(g["cfg_alt"]))]
+        dtype = "f64"
+    elif inject:
         side = os.path.join(golden_dir, name + "_AB.npz")          # (c2_sh: the operators of the headline geometry, in full)
         if "A" in g:
             AB = (g["A"], g["B"])

@@ -137,13 +137,14 @@ def run_oracle(base, m2c, modal_cm, seed, steps=STEPS):
     Shack-Hartmann sweep records it (float32 actions from the oracle's own observations)."""
     w = base.wfs
     shared = [x for x in (base.dm_modes, base.imat, w.phasor, w.mask, w.m, w.tt_buffer, w.Tip, w.Tilt) if x is not None]
-    orcs, rec = [], dict(seed=seed, obs0=[], actions=[], signal=[], obs=[], reward=[], strehl=[], frame=[])
+    orcs, rec = [], dict(seed=seed, obs0=[], screen0=[], actions=[], signal=[], obs=[], reward=[], strehl=[], frame=[])
     for k in range(N_ENVS):
         o = copy.deepcopy(base, memo={id(x): x for x in shared})
         o.M2C = np.asarray(m2c, dtype=np.float64)
         o.modal_cm = np.asarray(modal_cm, dtype=np.float64)
         o.reconstructor = o.M2C @ o.modal_cm
         o.new_episode(seed + SEED_STRIDE * k)
+        rec["screen0"].append([lay.mapShift.copy() for lay in o.atm.layers])
         rec["obs0"].append(o.reset_soft())
         orcs.append(o)
     rs = np.random.RandomState(9)
@@ -165,7 +166,7 @@ def run_oracle(base, m2c, modal_cm, seed, steps=STEPS):
         rec["actions"].append(act)
         obs = rec["obs"][-1]
     rec["crossings"] = crossings
-    rec["screen"] = [np.stack([lay.mapShift.copy() for lay in o.atm.layers]) for o in orcs]      # [env][layer, S, S]
+    rec["screen"] = [[lay.mapShift.copy() for lay in o.atm.layers] for o in orcs]                # [env][layer][S_l, S_l]
     rec["opd_atm"] = [o.atm.OPD.copy() for o in orcs]
     rec["opd_res"] = [o.tel_OPD.copy() for o in orcs]
     rec["total"] = np.stack([o.total[:steps] for o in orcs], axis=1)
