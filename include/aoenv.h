@@ -582,8 +582,8 @@ enum AoOption {
                                  lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
                                  whose winds stay below one pixel per frame nothing: the same launches */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 other than AOENV_PATH_MODAL_GEMM also keeps the shard off the fused step kernel; other bits are
-                                 rejected */
+                                 other than AOENV_PATH_MODAL_GEMM and AOENV_PATH_SH_PLAIN also keeps the shard off the fused step
+                                 kernel; other bits are rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
 enum AoPath {
@@ -591,10 +591,14 @@ enum AoPath {
     AOENV_PATH_GENERIC = 512,          /* the Stockham Pyramid passes at nRes 528 / 288, the tiled 16-byte phase kernel instead of its
                                           one-layer band form */
     AOENV_PATH_PYR_ROUND_ROBIN = 1024, /* nRes 528 / 288 Pyramid column pass: blocks dealt round-robin over the XCDs */
-    AOENV_PATH_MODAL_GEMM = 2048       /* the projection of the modal surface (aoenv_step_modal) as a batched GEMM plus a finish kernel
+    AOENV_PATH_MODAL_GEMM = 2048,      /* the projection of the modal surface (aoenv_step_modal) as a batched GEMM plus a finish kernel
                                           whatever its size, instead of the per-env kernel below the threshold.  It touches nothing
                                           inside the step, so unlike the other bits it leaves the shard on the fused step kernel: the
                                           loop state is the same bit for bit, only the order of the projection's sum differs */
+    AOENV_PATH_SH_PLAIN = 4096         /* the general instantiation of the fused step kernel (run-time camera and trig tests, the
+                                          pixel-by-pixel stage A epilogue) and the plain C++ lenslet transform, there and in the
+                                          batched spots kernel, instead of the forms specialised for the launch and the register-pair
+                                          transform.  The shard stays on the fused step kernel; every output is the same bit for bit */
 };
 int aoenv_set_option(AoEnv* env, int option, int value);
 

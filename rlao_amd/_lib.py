@@ -25,7 +25,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
 OPT_FORCE_PATH = 99
 MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
-PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM = 256, 512, 1024, 2048
+PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN = 256, 512, 1024, 2048, 4096
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
                 "gemm_recon", "recon_finish", "pyramid", "sh_tail", "env_step", "detector")
 

@@ -34,6 +34,9 @@ __device__ inline void camera_rotate(f32x16s& v) {
     v = f32x16s{v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[0], v[1], v[2], v[3], 0.f, 0.f, 0.f, 0.f};
 }
 
+// PHOTON_ONLY: the caller knows at compile time that the camera is photon noise and nothing else (QE 1, no dark current, full
+// well, gain, read-out noise or ADC): the same draws, without the code of the rest
+template <bool PHOTON_ONLY = false>
 __device__ inline void camera_sh6_lane(f32x16s& pxv, bool ok, uint32_t px0, int cam, uint32_t e, const DetectorCfg& det,
                                        const uint32_t* __restrict__ tab, float lmax) {
     // frame index of the pixel in element p = 4 t + s of the (unrotated) vector
@@ -42,7 +45,7 @@ __device__ inline void camera_sh6_lane(f32x16s& pxv, bool ok, uint32_t px0, int 
         return px0 + (uint32_t)((t < 2 ? s4 : 4 + (s4 & 1)) * cam + ((t == 1 || (t == 2 && s4 >= 2)) ? 3 : 0));
     };
     auto quad_id = [&](int t) { return px0 + (t == 1 ? 3u : (t == 2 ? (uint32_t)(4 * cam) : 0u)); };
-    if (det.photon_noise) {
+    if (PHOTON_ONLY || det.photon_noise) {
         // (a wave without light -- lenslets outside the pupil in the stand-alone kernel -- draws nothing: Poisson(0) = 0)
         float brightest = 0.f;
 #pragma unroll
@@ -93,6 +96,7 @@ __device__ inline void camera_sh6_lane(f32x16s& pxv, bool ok, uint32_t px0, int 
         }
     }
     // QE, dark shot noise, saturation, gain, read-out noise, ADC: quad by quad, the same rotation
+    if constexpr (PHOTON_ONLY) return;
     const bool has_dark = det.dark_e > 0.f, has_read = det.readout_noise != 0.f;
     if (has_dark || has_read || det.qe != 1.f || det.gain != 1.f || det.fwc > 0.f || det.bits > 0) {
         const float rtab = recip_table_lane();

@@ -260,6 +260,7 @@ struct ShConst {
     T units;                 // slopes_units
     T threshold;
     int fast_trig;           // 1: hardware sin/cos after Cody-Waite reduction (float32 shards only)
+    int plain;               // 1: AOENV_PATH_SH_PLAIN, the plain lenslet transform and the general fused step kernel
 };
 template <typename T>
 int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, int n_env, int R, int n_subap,

@@ -316,6 +316,7 @@ ShConst<T> sh_const(const AoEnv* env) {
     sc.units = (T)env->units;
     sc.threshold = (T)env->c.threshold_cog;
     sc.fast_trig = (env->use_fast_trig && sizeof(T) == 4) ? 1 : 0;
+    sc.plain = (env->force_path & AOENV_PATH_SH_PLAIN) ? 1 : 0;
     return sc;
 }
 
@@ -796,7 +797,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~AOENV_PATH_MODAL_GEMM) == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -2987,7 +2988,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             env->wind_pixels = value;
             return 0;
         case AOENV_OPT_FORCE_PATH:
-            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM))
+            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

@@ -149,6 +149,181 @@ __device__ inline void lenslet_spots(const cplx<T>* __restrict__ Ej, int q, T ct
         }
     }
 }
+// ---- the same transform in float32 with every complex value held as a (re, im) pair of adjacent registers ------------------------
+// Written as the compiler sees it above, a complex multiply-add is four scalar fmas that it packs two by two into v_pk_fma_f32,
+// and every packed operand it first assembles with v_mov_b32 (138 of the 504 vector instructions of a turn of the c loop).  Here
+// a value is a pair from its LDS load on (E0 already is one) and a complex multiply-add is two v_pk_fma_f32 whose operand
+// selects and lane negations do the shuffling:
+//     acc += x.re (t.re, t.im)          x broadcast from its low half
+//     acc += x.im (-t.im, t.re)         x broadcast from its high half, t swapped, low lane negated
+// which is the chain above product for product and in its order (fma(-a, b, c) and fma(a, -b, c) round alike), so the frame is
+// bit-identical.
+typedef float f32x2s __attribute__((ext_vector_type(2)));
+
+// acc.lo += a[A_LO] * (+-) b[B_LO] ; acc.hi += a[A_HI] * (+-) b[B_HI]     (an index picks the half, NEG_* negates the product)
+template <int A_LO, int A_HI, int B_LO, int B_HI, int NEG_LO, int NEG_HI>
+__device__ inline void pk_fma_vv(f32x2s& acc, f32x2s a, f32x2s b) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[%3,%4,0] op_sel_hi:[%5,%6,1] neg_lo:[0,%7,0] neg_hi:[0,%8,0]"
+        : "+v"(acc) : "v"(a), "v"(b), "n"(A_LO), "n"(B_LO), "n"(A_HI), "n"(B_HI), "n"(NEG_LO), "n"(NEG_HI));
+}
+// the same with b in a pair of scalar registers (stage 2's constants)
+template <int A_LO, int A_HI, int B_LO, int B_HI, int NEG_LO, int NEG_HI>
+__device__ inline void pk_fma_vs(f32x2s& acc, f32x2s a, f32x2s b) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[%3,%4,0] op_sel_hi:[%5,%6,1] neg_lo:[0,%7,0] neg_hi:[0,%8,0]"
+        : "+v"(acc) : "v"(a), "s"(b), "n"(A_LO), "n"(B_LO), "n"(A_HI), "n"(B_HI), "n"(NEG_LO), "n"(NEG_HI));
+}
+
+// the first product of a chain, (a[A_LO] * (+-) b[B_LO], a[A_HI] * (+-) b[B_HI]), for fma(a, b, +0): the two differ only where the
+// product is an exact zero, in the zero's sign, and nothing downstream tells -0 from +0 -- sums with a non-zero term do not, and
+// what is left ends squared into an accumulator that starts at +0 (see lenslet_spots_pk)
+template <int A_LO, int A_HI, int B_LO, int B_HI, int NEG_LO, int NEG_HI>
+__device__ inline f32x2s pk_mul_vv(f32x2s a, f32x2s b) {
+    f32x2s d;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[%3,%4] op_sel_hi:[%5,%6] neg_lo:[0,%7] neg_hi:[0,%8]"
+        : "=v"(d) : "v"(a), "v"(b), "n"(A_LO), "n"(B_LO), "n"(A_HI), "n"(B_HI), "n"(NEG_LO), "n"(NEG_HI));
+    return d;
+}
+template <int A_LO, int A_HI, int B_LO, int B_HI, int NEG_LO, int NEG_HI>
+__device__ inline f32x2s pk_mul_vs(f32x2s a, f32x2s b) {
+    f32x2s d;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[%3,%4] op_sel_hi:[%5,%6] neg_lo:[0,%7] neg_hi:[0,%8]"
+        : "=v"(d) : "v"(a), "s"(b), "n"(A_LO), "n"(B_LO), "n"(A_HI), "n"(B_HI), "n"(NEG_LO), "n"(NEG_HI));
+    return d;
+}
+
+// (a[A_LO] +- b[B_LO], a[A_HI] +- b[B_HI])
+template <int A_LO, int A_HI, int B_LO, int B_HI, int NEG_LO, int NEG_HI>
+__device__ inline f32x2s pk_add_vv(f32x2s a, f32x2s b) {
+    f32x2s d;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[%3,%4] op_sel_hi:[%5,%6] neg_lo:[0,%7] neg_hi:[0,%8]"
+        : "=v"(d) : "v"(a), "v"(b), "n"(A_LO), "n"(B_LO), "n"(A_HI), "n"(B_HI), "n"(NEG_LO), "n"(NEG_HI));
+    return d;
+}
+
+// |cos(m pi / 12)| is one of seven values, cos(j pi / 12), j = 0 .. 6 (the last one zero): three pairs hold the other six, a
+// stage-2 constant is a half of one of them and its sign a lane negation
+__device__ constexpr int cos_fold(int m) {
+    const int r = ((m % 24) + 24) % 24, h = r >= 12 ? 24 - r : r;      // cos is even about 12 ...
+    return h > 6 ? 12 - h : h;                                          // ... and odd about 6
+}
+__device__ constexpr int cre_j(int m) { return cos_fold(m); }
+__device__ constexpr int cim_j(int m) { return cos_fold(m + 18); }
+
+template <int I, int N_, typename F>
+__device__ inline void static_for(F&& f) {
+    if constexpr (I < N_) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N_>(f);
+    }
+}
+
+// one constant's products with the two columns' G values, accumulated into acc0 (column v) and acc1 (column v + 6):
+// real constant k:  acc += (G.re, G.im) k ;  imaginary constant k:  acc += (-G.im, G.re) k
+// FIRST: the chain's first product (acc = product)
+template <int J, bool IMAG, bool NEGATIVE, bool FIRST>
+__device__ inline void spots_const_fma(f32x2s& acc0, f32x2s& acc1, f32x2s g0, f32x2s g1, const f32x2s (&cpair)[3]) {
+    constexpr int H = J & 1;
+    constexpr int NL = IMAG ? !NEGATIVE : NEGATIVE, NH = NEGATIVE;
+    if constexpr (FIRST && IMAG) {
+        acc0 = pk_mul_vs<1, 0, H, H, NL, NH>(g0, cpair[J / 2]);
+        acc1 = pk_mul_vs<1, 0, H, H, NL, NH>(g1, cpair[J / 2]);
+    } else if constexpr (FIRST) {
+        acc0 = pk_mul_vs<0, 1, H, H, NL, NH>(g0, cpair[J / 2]);
+        acc1 = pk_mul_vs<0, 1, H, H, NL, NH>(g1, cpair[J / 2]);
+    } else if constexpr (IMAG) {
+        pk_fma_vs<1, 0, H, H, NL, NH>(acc0, g0, cpair[J / 2]);
+        pk_fma_vs<1, 0, H, H, NL, NH>(acc1, g1, cpair[J / 2]);
+    } else {
+        pk_fma_vs<0, 1, H, H, NL, NH>(acc0, g0, cpair[J / 2]);
+        pk_fma_vs<0, 1, H, H, NL, NH>(acc1, g1, cpair[J / 2]);
+    }
+}
+
+template <int LOW_REGS = 0, bool PRESCALED = false>
+__device__ inline void lenslet_spots_pk(const cplx<float>* __restrict__ Ej, int q, float ctab, float (&Ia)[6], float (&Ib)[6]) {
+    const f32x2s cpair[3] = {{(float)kCos[0], (float)kCos[1]}, {(float)kCos[2], (float)kCos[3]}, {(float)kCos[4], (float)kCos[5]}};
+    f32x2s A[3], B[3];                                            // PRESCALED: the bins of the rows u / 2 and u / 2 + 3 as pairs
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { A[j] = f32x2s{Ia[j], Ia[j + 3]}; B[j] = f32x2s{Ib[j], Ib[j + 3]}; }
+#pragma unroll 1
+    for (int c = 0; c < 2; ++c) {
+        f32x2s t1[P];                                             // stage-1 twiddles of this lane's column, (re, im)
+#pragma unroll
+        for (int b = 0; b < P; ++b) {
+            const int x = (b + LO) * (13 + 2 * (2 * q + c));
+            const int m = x - 24 * ((x * 171) >> 12);
+            const int m2 = m + 18 >= 24 ? m - 6 : m + 18;
+            t1[b] = f32x2s{lane_read(ctab, m), lane_read(ctab, m2)};       // (cos, sin): the twiddle is (cos, -sin), negated in the products
+        }
+        f32x2s G0[P], G1[P];                                      // columns v and v + 6
+#pragma unroll
+        for (int a = 0; a < P; ++a) {
+            f32x2s ev, od;
+#pragma unroll
+            for (int b = 0; b < P; ++b) {
+                const f32x2s x = *reinterpret_cast<const f32x2s*>(&Ej[a * P + b]);
+                // x.re (cos, -sin) then x.im (sin, cos): with t1i = -sin, the plain form's fma(-x.im, t1i, .) is fma(x.im, sin, .)
+                if ((b + LO) % 2 == 0) {
+                    if (b == 1) ev = pk_mul_vv<0, 0, 0, 1, 0, 1>(x, t1[b]); else pk_fma_vv<0, 0, 0, 1, 0, 1>(ev, x, t1[b]);
+                    pk_fma_vv<1, 1, 1, 0, 0, 0>(ev, x, t1[b]);
+                } else {
+                    if (b == 0) od = pk_mul_vv<0, 0, 0, 1, 0, 1>(x, t1[b]); else pk_fma_vv<0, 0, 0, 1, 0, 1>(od, x, t1[b]);
+                    pk_fma_vv<1, 1, 1, 0, 0, 0>(od, x, t1[b]);
+                }
+            }
+            G0[a] = ev + od;
+            G1[a] = ev - od;
+            if (LOW_REGS > 0 && (a + 1) % LOW_REGS == 0) asm volatile("" ::: "memory");
+        }
+        static_for<0, P>([&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            f32x2s e0, o0, e1, o1;
+            static_for<0, P>([&](auto ac) {
+                constexpr int a = decltype(ac)::value;
+                constexpr double kr = cre(k2(u, a)), ki = cim(k2(u, a));
+                constexpr int jr = cre_j(k2(u, a)), ji = cim_j(k2(u, a));
+                static_assert((kr < 0 ? -kr : kr) == kCos[jr] && (ki < 0 ? -ki : ki) == kCos[ji], "a folded constant is the table's");
+                // a = 1 starts the even chains, a = 0 the odd ones: by the real product where there is one
+                constexpr bool start = a < 2;
+                if constexpr ((a + LO) % 2 == 0) {
+                    if constexpr (kr != 0) spots_const_fma<jr, false, (kr < 0), start>(e0, e1, G0[a], G1[a], cpair);
+                    if constexpr (ki != 0) spots_const_fma<ji, true, (ki < 0), (start && kr == 0)>(e0, e1, G0[a], G1[a], cpair);
+                } else {
+                    if constexpr (kr != 0) spots_const_fma<jr, false, (kr < 0), start>(o0, o1, G0[a], G1[a], cpair);
+                    if constexpr (ki != 0) spots_const_fma<ji, true, (ki < 0), (start && kr == 0)>(o0, o1, G0[a], G1[a], cpair);
+                }
+            });
+            if constexpr (PRESCALED) {
+                // rows u and u + 6 side by side, (re F[u], re F[u+6]) and (im F[u], im F[u+6]): each bin still gets re^2 then im^2
+                const f32x2s p0 = pk_add_vv<0, 0, 0, 0, 0, 1>(e0, o0), q0 = pk_add_vv<1, 1, 1, 1, 0, 1>(e0, o0);
+                pk_fma_vv<0, 1, 0, 1, 0, 0>(A[u / 2], p0, p0);                                      // (u, v) | (u+6, v)
+                pk_fma_vv<0, 1, 0, 1, 0, 0>(A[u / 2], q0, q0);
+                const f32x2s p1 = pk_add_vv<0, 0, 0, 0, 0, 1>(e1, o1), q1 = pk_add_vv<1, 1, 1, 1, 0, 1>(e1, o1);
+                pk_fma_vv<0, 1, 0, 1, 0, 0>(B[u / 2], p1, p1);                                      // (u, v+6) | (u+6, v+6)
+                pk_fma_vv<0, 1, 0, 1, 0, 0>(B[u / 2], q1, q1);
+            } else {
+                const float inv_n2 = (float)(1.0 / (N * N));
+                f32x2s f;
+                float fr_, fi_;
+                f = e0 + o0; fr_ = f.x; fi_ = f.y; Ia[u / 2] += (fr_ * fr_ + fi_ * fi_) * inv_n2;
+                f = e0 - o0; fr_ = f.x; fi_ = f.y; Ia[u / 2 + 3] += (fr_ * fr_ + fi_ * fi_) * inv_n2;
+                f = e1 + o1; fr_ = f.x; fi_ = f.y; Ib[u / 2] += (fr_ * fr_ + fi_ * fi_) * inv_n2;
+                f = e1 - o1; fr_ = f.x; fi_ = f.y; Ib[u / 2 + 3] += (fr_ * fr_ + fi_ * fi_) * inv_n2;
+            }
+        });
+    }
+    if constexpr (PRESCALED) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { Ia[j] = A[j].x; Ia[j + 3] = A[j].y; Ib[j] = B[j].x; Ib[j + 3] = B[j].y; }
+    }
+}
+
+// PAIRS selects the register-pair form (float32 only); the plain form serves double and AOENV_PATH_SH_PLAIN
+template <typename T, int LOW_REGS, bool PRESCALED, bool PAIRS>
+__device__ inline void lenslet_spots_sel(const cplx<T>* __restrict__ Ej, int q, T ctab, T (&Ia)[6], T (&Ib)[6]) {
+    if constexpr (PAIRS && sizeof(T) == 4) lenslet_spots_pk<LOW_REGS, PRESCALED>(Ej, q, ctab, Ia, Ib);
+    else lenslet_spots<T, LOW_REGS, PRESCALED>(Ej, q, ctab, Ia, Ib);
+}
 }  // namespace fast6
 
 // Scalar telemetry of one env from the pupil sums v = {Sum atm, Sum atm^2, Sum res, Sum res^2} of the OPD [m]:

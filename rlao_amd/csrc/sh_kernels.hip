@@ -115,7 +115,8 @@ __global__ void __launch_bounds__(256) k_sh_spots(const T* __restrict__ phase, c
 // centring phasor exp(-i pi (n+1)/n (x+y)) = ph_a ph_b is folded into the twiddles.
 // ---------------------------------------------------------------------------------------------------
 
-template <typename T, bool FAST_TRIG>
+// PAIRS: the float32 register-pair form of the transform (sh_device.hpp); without it, and in double, the plain one
+template <typename T, bool FAST_TRIG, bool PAIRS>
 __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ phase, const ShConst<T> sc,
                                                      const uint8_t* __restrict__ valid2d, T* __restrict__ frame,
                                                      T* __restrict__ wfs_max, int R, int n_subap) {
@@ -175,7 +176,7 @@ __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ ph
 #pragma unroll
         for (int u = 0; u < P; ++u) Ia[u] = Ib[u] = (T)0;
         if (lit)                                                       // wave-uniform: the twiddle shuffles need every lane
-            lenslet_spots<T>(Ew + (lane < SPW * HP ? jl : 0) * EST, q, ctab, Ia, Ib);
+            lenslet_spots_sel<T, 0, false, PAIRS>(Ew + (lane < SPW * HP ? jl : 0) * EST, q, ctab, Ia, Ib);
         if (!ok) {
 #pragma unroll
             for (int u = 0; u < P; ++u) Ia[u] = Ib[u] = (T)0;
@@ -218,11 +219,22 @@ int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, 
     if (p == fast6::P && sc.valid2d != nullptr) {
         const size_t lds6 = 2 * (sizeof(cplx<T>) * fast6::SPW * fast6::EST + sizeof(T) * fast6::P * fast6::SPW * fast6::P);
         dim3 grid6(cdiv(n_subap, 2), n_env);
-        if (sc.fast_trig)
-            hipLaunchKernelGGL((k_sh_spots_p6<T, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+        bool pairs = false;
+        if constexpr (sizeof(T) == 4) {
+            pairs = !sc.plain;
+            if (pairs && sc.fast_trig)
+                hipLaunchKernelGGL((k_sh_spots_p6<T, true, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+                                   wfs_max, R, n_subap);
+            else if (pairs)
+                hipLaunchKernelGGL((k_sh_spots_p6<T, false, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+                                   wfs_max, R, n_subap);
+        }
+        if (pairs) {
+        } else if (sc.fast_trig)
+            hipLaunchKernelGGL((k_sh_spots_p6<T, true, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
                                wfs_max, R, n_subap);
         else
-            hipLaunchKernelGGL((k_sh_spots_p6<T, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+            hipLaunchKernelGGL((k_sh_spots_p6<T, false, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
                                wfs_max, R, n_subap);
         AO_HIP(hipGetLastError());
         return 0;
