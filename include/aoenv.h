@@ -338,6 +338,37 @@ int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream);  
 int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* stream);
 int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream);
 
+/* Replaces: OOPAOEnvRazor.change_mag (MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647: source.nPhoton = zeroPoint 10^(-0.4 mag), then
+ * source * tel * wfs) and the assignment env.wfs.threshold_cog = t, as the noise study makes them between its serial runs
+ * (MAIN/OOPAOEnvRazor/integrator_threshold.py:34-106: six thresholds for each of six magnitudes) -- for the envs of ONE shard: every
+ * env its own guide-star flux and its own centroid threshold, one calibration.
+ * The model (OOPAO/Source.py:109, 151; OOPAO/ShackHartmann.py:327-338, 515-517; rlao_amd/csrc/star_env.hpp): fluxMap is linear in
+ * nPhoton and the WFS amplitude is sqrt(fluxMap); the valid lenslets / pixels are chosen relative to the maximum and the reference
+ * slopes and slope units are measured on ideal intensities, so none of them moves with the flux.  Env e is therefore the calibrated
+ * shard with every WFS amplitude multiplied by a_e = sqrt(h_scale[e]): one multiply in the env dtype where a kernel loads the
+ * amplitude (both Shack-Hartmann spot kernels, both Pyramid row kernels, the fused step kernel), the product rounded once -- the bits
+ * of a shard whose AOENV_C_WFS_AMP was replaced by the rounded product.  The reconstructor, the modal basis, the photon-noise tables
+ * and their range stay those of the calibration, as change_mag leaves them.  The env's threshold takes the place of
+ * AoCfg.threshold_cog in  I < thr max -> 0  (ShackHartmann.py:314-324) in the centroid kernel, the fused tail and the fused step kernel.
+ * h_scale [n_env]: flux relative to the uploaded AOENV_C_WFS_AMP, finite and > 0; the host forms sqrt in float64 and stores it in the
+ * env dtype, h_scale[e] == 1 gives exactly 1.  h_thr [n_env]: finite and >= 0, stored in the env dtype.
+ * NULL: back to one value for the shard; the array is then absent (freed), not filled with ones, and the kernels are handed a null
+ * pointer: a shard that never made the call, and one that returned, run what they ran before.  With either array present a shard in
+ * the fused step kernel's envelope runs an instantiation of that kernel of its own; aoenv_fused_step_active stays 1.
+ * Both are configuration, as the per-env mirrors are: copied before the call returns (the stream is waited for once), not loop state,
+ * not in the checkpoint buffers, no buffer id; aoenv_reset_envs and aoenv_new_screens* leave them alone.  Everything that steps or
+ * measures follows without a new argument: aoenv_step, aoenv_measure, aoenv_reset_soft, aoenv_run_integrator, both recorded
+ * rollouts, the modal surface, a delay, a disturbance.  aoenv_compute_psf keeps the calibrated star: the PSF's flux is not per env.
+ * Refused, with nothing changed: a non-finite entry, a scale <= 0, a threshold < 0; aoenv_set_threshold_env on a Pyramid shard (no
+ * centre of gravity) and on a shard with max_group > 1 (the envs of a batch share the threshold maximum: the interaction-matrix
+ * emulation); an allocation that fails.
+ * aoenv_get_flux_env fills h_amp [n_env] with the amplitude factors a_e as held (env dtype widened to float64), aoenv_get_threshold_env
+ * h_thr [n_env] likewise.  Each fails while its array is absent. */
+int aoenv_set_flux_env(AoEnv* env, const double* h_scale, void* stream);
+int aoenv_get_flux_env(AoEnv* env, double* h_amp, void* stream);
+int aoenv_set_threshold_env(AoEnv* env, const double* h_thr, void* stream);
+int aoenv_get_threshold_env(AoEnv* env, double* h_thr, void* stream);
+
 /* Replaces: TimeDelayEnv (MAIN/PO4AO/util_simple.py:25-52, the contract is :46-52: append the action, apply action_buffer[0], drop
  * it), which both trainer mains put around the env with delay = 1 (MAIN/mbrl_main.py:46, MAIN/mbrl_main_network.py:41,
  * MAIN/PO4AO/mbrl_funcsRAZOR.py:32-33), and the action_buffer every gymnasium env of the reference carries (OOPAOEnv_VPG.py:562-566,

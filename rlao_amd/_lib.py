@@ -100,6 +100,10 @@ EXPORTS = {
                                              C.c_void_p]),
     "aoenv_set_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_flux_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_flux_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_threshold_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_threshold_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_delay": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_get_delay": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "aoenv_get_delay_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

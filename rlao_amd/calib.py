@@ -126,6 +126,15 @@ def source(band: str, magnitude: float):
     return wl, (zp / 368) * 10 ** (-0.4 * magnitude)
 
 
+def flux_scale(magnitude, magnitude_cal):
+    """Flux of a star of ``magnitude`` relative to one of ``magnitude_cal``: the ratio of their ``nPhoton`` (OOPAO/Source.py:109;
+    ``change_mag``, MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647), the zero point cancelling.  Formed as the quotient of the two
+    powers of ten, so that it is within three roundings of ``source(b, m)[1] / source(b, m_cal)[1]`` and exactly 1 where the
+    magnitudes are equal.  Scalars or arrays, float64."""
+    m = np.asarray(magnitude, dtype=np.float64)
+    return 10 ** (-0.4 * m) / 10 ** (-0.4 * np.float64(magnitude_cal))
+
+
 # ------------------------------------------------------------------------------------------------------
 # Atmosphere tables
 # ------------------------------------------------------------------------------------------------------

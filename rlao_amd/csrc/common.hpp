@@ -262,11 +262,18 @@ struct ShConst {
     int fast_trig;           // 1: hardware sin/cos after Cody-Waite reduction (float32 shards only)
     int plain;               // 1: AOENV_PATH_SH_PLAIN, the plain lenslet transform and the general fused step kernel
 };
+// every env its own guide star (aoenv_set_flux_env, aoenv_set_threshold_env; the model is star_env.hpp): beside ShConst, not in it,
+// so that the argument block of the fused step kernel's specialised instantiations stays what it was
 template <typename T>
-int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, int n_env, int R, int n_subap,
+struct StarEnv {
+    const T* amp;            // [E] factor of ShConst::amp, sqrt of the env's flux relative to the calibrated star; null = 1 for every env
+    const T* thr;            // [E] the env's centroid threshold in place of ShConst::threshold; null = that one
+};
+template <typename T>
+int launch_sh_spots(const T* phase, const ShConst<T>& sc, const T* amp_env, T* frame, T* wfs_max, int n_env, int R, int n_subap,
                     int n_valid, hipStream_t st);
 template <typename T>
-int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, T* signal, int n_env, int R,
+int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, int n_env, int R,
                        int n_subap, int n_valid, int max_group, hipStream_t st);
 
 // Step epilogue (one workgroup per env): reconstruction image, reward, integrator, telemetry scalars.
@@ -296,7 +303,7 @@ template <typename T>
 int launch_recon_finish(const FinishArgs<T>& fa, int n_env, hipStream_t st);
 // fused SH tail: centroid + low-rank R.s + epilogue in one launch; -1 if it does not fit in LDS
 template <typename T>
-int launch_sh_tail(const T* frame, const T* wfs_max, const ShConst<T>& sc, T* signal, const T* fac_m,
+int launch_sh_tail(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, const T* fac_m,
                    const T* fac_m2c_t, int n_modes, const FinishArgs<T>& fa, int n_env, int R, int n_subap, int n_valid,
                    int max_group, hipStream_t st);
 // WFS camera model (detector.hpp)
@@ -348,7 +355,8 @@ struct StepArgs {
 };
 int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes);
 int step_alias_capacity(int n_act);
-int launch_env_step(const StepArgs& a, hipStream_t st);
+// star: the per-env amplitude factors and thresholds; with either set the launch runs the STEP_STAR instantiation
+int launch_env_step(const StepArgs& a, const StarEnv<float>& star, hipStream_t st);
 
 // exploration action of aoenv_run_rollout (rollout_kernels.hip): action = gain * obs + sigma_e vec_to_img(Fl (Fr z)), z from explore.hpp
 template <typename T>
@@ -450,6 +458,7 @@ template <typename T>
 struct PyrArgs {
     const T* phase;        // [E][R*R]
     const T* amp;          // [R*R]   sqrt(flux / nTheta) * reflectivity
+    const T* amp_env;      // [E] per-env factor of amp (aoenv_set_flux_env), or null: one star for the shard
     const T* tt;           // [nTheta][R*R] modulation tip/tilt (float32-rounded in the reference) or null
     const T* mask;         // [N*N][2] exp(i m), complex64-rounded
     const T* tw;           // [N][2]

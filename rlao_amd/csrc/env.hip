@@ -16,6 +16,7 @@
 #include "modal.hpp"
 #include "policy.hpp"
 #include "sh_device.hpp"
+#include "star_env.hpp"
 
 namespace ao {
 
@@ -176,6 +177,13 @@ struct AoEnv {
         void *gx = nullptr, *gy = nullptr, *gxt = nullptr;
         float *gxa = nullptr, *gya = nullptr;
     } dm_env;
+    // per-env guide stars (aoenv_set_flux_env / aoenv_set_threshold_env, star_env.hpp): [E] each in the env dtype, an allocation of
+    // its own each (not in `allocs`: NULL frees it); absent = null, and the kernels are then handed null pointers
+    struct StarDev {
+        void* amp = nullptr;                // sqrt of the env's flux relative to the uploaded AOENV_C_WFS_AMP
+        void* thr = nullptr;                // the env's centroid threshold
+    } star;
+    template <typename T> StarEnv<T> star_env() const { return StarEnv<T>{static_cast<const T*>(star.amp), static_cast<const T*>(star.thr)}; }
     DmLayout dm_layout() const { DmLayout l; l.R = R; l.n_act = nAct; l.ga_stride = ga_stride; return l; }
     std::vector<uint8_t> h_pupil;           // host copies, to rebuild amp_pupil
     std::vector<double> h_amp;
@@ -642,7 +650,7 @@ template <typename T>
 int run_spots_and_camera(AoEnv* env, const ShConst<T>& sc, hipStream_t st) {
     {
         AO_PROF(env, SH_SPOTS, st);
-        AO_TRY(launch_sh_spots<T>(env->as<T>(env->phase), sc, env->as<T>(env->frame), env->as<T>(env->wfs_max), env->E,
+        AO_TRY(launch_sh_spots<T>(env->as<T>(env->phase), sc, env->star_env<T>().amp, env->as<T>(env->frame), env->as<T>(env->wfs_max), env->E,
                                   env->R, env->nSub, env->nVal, st));
     }
     return apply_detector<T>(env, true, st);
@@ -656,6 +664,7 @@ int run_wfs(AoEnv* env, hipStream_t st) {
         PyrArgs<T> pa{};
         pa.phase = env->as<T>(env->phase);
         pa.amp = env->as<T>(env->amp);
+        pa.amp_env = env->star_env<T>().amp;
         pa.tt = env->c.pyr_n_theta > 1 ? env->as<T>(env->pyr_tt) : nullptr;
         pa.mask = env->as<T>(env->pyr_mask);
         pa.tw = env->as<T>(env->pyr_tw);
@@ -692,7 +701,7 @@ int run_wfs(AoEnv* env, hipStream_t st) {
     AO_TRY(run_spots_and_camera<T>(env, sc, st));                  // spots, self*self.cam (OOPAO/ShackHartmann.py:539-576)
     {
         AO_PROF(env, SH_CENTROID, st);
-        AO_TRY(launch_sh_centroid<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->as<T>(env->signal),
+        AO_TRY(launch_sh_centroid<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->star_env<T>().thr, env->as<T>(env->signal),
                                      env->E, env->R, env->nSub, env->nVal, env->c.max_group, st));
     }
     return 0;
@@ -901,7 +910,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.n_env = env->E;
     {
         AO_PROF(env, ENV_STEP, st);
-        AO_TRY(launch_env_step(a, st));
+        AO_TRY(launch_env_step(a, env->star_env<float>(), st));
     }
     rings_written(env);
     return 0;
@@ -994,7 +1003,7 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
         int rc;
         {
             AO_PROF(env, SH_TAIL, st);
-            rc = launch_sh_tail<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->as<T>(env->signal),
+            rc = launch_sh_tail<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->star_env<T>().thr, env->as<T>(env->signal),
                                    env->as<T>(env->fac_m), env->as<T>(env->fac_m2c_t), env->n_modes, fa, env->E, env->R,
                                    env->nSub, env->nVal, env->c.max_group, st);
         }
@@ -1004,7 +1013,7 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
         } else {                                                   // does not fit in LDS: the separate kernels
             {
                 AO_PROF(env, SH_CENTROID, st);
-                AO_TRY(launch_sh_centroid<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->as<T>(env->signal),
+                AO_TRY(launch_sh_centroid<T>(env->as<T>(env->frame), env->as<T>(env->wfs_max), sc, env->star_env<T>().thr, env->as<T>(env->signal),
                                              env->E, env->R, env->nSub, env->nVal, env->c.max_group, st));
             }
             AO_TRY(run_recon<T>(env, static_cast<const T*>(d_action), static_cast<T*>(d_obs), static_cast<T*>(d_reward),
@@ -1374,6 +1383,8 @@ int aoenv_destroy(AoEnv* env) {
     for (auto& e : env->prof_ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (void* p : env->allocs) (void)hipFree(p);
     if (env->dm_env.base) (void)hipFree(env->dm_env.base);
+    if (env->star.amp) (void)hipFree(env->star.amp);
+    if (env->star.thr) (void)hipFree(env->star.thr);
     if (env->modal.base) (void)hipFree(env->modal.base);
     delete env;
     return 0;
@@ -2279,6 +2290,83 @@ int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
     if (!env->dm_env.on) return fail("aoenv_get_dm_env: the shard shares one mirror (aoenv_set_dm_env has not been called)");
     AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return env->c.dtype == AOENV_F32 ? get_dm_env_t<float>(env, h_gx, h_gy) : get_dm_env_t<double>(env, h_gx, h_gy);
+}
+
+// ---- per-env guide stars (star_env.hpp) ------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// one [E] array of the env dtype in an allocation of its own: `h` (already validated) through `fill`, or freed when h is null
+template <typename T, typename Fill>
+int set_star_row_t(AoEnv* env, void** slot, const double* h, Fill fill, const char* who, hipStream_t st) {
+    std::vector<T> t((size_t)env->E);
+    fill(h, env->E, t.data());
+    AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the array in place
+    void* p = *slot;
+    if (!p && hipMalloc(&p, t.size() * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("%s: no device memory for %d values", who, env->E);
+    }
+    if (hipMemcpy(p, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        if (!*slot) (void)hipFree(p);
+        return fail("%s: the copy to the device failed", who);     // (an array already held keeps being used: same size, same place)
+    }
+    *slot = p;
+    return 0;
+}
+int clear_star_row(void** slot, hipStream_t st) {
+    if (*slot) {
+        AO_HIP(hipStreamSynchronize(st));
+        (void)hipFree(*slot);
+        *slot = nullptr;
+    }
+    return 0;
+}
+template <typename T>
+int get_star_row_t(const AoEnv* env, const void* src, double* dst) {
+    std::vector<T> t((size_t)env->E);
+    AO_HIP(hipMemcpy(t.data(), src, t.size() * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < t.size(); ++i) dst[i] = (double)t[i];
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int aoenv_set_flux_env(AoEnv* env, const double* h_scale, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_scale) return clear_star_row(&env->star.amp, st);
+    char msg[96];
+    if (star_flux_check(h_scale, env->E, msg, sizeof msg)) return fail("aoenv_set_flux_env: %s", msg);
+    return env->c.dtype == AOENV_F32 ? set_star_row_t<float>(env, &env->star.amp, h_scale, star_amp_factors<float>, "aoenv_set_flux_env", st)
+                                     : set_star_row_t<double>(env, &env->star.amp, h_scale, star_amp_factors<double>, "aoenv_set_flux_env", st);
+}
+
+int aoenv_get_flux_env(AoEnv* env, double* h_amp, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_amp) return fail("aoenv_get_flux_env: null destination");
+    if (!env->star.amp) return fail("aoenv_get_flux_env: the shard has one star (aoenv_set_flux_env has not been called)");
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return env->c.dtype == AOENV_F32 ? get_star_row_t<float>(env, env->star.amp, h_amp) : get_star_row_t<double>(env, env->star.amp, h_amp);
+}
+
+int aoenv_set_threshold_env(AoEnv* env, const double* h_thr, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_thr) return clear_star_row(&env->star.thr, st);
+    if (const char* why = star_threshold_refusal(env->c.wfs_type == AOENV_WFS_PYRAMID, env->c.max_group)) return fail("aoenv_set_threshold_env: %s", why);
+    char msg[96];
+    if (star_threshold_check(h_thr, env->E, msg, sizeof msg)) return fail("aoenv_set_threshold_env: %s", msg);
+    return env->c.dtype == AOENV_F32 ? set_star_row_t<float>(env, &env->star.thr, h_thr, star_thresholds<float>, "aoenv_set_threshold_env", st)
+                                     : set_star_row_t<double>(env, &env->star.thr, h_thr, star_thresholds<double>, "aoenv_set_threshold_env", st);
+}
+
+int aoenv_get_threshold_env(AoEnv* env, double* h_thr, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_thr) return fail("aoenv_get_threshold_env: null destination");
+    if (!env->star.thr) return fail("aoenv_get_threshold_env: the shard has one threshold (aoenv_set_threshold_env has not been called)");
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return env->c.dtype == AOENV_F32 ? get_star_row_t<float>(env, env->star.thr, h_thr) : get_star_row_t<double>(env, env->star.thr, h_thr);
 }
 
 // ---- the modal control surface (modal.hpp) ----------------------------------------------------------------------------------------

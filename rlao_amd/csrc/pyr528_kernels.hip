@@ -118,6 +118,7 @@ __global__ void __launch_bounds__(F::lanes(SEQS)) k_pyr528_rows(const PyrArgs<fl
         const float* ph = a.phase + (size_t)e * R * R;
         const float* tt = a.tt ? a.tt + (size_t)(a.theta0 + th) * R * R : nullptr;
         const float pi_over_n = (float)(3.14159265358979323846 / N);
+        const float star = a.amp_env ? a.amp_env[e] : 1.f;        // the env's own guide star (aoenv_set_flux_env): workgroup-uniform
         // four points per lane and turn: their loads are independent of one another and issued together (one point at a time,
         // amplitude -> branch -> phase is a chain of two memory latencies per point: 20 us per workgroup)
         for (int i0 = tid; i0 < SEQS * W; i0 += 4 * LANES) {
@@ -132,6 +133,7 @@ __global__ void __launch_bounds__(F::lanes(SEQS)) k_pyr528_rows(const PyrArgs<fl
                 const bool in = i < SEQS * W && row < R && (unsigned)x < (unsigned)R;
                 const int p = in ? row * R + x : 0;
                 am[u] = in ? a.amp[p] : 0.f;
+                if (a.amp_env) am[u] = am[u] * star;
                 ang[u] = ph[p];
                 if (tt) ang[u] += tt[p];
             }

@@ -37,6 +37,7 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 ? 4 : 1) k_pyr_rows(const 
     const T* ph = a.phase + (size_t)e * R * R;
     const T* tt = a.tt ? a.tt + (size_t)(a.theta0 + th) * R * R : nullptr;
     const T pi_over_n = (T)(3.14159265358979323846 / N);
+    const T star = a.amp_env ? a.amp_env[e] : (T)1;             // the env's own guide star (aoenv_set_flux_env): workgroup-uniform
     // (loops are (sequence, element) nests: an integer division by a run-time N per element costs as much as the butterflies)
     const int two_n = 2 * N;
     for (int r = 0; r < RB; ++r)
@@ -45,7 +46,8 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 ? 4 : 1) k_pyr_rows(const 
         const int x = xg - a.off;
         if (r < nrow && x >= 0 && x < R) {
             const int p = (y0 + r) * R + x;
-            const T am = a.amp[p];
+            T am = a.amp[p];
+            if (a.amp_env) am = am * star;
             if (am != (T)0) {
                 T ang = ph[p];
                 if (tt) ang += tt[p];

@@ -18,7 +18,7 @@ namespace ao {
 // (the reference tiles phase.T, so the spot image is transposed inside its camera block).
 template <typename T>
 __global__ void __launch_bounds__(256) k_sh_spots(const T* __restrict__ phase, const ShConst<T> sc,
-                                                  T* __restrict__ frame, T* __restrict__ wfs_max, int R, int n_subap,
+                                                  const T* __restrict__ amp_env, T* __restrict__ frame, T* __restrict__ wfs_max, int R, int n_subap,
                                                   int n_valid) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int p = R / n_subap, n = 2 * p, lo = n / 2 - p / 2;
@@ -34,13 +34,15 @@ __global__ void __launch_bounds__(256) k_sh_spots(const T* __restrict__ phase, c
     const bool active = s < n_valid;          // no early return: the barriers below are workgroup-wide
     const int k = active ? sc.subap_idx[s] : 0, i = k / n_subap, j = k % n_subap;
     const T* ph = phase + (size_t)e * R * R;
+    const T star = amp_env ? amp_env[e] : (T)1;               // the env's own guide star: workgroup-uniform, null = the shard's
 
     for (int idx = lane; active && idx < p * p; idx += kWave) {
         const int a = idx / p, b = idx % p;
         const int pix = (i * p + b) * R + (j * p + a);
         T sn, cs;
         sincos_t<T>(ph[pix], &sn, &cs);
-        const T am = sc.amp[pix];
+        T am = sc.amp[pix];
+        if (amp_env) am = am * star;
         // phasor exp(-i pi (n+1)/n (x + y)) = ph[a] * ph[b]
         const T pr = sc.ph[2 * a] * sc.ph[2 * b] - sc.ph[2 * a + 1] * sc.ph[2 * b + 1];
         const T pi = sc.ph[2 * a] * sc.ph[2 * b + 1] + sc.ph[2 * a + 1] * sc.ph[2 * b];
@@ -118,8 +120,8 @@ __global__ void __launch_bounds__(256) k_sh_spots(const T* __restrict__ phase, c
 // PAIRS: the float32 register-pair form of the transform (sh_device.hpp); without it, and in double, the plain one
 template <typename T, bool FAST_TRIG, bool PAIRS>
 __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ phase, const ShConst<T> sc,
-                                                     const uint8_t* __restrict__ valid2d, T* __restrict__ frame,
-                                                     T* __restrict__ wfs_max, int R, int n_subap) {
+                                                     const uint8_t* __restrict__ valid2d, const T* __restrict__ amp_env,
+                                                     T* __restrict__ frame, T* __restrict__ wfs_max, int R, int n_subap) {
     using namespace fast6;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
@@ -135,6 +137,7 @@ __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ ph
     const int jl = lane / HP, q = lane - jl * HP;
 
     const T ctab = cos_table_lane<T>();
+    const T star = amp_env ? amp_env[e] : (T)1;               // the env's own guide star: workgroup-uniform, null = the shard's
     T mx = 0;
     for (int j0 = 0; j0 < n_subap; j0 += SPW) {
         // a strip without a valid lenslet (the corners of the lenslet array: 7 % of the strips of an 80 x 80 array) is all zeros
@@ -154,6 +157,7 @@ __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ ph
             if (lit && t < P * W && col < R) {
                 const int pix = (i * P + b) * R + col;
                 amv[k] = sc.amp[pix];
+                if (amp_env) amv[k] = amv[k] * star;
                 phv[k] = ph[pix];
             }
         }
@@ -213,7 +217,7 @@ __global__ void __launch_bounds__(128, 2) k_sh_spots_p6(const T* __restrict__ ph
 }
 
 template <typename T>
-int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, int n_env, int R, int n_subap,
+int launch_sh_spots(const T* phase, const ShConst<T>& sc, const T* amp_env, T* frame, T* wfs_max, int n_env, int R, int n_subap,
                     int n_valid, hipStream_t st) {
     const int p = R / n_subap, n = 2 * p;
     if (p == fast6::P && sc.valid2d != nullptr) {
@@ -223,18 +227,18 @@ int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, 
         if constexpr (sizeof(T) == 4) {
             pairs = !sc.plain;
             if (pairs && sc.fast_trig)
-                hipLaunchKernelGGL((k_sh_spots_p6<T, true, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+                hipLaunchKernelGGL((k_sh_spots_p6<T, true, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, amp_env, frame,
                                    wfs_max, R, n_subap);
             else if (pairs)
-                hipLaunchKernelGGL((k_sh_spots_p6<T, false, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+                hipLaunchKernelGGL((k_sh_spots_p6<T, false, true>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, amp_env, frame,
                                    wfs_max, R, n_subap);
         }
         if (pairs) {
         } else if (sc.fast_trig)
-            hipLaunchKernelGGL((k_sh_spots_p6<T, true, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+            hipLaunchKernelGGL((k_sh_spots_p6<T, true, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, amp_env, frame,
                                wfs_max, R, n_subap);
         else
-            hipLaunchKernelGGL((k_sh_spots_p6<T, false, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, frame,
+            hipLaunchKernelGGL((k_sh_spots_p6<T, false, false>), grid6, dim3(128), lds6, st, phase, sc, sc.valid2d, amp_env, frame,
                                wfs_max, R, n_subap);
         AO_HIP(hipGetLastError());
         return 0;
@@ -242,7 +246,7 @@ int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, 
     const size_t lds = sizeof(cplx<T>) * (n + 4 * (p * p + p * n));
     if (lds > 64 * 1024) return fail("sh_spots: %d px per lenslet needs %zu B of LDS", p, lds);
     dim3 grid(cdiv(n_valid, 4), n_env);
-    hipLaunchKernelGGL(k_sh_spots<T>, grid, dim3(256), lds, st, phase, sc, frame, wfs_max, R, n_subap, n_valid);
+    hipLaunchKernelGGL(k_sh_spots<T>, grid, dim3(256), lds, st, phase, sc, amp_env, frame, wfs_max, R, n_subap, n_valid);
     AO_HIP(hipGetLastError());
     return 0;
 }
@@ -252,8 +256,8 @@ int launch_sh_spots(const T* phase, const ShConst<T>& sc, T* frame, T* wfs_max, 
 // all of them are in flight at once; the three partial sums are folded across the 8 lanes with DPP shuffles.
 template <typename T>
 __global__ void __launch_bounds__(256) k_sh_centroid(const T* __restrict__ frame, const T* __restrict__ wfs_max,
-                                                     const ShConst<T> sc, T* __restrict__ signal, int R, int n_subap,
-                                                     int n_valid, int max_group, int n_env) {
+                                                     const ShConst<T> sc, const T* __restrict__ thr_env, T* __restrict__ signal,
+                                                     int R, int n_subap, int n_valid, int max_group, int n_env) {
     const int e = blockIdx.y;
     const int p = R / n_subap;
     // envs of one measurement batch share the threshold maximum (ShackHartmann.py:605-660)
@@ -261,7 +265,7 @@ __global__ void __launch_bounds__(256) k_sh_centroid(const T* __restrict__ frame
     const int g1 = min(g0 + max_group, n_env);
     T mx = 0;
     for (int q = g0; q < g1; ++q) mx = wfs_max[q] > mx ? wfs_max[q] : mx;
-    const T cut = sc.threshold * mx;
+    const T cut = (thr_env ? thr_env[e] : sc.threshold) * mx;   // (the env's own threshold: workgroup-uniform)
     const T* fr = frame + (size_t)e * R * R;
     T* sg = signal + (size_t)e * 2 * n_valid;
     const int s = blockIdx.x * 32 + (threadIdx.x >> 3), sub = threadIdx.x & 7;
@@ -312,9 +316,9 @@ __global__ void __launch_bounds__(256) k_sh_centroid(const T* __restrict__ frame
 }
 
 template <typename T>
-int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, T* signal, int n_env, int R,
+int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, int n_env, int R,
                        int n_subap, int n_valid, int max_group, hipStream_t st) {
-    hipLaunchKernelGGL(k_sh_centroid<T>, dim3(cdiv(n_valid, 32), n_env), dim3(256), 0, st, frame, wfs_max, sc, signal,
+    hipLaunchKernelGGL(k_sh_centroid<T>, dim3(cdiv(n_valid, 32), n_env), dim3(256), 0, st, frame, wfs_max, sc, thr_env, signal,
                        R, n_subap, n_valid, max_group, n_env);
     AO_HIP(hipGetLastError());
     return 0;
@@ -331,7 +335,7 @@ int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, T
 // ---------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(1024) k_sh_tail(const T* __restrict__ frame, const T* __restrict__ wfs_max,
-                                                   const ShConst<T> sc, T* __restrict__ signal,
+                                                   const ShConst<T> sc, const T* __restrict__ thr_env, T* __restrict__ signal,
                                                    const T* __restrict__ fac_m, const T* __restrict__ fac_m2c_t,
                                                    int n_modes, const FinishArgs<T> f, int R, int n_subap,
                                                    int n_valid, int max_group, int n_env) {
@@ -344,7 +348,7 @@ __global__ void __launch_bounds__(1024) k_sh_tail(const T* __restrict__ frame, c
     const int g0 = (e / max_group) * max_group, g1 = min(g0 + max_group, n_env);
     T mx = 0;
     for (int q = g0; q < g1; ++q) mx = wfs_max[q] > mx ? wfs_max[q] : mx;
-    const T cut = sc.threshold * mx;
+    const T cut = (thr_env ? thr_env[e] : sc.threshold) * mx;   // (the env's own threshold: workgroup-uniform)
     const T* fr = frame + (size_t)e * R * R;
     const int img = f.n_act * f.n_act;
     for (int q = tid; q < img; q += blockDim.x) img_s[q] = (T)0;
@@ -398,22 +402,22 @@ __global__ void __launch_bounds__(1024) k_sh_tail(const T* __restrict__ frame, c
 }
 
 template <typename T>
-int launch_sh_tail(const T* frame, const T* wfs_max, const ShConst<T>& sc, T* signal, const T* fac_m,
+int launch_sh_tail(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, const T* fac_m,
                    const T* fac_m2c_t, int n_modes, const FinishArgs<T>& fa, int n_env, int R, int n_subap, int n_valid,
                    int max_group, hipStream_t st) {
     const size_t lds = sizeof(T) * ((size_t)2 * n_valid + (size_t)fa.n_act * fa.n_act + (size_t)n_modes);
     if (lds > 64 * 1024) return -1;
-    hipLaunchKernelGGL(k_sh_tail<T>, dim3(n_env), dim3(1024), lds, st, frame, wfs_max, sc, signal, fac_m, fac_m2c_t,
+    hipLaunchKernelGGL(k_sh_tail<T>, dim3(n_env), dim3(1024), lds, st, frame, wfs_max, sc, thr_env, signal, fac_m, fac_m2c_t,
                        n_modes, fa, R, n_subap, n_valid, max_group, n_env);
     AO_HIP(hipGetLastError());
     return 0;
 }
 
 #define INST(T)                                                                                                 \
-    template int launch_sh_spots<T>(const T*, const ShConst<T>&, T*, T*, int, int, int, int, hipStream_t);      \
-    template int launch_sh_centroid<T>(const T*, const T*, const ShConst<T>&, T*, int, int, int, int, int,      \
+    template int launch_sh_spots<T>(const T*, const ShConst<T>&, const T*, T*, T*, int, int, int, int, hipStream_t); \
+    template int launch_sh_centroid<T>(const T*, const T*, const ShConst<T>&, const T*, T*, int, int, int, int, int, \
                                        hipStream_t);                                                            \
-    template int launch_sh_tail<T>(const T*, const T*, const ShConst<T>&, T*, const T*, const T*, int,         \
+    template int launch_sh_tail<T>(const T*, const T*, const ShConst<T>&, const T*, T*, const T*, const T*, int, \
                                    const FinishArgs<T>&, int, int, int, int, int, hipStream_t);
 INST(float)
 INST(double)

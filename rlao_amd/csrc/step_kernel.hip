@@ -1,6 +1,6 @@
 // The fused step kernel's host side: its LDS layout, the envelope it serves and the choice of the instantiation for a launch.
 // The kernel is step_kernel_body.hpp; its instantiations are compiled in step_kernel_general.hip, step_kernel_nocam.hip,
-// step_kernel_photon.hip and step_kernel_camera.hip.
+// step_kernel_photon.hip, step_kernel_camera.hip and step_kernel_star.hip.
 #include "step_kernel.hpp"
 
 #include "sh_device.hpp"
@@ -44,18 +44,20 @@ int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes
 // tables that fits there for ALL its camera kernels, so that a pixel is drawn the same way whichever kernel meets it
 int step_alias_capacity(int n_act) { return step_lds_layout(n_act, 1, 1, 1).tab_cap; }
 
-int launch_env_step(const StepArgs& a, hipStream_t st) {
+int launch_env_step(const StepArgs& a, const StarEnv<float>& star, hipStream_t st) {
     const StepLds L = step_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
     if (a.det.active && a.det.photon_noise && (!a.pa.tab || a.pa.words > L.tab_cap || a.pa.lmax < palias::kCoarseStep))
         return fail("fused step: the photon-noise tables are missing or do not fit (%d words, room for %d)", a.pa.words, L.tab_cap);
-    // the instantiation: the general one without fast trig or under AOENV_PATH_SH_PLAIN, else by the camera's kind
-    if (!a.sc.fast_trig || a.sc.plain) return launch_env_step_spec<STEP_GENERAL>(a, L, st);
-    if (!a.det.active) return launch_env_step_spec<STEP_NOCAM>(a, L, st);
+    // the instantiation: per-env stars have their own; the general one without fast trig or under AOENV_PATH_SH_PLAIN, else by the
+    // camera's kind
+    if (star.amp || star.thr) return launch_env_step_spec<STEP_STAR>(a, L, star, st);
+    if (!a.sc.fast_trig || a.sc.plain) return launch_env_step_spec<STEP_GENERAL>(a, L, star, st);
+    if (!a.det.active) return launch_env_step_spec<STEP_NOCAM>(a, L, star, st);
     const DetectorCfg& d = a.det;
     // (the condition under which camera_sh6_lane has nothing to do behind the photon draw)
     const bool after_photons = d.dark_e > 0.f || d.readout_noise != 0.f || d.qe != 1.f || d.gain != 1.f || d.fwc > 0.f || d.bits > 0;
-    if (d.photon_noise && !after_photons) return launch_env_step_spec<STEP_PHOTON>(a, L, st);
-    return launch_env_step_spec<STEP_CAMERA>(a, L, st);
+    if (d.photon_noise && !after_photons) return launch_env_step_spec<STEP_PHOTON>(a, L, star, st);
+    return launch_env_step_spec<STEP_CAMERA>(a, L, star, st);
 }
 
 }  // namespace ao

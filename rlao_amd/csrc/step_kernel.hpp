@@ -11,7 +11,8 @@ enum StepSpec {
     STEP_GENERAL = 0,      // nothing: run-time fast_trig and camera tests, the plain lenslet transform
     STEP_NOCAM = 1,        // fast trig, the ideal detector
     STEP_PHOTON = 2,       // fast trig, photon noise and nothing else: QE 1, no dark current, read-out noise, full well, gain or ADC
-    STEP_CAMERA = 3        // fast trig, any other camera
+    STEP_CAMERA = 3,       // fast trig, any other camera
+    STEP_STAR = 4          // what STEP_GENERAL knows, and every env its own amplitude factor and centroid threshold (StarEnv)
 };
 
 namespace fstep {
@@ -27,10 +28,11 @@ struct StepLds {
 };
 
 template <int SPEC>
-int launch_env_step_spec(const StepArgs& a, const StepLds& L, hipStream_t st);
-extern template int launch_env_step_spec<STEP_GENERAL>(const StepArgs&, const StepLds&, hipStream_t);
-extern template int launch_env_step_spec<STEP_NOCAM>(const StepArgs&, const StepLds&, hipStream_t);
-extern template int launch_env_step_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, hipStream_t);
-extern template int launch_env_step_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, hipStream_t);
+int launch_env_step_spec(const StepArgs& a, const StepLds& L, const StarEnv<float>& star, hipStream_t st);
+extern template int launch_env_step_spec<STEP_GENERAL>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+extern template int launch_env_step_spec<STEP_NOCAM>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+extern template int launch_env_step_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+extern template int launch_env_step_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+extern template int launch_env_step_spec<STEP_STAR>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 
 }  // namespace ao

@@ -21,7 +21,7 @@
 // Arithmetic is the same as in the separate kernels (phase_kernel.hip, sh_kernels.hip); only summation orders of the
 // centroid and of the telemetry differ (float32 / float64 rounding level).  No atomics: bitwise reproducible.
 // (the body of the kernel and its launcher: step_kernel_general.hip, _nocam.hip, _photon.hip and _camera.hip instantiate one
-// value of SPEC each, step_kernel.hip holds the layout and the dispatch)
+// value of SPEC each, step_kernel_star.hip the one with per-env guide stars, step_kernel.hip holds the layout and the dispatch)
 #pragma once
 #include "step_kernel.hpp"
 
@@ -58,9 +58,12 @@ __device__ inline const LayerTaps& step_taps(const PhaseArgs& pa, int l, int e) 
 // are compared with bit for bit.  The others have fast trig and the camera's kind fixed, so that neither sincosf's slow path
 // (inlined at every pixel) nor the camera blocks a launch cannot reach are in their code, and run the register-pair transform.
 // What changes between the steps of one call (store_phase / store_frame / store_atm, do_integrate, the ring) stays run-time.
+// STEP_STAR is the general body with every env's own guide star: `star` is a third argument, read by that instantiation alone, so
+// that the argument blocks and the code of the others are what they were without it.
 template <int KS, bool PE, int SPEC>
-__global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const StepLds L) {
-    constexpr bool GEN = SPEC == STEP_GENERAL;
+__global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const StepLds L, const StarEnv<float> star) {
+    constexpr bool STAR = SPEC == STEP_STAR;
+    constexpr bool GEN = SPEC == STEP_GENERAL || STAR;
     constexpr bool CAM_PHOTON_ONLY = SPEC == STEP_PHOTON;
     using namespace fstep;
     using fast6::EST;
@@ -262,6 +265,8 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
             apv[tt] = *reinterpret_cast<const f32x4s*>(a.amp_pupil + (okp ? (size_t)y * R + x : 0));
             if (!okp) apv[tt] = f32x4s{-1.f, -1.f, -1.f, -1.f};
         }
+        float star_amp = 1.f;                                    // (scalar: the env is the workgroup)
+        if constexpr (STAR) star_amp = star.amp ? star.amp[e] : 1.f;
 
         // ---- atmosphere: every layer's tile through LDS (16-byte loads), separable Catmull-Rom ----------------------------
         f32x4s sup[2];
@@ -373,7 +378,14 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                     const int jx = (x + r) / 6, ax = (x + r) - 6 * jx;
                     const int slot = slot_s[iy * n_sub + jx];
                     if (slot >= 0) {                                      // every pixel of a valid lenslet, lit or not
-                        const float am = apv[tt][r] >= 0.f ? apv[tt][r] * (1.f / 12.f) : 0.f;   // 1/n of |FFT2(E)/n|^2 (ShackHartmann.py:539)
+                        float am;
+                        if constexpr (STAR) {
+                            // the env's factor, a product of its own (one rounding); the test is on the table's value: -1 = outside the pupil
+                            const float amp = apv[tt][r] * star_amp;
+                            am = apv[tt][r] >= 0.f ? amp * (1.f / 12.f) : 0.f;
+                        } else {
+                            am = apv[tt][r] >= 0.f ? apv[tt][r] * (1.f / 12.f) : 0.f;   // 1/n of |FFT2(E)/n|^2 (ShackHartmann.py:539)
+                        }
                         float sn = 0.f, cs = 0.f;
                         if (am != 0.f) {
                             if (!GEN || a.sc.fast_trig) sincos_fast(phi[r], &sn, &cs); else sincosf(phi[r], &sn, &cs);
@@ -518,7 +530,9 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     // (aliases E0: every wave has its spots by now) zero at non-actuators: vec_to_img.  Stage C writes the actuators' values two
     // barriers from here.
     for (int i = tid; i < nA * nA; i += 1024) img_s[i] = 0.f;
-    const float cut = a.sc.threshold * mx;
+    float cut;
+    if constexpr (STAR) cut = (star.thr ? star.thr[e] : a.sc.threshold) * mx;
+    else cut = a.sc.threshold * mx;
     {
         float norm = 0.f, m0 = 0.f, m1 = 0.f;
 #pragma unroll
@@ -628,7 +642,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
 }
 
 template <int SPEC>
-int launch_env_step_spec(const StepArgs& a, const StepLds& L, hipStream_t st) {
+int launch_env_step_spec(const StepArgs& a, const StepLds& L, const StarEnv<float>& star, hipStream_t st) {
     const size_t lds = (size_t)L.total * 4;
     const int v = a.k.n_act <= 24 ? 0 : 1;
     const bool pe = a.k.pa.env_taps != nullptr;
@@ -640,10 +654,10 @@ int launch_env_step_spec(const StepArgs& a, const StepLds& L, hipStream_t st) {
         AO_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set[vi] = lds;
     }
-    if (v == 0 && !pe) hipLaunchKernelGGL((k_env_step_sh6<6, false, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L);
-    else if (v == 0) hipLaunchKernelGGL((k_env_step_sh6<6, true, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L);
-    else if (!pe) hipLaunchKernelGGL((k_env_step_sh6<8, false, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L);
-    else hipLaunchKernelGGL((k_env_step_sh6<8, true, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L);
+    if (v == 0 && !pe) hipLaunchKernelGGL((k_env_step_sh6<6, false, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L, star);
+    else if (v == 0) hipLaunchKernelGGL((k_env_step_sh6<6, true, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L, star);
+    else if (!pe) hipLaunchKernelGGL((k_env_step_sh6<8, false, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L, star);
+    else hipLaunchKernelGGL((k_env_step_sh6<8, true, SPEC>), dim3(a.n_env), dim3(1024), lds, st, a, L, star);
     AO_HIP(hipGetLastError());
     return 0;
 }

@@ -2,5 +2,5 @@
 #include "step_kernel_body.hpp"
 
 namespace ao {
-template int launch_env_step_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, hipStream_t);
+template int launch_env_step_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 }  // namespace ao

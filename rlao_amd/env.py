@@ -356,6 +356,42 @@ def resolve_dm_misregistration(values: dict, env_ids, n_envs: int, current) -> d
     return out
 
 
+STAR_KINDS = {"magnitude": None, "threshold": 0.0}                 # name: lower bound (inclusive), None = any finite value
+
+
+def resolve_star_per_env(kind: str, value, env_ids, n_envs: int, current) -> np.ndarray:
+    """The ``[n_envs]`` float64 magnitudes (``kind = "magnitude"``) or centroid thresholds (``"threshold"``) of a shard after a
+    ``set_magnitude_per_env`` / ``set_threshold_per_env`` call.  ``value``: a scalar or an array of length ``n_envs`` (with
+    ``env_ids``, anything ``normalize_env_ids`` takes: ``len(env_ids)``, in the order of ``env_ids``, a mask ascending).
+    ``current``: the ``[n_envs]`` values in force (the calibrated ones while the feature is off); envs not listed keep theirs and
+    ``current`` is not written.  Raises ``ValueError`` for an unknown kind, a wrong shape, non-numeric or non-finite values and a
+    threshold below 0.  Pure host code."""
+    if kind not in STAR_KINDS:
+        raise ValueError(f"unknown per-env star parameter {kind!r}")
+    n_envs = int(n_envs)
+    if env_ids is None:
+        rows = np.arange(n_envs)
+    else:
+        _, rows = normalize_env_ids(env_ids, n_envs, return_order=True)
+    v = value
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    try:
+        v = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{kind} must be numeric") from None
+    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != len(rows)):
+        raise ValueError(f"{kind} must be a scalar or have shape ({len(rows)},), got {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError(f"{kind} must be finite")
+    low = STAR_KINDS[kind]
+    if low is not None and (v < low).any():
+        raise ValueError(f"{kind} must not be below {low:g}")
+    out = np.array(current, dtype=np.float64).reshape(n_envs).copy()
+    out[rows] = v
+    return out
+
+
 class Shard:
     """One AoEnv handle of libaoenv (a shard of independent loops on one GPU)."""
 
@@ -511,6 +547,34 @@ class Shard:
         gx, gy = np.zeros(shape), np.zeros(shape)
         L.check(self.lib.aoenv_get_dm_env(self.h, gx.ctypes.data_as(C.c_void_p), gy.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
         return gx, gy
+
+    # per-env guide stars: flux relative to the uploaded C_WFS_AMP / centroid thresholds, [n_env] float64 (None: one for the shard)
+    def _set_star_row(self, fn, values, stream):
+        if values is None:
+            L.check(fn(self.h, None, C.c_void_p(stream)))
+            return
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        if a.shape != (self.cfg.n_env,):
+            raise ValueError(f"per-env star values must have shape ({self.cfg.n_env},)")
+        L.check(fn(self.h, a.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+
+    def _get_star_row(self, fn, stream):
+        out = np.zeros(self.cfg.n_env)
+        L.check(fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        return out
+
+    def set_flux_env(self, scale, stream=0):
+        self._set_star_row(self.lib.aoenv_set_flux_env, scale, stream)
+
+    def get_flux_env(self, stream=0):
+        """The amplitude factors sqrt(scale) as held (env dtype widened)."""
+        return self._get_star_row(self.lib.aoenv_get_flux_env, stream)
+
+    def set_threshold_env(self, thr, stream=0):
+        self._set_star_row(self.lib.aoenv_set_threshold_env, thr, stream)
+
+    def get_threshold_env(self, stream=0):
+        return self._get_star_row(self.lib.aoenv_get_threshold_env, stream)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -684,11 +748,64 @@ class _Cam:
         return self._e._fetch(L.B_FRAME, (self._e.cam_res, self._e.cam_res))
 
 
+class _SourceProxy:
+    """``env.source`` / ``env.ngs`` (MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647 reaches into ``source.nPhoton``): the guide star
+    of every env.  ``magnitude`` and ``nPhoton`` are ``[n_envs]``; assigning either (a scalar or an array) is
+    ``set_magnitude_per_env``."""
+    tag = "source"
+    type = "NGS"
+
+    def __init__(self, env):
+        object.__setattr__(self, "_e", env)
+
+    @property
+    def optBand(self):
+        return self._e.param.opticalBand
+
+    @property
+    def wavelength(self):
+        return self._e.src_wavelength
+
+    @property
+    def zeroPoint(self):
+        return calib.source(self._e.param.opticalBand, 0.0)[1]
+
+    @property
+    def magnitude(self):
+        return self._e.magnitude
+
+    @property
+    def nPhoton(self):
+        return self._e.nPhoton * calib.flux_scale(self._e.magnitude, self._e.param.magnitude)
+
+    def __setattr__(self, name, value):
+        if name == "magnitude":
+            self._e.set_magnitude_per_env(value)
+        elif name == "nPhoton":
+            v = value.detach().cpu().numpy() if hasattr(value, "detach") else value
+            v = np.asarray(v, dtype=np.float64)
+            if not (np.isfinite(v).all() and (v > 0).all()):
+                raise ValueError("nPhoton must be finite and above 0")
+            self._e.set_magnitude_per_env(-2.5 * np.log10(v / self.zeroPoint))
+        else:
+            raise AttributeError(f"cannot set source.{name}")
+
+
 class _WfsProxy:
     def __init__(self, env):
         self._e = env
         self.tag = "shackHartmann"
         self.cam = _Cam(env)
+
+    @property
+    def threshold_cog(self):
+        """``[n_envs]`` centroid thresholds (``env.threshold_cog``); assigning a scalar or an array is ``set_threshold_per_env``,
+        as ``atm.r0 = array`` is ``set_r0_per_env``."""
+        return self._e.threshold_cog
+
+    @threshold_cog.setter
+    def threshold_cog(self, value):
+        self._e.set_threshold_per_env(value)
 
     @property
     def nSignal(self):
@@ -836,6 +953,8 @@ class BatchedAOEnv:
         self._mobs = None                                          # the modal observation run_integrator_modal goes on from
         self._surface = "zonal"                                    # which surface the last observation came from: "zonal" | "modal"
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
+        self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
+        self.source = self.ngs = None
 
     # -- construction --------------------------------------------------------------------------------
     def set_params_file(self, param_file, oopao_path):
@@ -944,6 +1063,7 @@ class BatchedAOEnv:
         self._per_env_clock = False
         self._wind_pixels = 1
         self._dm_per_env, self._dm_misreg = False, None              # ... and one mirror, the calibrated one
+        self._mag_env = self._thr_env = None                         # ... and one star, the calibrated one
         self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
         self._surface = "zonal"
         sh = self._shard
@@ -964,6 +1084,7 @@ class BatchedAOEnv:
             if self.return_frame else None
         self.SR = []
         self.atm, self.dm, self.tel, self.wfs = _AtmProxy(self), _DmProxy(self), _TelProxy(self), _WfsProxy(self)
+        self.source = self.ngs = _SourceProxy(self)
         self.wfs.tag = "shackHartmann" if self.wfs_type == "sh" else "pyramid"
         pre, post = CAMERAS[camera]
         self.wfs.cam.configure(**{k: (p.samplingTime if v == "samplingTime" else v) for k, v in pre.items()})
@@ -1297,6 +1418,50 @@ class BatchedAOEnv:
         if self._dm_misreg is None:
             return {k: np.zeros(self.n_envs) for k in MISREG_KEYS}
         return {k: v.copy() for k, v in self._dm_misreg.items()}
+
+    # -- every env its own guide star (aoenv_set_flux_env / aoenv_set_threshold_env) -------------------------------------------
+    def set_magnitude_per_env(self, mag, env_ids=None):
+        """Every env its own guide-star magnitude (``change_mag``, MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647, for the envs of one
+        shard): ``mag`` a scalar or ``[n_envs]`` (with ``env_ids``, a list or a mask: ``[len(env_ids)]`` in that order); listed
+        envs are replaced, the others keep theirs.  Env e then runs as the calibrated shard with every WFS amplitude multiplied
+        by ``sqrt(calib.flux_scale(mag_e, param.magnitude))``; the calibration, the reconstructor and the modal basis stay, as
+        ``change_mag`` leaves them.  ``step``, ``measure``, ``reset_soft``, ``run_integrator``, both rollouts, the modal surface,
+        a delay and a disturbance all see the env's star without a new argument; ``reset_envs`` and new screens leave it in
+        place; the science PSF keeps the calibrated star.  Bad arguments raise before anything is touched.  Not part of
+        ``get_state``: after ``set_state`` call this again."""
+        full = resolve_star_per_env("magnitude", mag, env_ids, self.n_envs, self.magnitude)
+        self._shard.set_flux_env(calib.flux_scale(full, self.param.magnitude), self._stream())
+        self._mag_env = full
+
+    def set_threshold_per_env(self, thr, env_ids=None):
+        """Every env its own centroid threshold in ``I < thr * max -> 0`` (OOPAO/ShackHartmann.py:314-324; the inner loop of
+        MAIN/OOPAOEnvRazor/integrator_threshold.py:34-106): ``thr`` >= 0, a scalar or an array as in ``set_magnitude_per_env``.
+        Shack-Hartmann only.  Bad arguments raise before anything is touched.  Not part of ``get_state``."""
+        if self.wfs_type != "sh":
+            raise ValueError("a Pyramid env has no centre of gravity to threshold")
+        full = resolve_star_per_env("threshold", thr, env_ids, self.n_envs, self.threshold_cog)
+        self._shard.set_threshold_env(full, self._stream())
+        self._thr_env = full
+
+    def clear_star_per_env(self):
+        """Every env the calibrated star and ``param.threshold_cog`` again: every call does exactly what it did before."""
+        self._shard.set_flux_env(None, self._stream())
+        self._shard.set_threshold_env(None, self._stream())
+        self._mag_env = self._thr_env = None
+
+    def change_mag(self, mag):
+        """The reference's name (OOPAOEnvRazor.py:644-647): ``set_magnitude_per_env(mag)`` for every env."""
+        self.set_magnitude_per_env(mag)
+
+    @property
+    def magnitude(self):
+        """``[n_envs]`` guide-star magnitudes; ``param.magnitude`` for every env while no per-env star is set."""
+        return np.full(self.n_envs, float(self.param.magnitude)) if self._mag_env is None else self._mag_env.copy()
+
+    @property
+    def threshold_cog(self):
+        """``[n_envs]`` centroid thresholds; ``param.threshold_cog`` for every env while none is set."""
+        return np.full(self.n_envs, float(self.param.threshold_cog)) if self._thr_env is None else self._thr_env.copy()
 
     # -- the control delay inside the library (TimeDelayEnv, MAIN/PO4AO/util_simple.py:25-52) ----------------------------------
     def set_delay(self, d: int):
@@ -1792,7 +1957,8 @@ class BatchedAOEnv:
     def get_state(self) -> dict:
         """Everything the next ``step`` depends on, as host arrays: restoring it with ``set_state`` (same geometry, same
         n_envs) continues the episode bit for bit.  Configuration a caller restores itself, because it is not loop state: the
-        disturbance (``set_disturbance``) and the per-env mirrors (``set_dm_misregistration`` / ``set_dm_tables_per_env``)."""
+        disturbance (``set_disturbance``), the per-env mirrors (``set_dm_misregistration`` / ``set_dm_tables_per_env``) and the
+        per-env guide stars (``set_magnitude_per_env`` / ``set_threshold_per_env``)."""
         sh, p, at = self._shard, self.param, self._atm_tables
         st = self._stream()
         d = self.delay

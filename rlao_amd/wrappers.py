@@ -78,6 +78,26 @@ class TorchWrapper:
     def dm_misregistration(self):
         return self._env.dm_misregistration
 
+    def set_magnitude_per_env(self, mag, env_ids=None):
+        return self._env.set_magnitude_per_env(mag, env_ids)
+
+    def set_threshold_per_env(self, thr, env_ids=None):
+        return self._env.set_threshold_per_env(thr, env_ids)
+
+    def clear_star_per_env(self):
+        return self._env.clear_star_per_env()
+
+    def change_mag(self, mag):
+        return self._env.change_mag(mag)
+
+    @property
+    def magnitude(self):
+        return self._env.magnitude
+
+    @property
+    def threshold_cog(self):
+        return self._env.threshold_cog
+
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
 
@@ -171,6 +191,26 @@ class TimeDelayEnv:
     @property
     def dm_misregistration(self):
         return self._env.dm_misregistration
+
+    def set_magnitude_per_env(self, mag, env_ids=None):
+        return self._env.set_magnitude_per_env(mag, env_ids)
+
+    def set_threshold_per_env(self, thr, env_ids=None):
+        return self._env.set_threshold_per_env(thr, env_ids)
+
+    def clear_star_per_env(self):
+        return self._env.clear_star_per_env()
+
+    def change_mag(self, mag):
+        return self._env.change_mag(mag)
+
+    @property
+    def magnitude(self):
+        return self._env.magnitude
+
+    @property
+    def threshold_cog(self):
+        return self._env.threshold_cog
 
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
@@ -313,6 +353,26 @@ class HistoryEnv:
     @property
     def dm_misregistration(self):
         return self._env.dm_misregistration
+
+    def set_magnitude_per_env(self, mag, env_ids=None):
+        return self._env.set_magnitude_per_env(mag, env_ids)
+
+    def set_threshold_per_env(self, thr, env_ids=None):
+        return self._env.set_threshold_per_env(thr, env_ids)
+
+    def clear_star_per_env(self):
+        return self._env.clear_star_per_env()
+
+    def change_mag(self, mag):
+        return self._env.change_mag(mag)
+
+    @property
+    def magnitude(self):
+        return self._env.magnitude
+
+    @property
+    def threshold_cog(self):
+        return self._env.threshold_cog
 
     def set_r0_per_env(self, r0, env_ids=None):
         """Every env its own Fried parameter (``BatchedAOEnv.set_r0_per_env``); histories and delayed actions go on."""
