@@ -459,6 +459,56 @@ int aoenv_step_modal(AoEnv* env, int i, const void* d_action, void* d_obs, void*
 int aoenv_run_integrator_modal(AoEnv* env, int i0, int n_steps, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
                                void* stream);
 
+/* Replaces: the modal read-out of the wavefront that the reference forms on the host, always as
+ *     opd2m @ tel.OPD[xpupil, ypupil]            with opd2m = pinv(M2OPD)
+ * (MAIN_CODE/OOPAOEnv/SinEnv.py:150-204, MultiAtmEnv: the observation is the first modes of the open-loop atmosphere OPD;
+ * MAIN_CODE/predictiveControl/EOF/EOF_POL.py:105-123, EOF_OPD.py, linear_extrap/le_OPD.py: time series of the true coefficients;
+ * MAIN_CODE/make_dataset.py:84-103: the modal fit of a screen; MAIN_CODE/Plots/AO_plots.py zernike_dist: the modal spectrum of
+ * recorded residual frames).  The model is rlao_amd/csrc/wavefront.hpp.  With K modes, R^2 pixels and T the env dtype:
+ *     c[e][m] = s * sum_q P[m][q] X[e][q]
+ *     P            opd2m scattered to the full grid in T (pixel p of the table = the p-th pixel of np.where(tel.pupil == 1)), zero
+ *                  outside the pupil
+ *     residual     X = AOENV_B_PHASE (rad at the source wavelength), s = (T)(lambda_src / 2 pi) applied once after the sum: the
+ *                  coefficients of tel.OPD in metres
+ *     atmosphere   X = what aoenv_download(AOENV_B_OPD_ATM) would return at that moment, s = 1: those of the pupil-masked atm.OPD
+ * The sum runs over slices of [0, R^2) whose count and bounds depend on (R^2, K) alone, added in slice order without atomics: an
+ * env with the same buffers has the same bits in any shard and at any place in it.  float32 shards sum a slice on the matrix
+ * cores, float64 shards and AOENV_PATH_WF_GENERAL as one fma chain; the two orders have the bound of any summation order in common.
+ * aoenv_set_wavefront_basis hands over the projector; it is copied (and the slab scratch allocated) before the call returns, the
+ * stream is waited for once.  Like the modal basis it is configuration: in no checkpoint buffer, and a caller that restores a
+ * state sets it again.  A NULL cfg forgets it and detaches the record; so do a new basis and an upload of AOENV_C_PUPIL.
+ * Refused, with nothing changed: n_modes outside [1, min(n_pix, AOENV_MAX_WF_MODES)], n_pix different from the number of pupil
+ * pixels or no pupil uploaded, a null table, an entry that is not finite in the env dtype.  No buffer id, no profiled kernel and
+ * no ABI version go with it: the coefficients have these accessors of their own, and aoenv_profile does not attribute the
+ * projection's launches (the re-derivation of the atmosphere OPD in front of an on-demand atmosphere projection is a launch of the
+ * phase kernel and counts under AOENV_K_PHASE, as it does for aoenv_download).  float32 shards take the matrix-core tile of
+ * wavefront_kernels.hip up to 64 modes and the split-K GEMM of the reconstruction above (measured: profiles/wavefront_timing.json);
+ * the split count of that route is a function of (R^2, K) too. */
+#define AOENV_MAX_WF_MODES 1024
+enum AoWavefront { AOENV_WF_RESIDUAL = 1, AOENV_WF_ATMOSPHERE = 2 };
+typedef struct AoWavefrontBasis {
+    int32_t n_modes;               /* K in [1, min(n_pix, AOENV_MAX_WF_MODES)] */
+    int32_t n_pix;                 /* must equal the number of pupil pixels of the uploaded pupil */
+    const double* h_opd2m;         /* [K][n_pix], pixel p = the p-th pixel of np.where(tel.pupil == 1), row-major */
+} AoWavefrontBasis;
+int aoenv_set_wavefront_basis(AoEnv* env, const AoWavefrontBasis* cfg, void* stream);
+/* The coefficients of the buffers as they are now -- after aoenv_reset_soft, aoenv_measure, aoenv_set_atm_opd, an
+ * aoenv_upload_state(AOENV_B_PHASE) or a step of the per-call API -- into d_out [n_env][K] (env dtype).  `what` is exactly one
+ * AoWavefront bit.  Two launches (the slices, then their sum); the atmosphere is first re-derived from the screens where
+ * aoenv_download would do so.  Refused: no basis, zero or two bits, a null d_out. */
+int aoenv_project_wavefront(AoEnv* env, int what, void* d_out, void* stream);
+/* A per-step record that every stepped call honours: while attached, stepped frame i of aoenv_step, aoenv_step_modal,
+ * aoenv_run_integrator, aoenv_run_integrator_modal, aoenv_run_rollout and aoenv_run_policy_rollout writes slot i - i_base of the
+ * caller-owned d_rec [n_slots][W][n_env][K] (env dtype; W = the number of bits in `what`, residual first; with both, one pass over
+ * P serves the two).  The recorded residual is the one the sensor saw in that step -- the atmosphere after its advance minus the
+ * command latched by the previous call, under the delay and with the disturbance: the content AOENV_B_PHASE has after that step,
+ * bit for bit what aoenv_project_wavefront gives after the same step of the per-call API.  A loop step then stores the phase (and
+ * the atmosphere OPD, with that bit) it otherwise skips, not the camera frame; the loop's state and every output of the loop are
+ * bit for bit what they are without the record.  A call whose frames do not all lie in [i_base, i_base + n_slots) is refused
+ * before anything is launched.  NULL d_rec detaches; no stream is waited for (the caller keeps d_rec alive until the work
+ * enqueued so far is done).  Refused: no basis, no or unknown bits, i_base < 0, n_slots < 1. */
+int aoenv_set_wavefront_record(AoEnv* env, int what, void* d_rec, int i_base, int n_slots);
+
 /* Replaces: the exploration episodes of the trainers (MAIN/PO4AO/mbrl.py:64-89), kept on the device and recorded:
  *     action = gain * obs + env.sample_noise(sigma);  next_obs, _, reward, strehl, done, _ = env.step(i, action)
  * for the frames [i0, i0 + n_steps), every observation, action, reward and Strehl ratio written into the caller's trajectory buffers
@@ -613,7 +663,7 @@ enum AoOption {
                                  lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
                                  whose winds stay below one pixel per frame nothing: the same launches */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 other than AOENV_PATH_MODAL_GEMM and AOENV_PATH_SH_PLAIN also keeps the shard off the fused step
+                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN and AOENV_PATH_WF_GENERAL also keeps the shard off the fused step
                                  kernel; other bits are rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
@@ -626,6 +676,9 @@ enum AoPath {
                                           whatever its size, instead of the per-env kernel below the threshold.  It touches nothing
                                           inside the step, so unlike the other bits it leaves the shard on the fused step kernel: the
                                           loop state is the same bit for bit, only the order of the projection's sum differs */
+    AOENV_PATH_WF_GENERAL = 8192,      /* the wavefront projection (aoenv_project_wavefront, the record) as one fma chain per (env, mode,
+                                          slice) on float32 shards too, instead of the matrix-core kernel.  Like AOENV_PATH_MODAL_GEMM
+                                          it touches nothing inside the step and leaves the shard on the fused step kernel */
     AOENV_PATH_SH_PLAIN = 4096         /* the general instantiation of the fused step kernel (run-time camera and trig tests, the
                                           pixel-by-pixel stage A epilogue) and the plain C++ lenslet transform, there and in the
                                           batched spots kernel, instead of the forms specialised for the launch and the register-pair

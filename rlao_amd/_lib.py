@@ -25,7 +25,9 @@ WFS_SH, WFS_PYRAMID = 0, 1
 OPT_FORCE_PATH = 99
 MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
-PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN = 256, 512, 1024, 2048, 4096
+PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN, PATH_WF_GENERAL = 256, 512, 1024, 2048, 4096, 8192
+WF_RESIDUAL, WF_ATMOSPHERE = 1, 2                                  # enum AoWavefront
+MAX_WF_MODES = 1024                                                # AOENV_MAX_WF_MODES
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
                 "gemm_recon", "recon_finish", "pyramid", "sh_tail", "env_step", "detector")
 
@@ -65,6 +67,10 @@ class AoModal(C.Structure):
     _fields_ = [("n_modes", C.c_int32), ("h_m2c", C.c_void_p), ("h_cm", C.c_void_p)]
 
 
+class AoWavefrontBasis(C.Structure):
+    _fields_ = [("n_modes", C.c_int32), ("n_pix", C.c_int32), ("h_opd2m", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "aoenv_last_error": (C.c_char_p, []),
@@ -98,6 +104,9 @@ EXPORTS = {
                                    C.c_void_p]),
     "aoenv_run_integrator_modal": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "aoenv_set_wavefront_basis": (C.c_int, [C.c_void_p, C.POINTER(AoWavefrontBasis), C.c_void_p]),
+    "aoenv_project_wavefront": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "aoenv_set_wavefront_record": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "aoenv_set_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_flux_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -439,6 +439,25 @@ int launch_modal_obs(const ModalObsArgs<T>& a, int n_env, hipStream_t st);
 template <typename T>
 int launch_modal_finish(const ModalObsArgs<T>& a, int n_env, hipStream_t st);
 
+// wavefront modes (wavefront_kernels.hip; the model, the slices and the order of the sum are wavefront.hpp):
+// out[w][e][m] = scale[w] * sum_q p[m][q] x[w][e][q] for the n_w operands of a launch, through `slabs` [n_slices][n_w][E][K].
+// general: the fma-chain kernel also on float32 (AOENV_PATH_WF_GENERAL); float64 always takes it
+template <typename T>
+struct WfArgs {
+    const T* x[2];         // [E][r2] each: the residual phase and / or the atmosphere OPD
+    const T* p;            // [K][ld] the projector on the full grid, zero outside the pupil and in the pad
+    T* slabs;              // [n_slices][n_w][E][K]
+    T* out;                // [n_w][E][K]
+    T scale[2];            // applied once after the sum where use_scale is set
+    int use_scale[2];
+    int n_w, n_env, r2, ld, n_modes, n_slices, slice_len;
+};
+template <typename T>
+int launch_wf_project(const WfArgs<T>& a, bool general, hipStream_t st);
+// the second launch of launch_wf_project on its own: out = scale * (slab 0 + slab 1 + ...) over a.n_slices slabs, whoever wrote them
+template <typename T>
+int launch_wf_finish(const WfArgs<T>& a, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

@@ -17,6 +17,7 @@
 #include "policy.hpp"
 #include "sh_device.hpp"
 #include "star_env.hpp"
+#include "wavefront.hpp"
 
 namespace ao {
 
@@ -151,6 +152,19 @@ struct AoEnv {
         void* zscal = nullptr;              // [2][E] its reward, and a Strehl row nobody asked for
         void* slabs = nullptr;              // [splits][E][K] products of the GEMM path
     } modal;
+    // wavefront modes (aoenv_set_wavefront_basis, wavefront.hpp): configuration like the modal basis, in ONE allocation of its own
+    // (not in `allocs`: a NULL basis frees it); the record is the caller's memory
+    struct Wavefront {
+        bool set = false;
+        int K = 0;
+        WfPlan plan{};
+        void* base = nullptr;
+        void* p = nullptr;                  // [K][wf_row_stride(R^2)] the projector on the full grid
+        void* slabs = nullptr;              // [n_slices][2][E][K]
+        void* rec = nullptr;                // caller-owned [n_slots][W][E][K], or null: nothing is recorded
+        int rec_what = 0, i_base = 0, n_slots = 0;
+        int recorded() const { return rec ? rec_what : 0; }
+    } wf;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -806,7 +820,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN)) == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -876,7 +890,9 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     StepArgs a{};
     PhaseArgs pa;
     PhaseBuffers<float> pb;
-    fill_phase_args<float>(env, pa, pb, 1, env->store_opd_atm ? 1 : 0, 1);
+    // (a wavefront record reads the phase -- and the atmosphere, if it records it -- of EVERY step: both stores, not the frame's)
+    const int rec = env->wf.recorded();
+    fill_phase_args<float>(env, pa, pb, 1, (env->store_opd_atm || (rec & AOENV_WF_ATMOSPHERE)) ? 1 : 0, 1);
     a.k = make_phase_kargs<float>(pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
     a.sc = sh_const<float>(env);
     a.fa = finish_args<float>(env, static_cast<const float*>(d_action), static_cast<float*>(d_obs),
@@ -884,7 +900,8 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.fa.n_tiles = 1;
     a.frame = env->as<float>(env->frame);
     // (atm.OPD written every step is the state-inspection mode: every step is then observable, there is no fast path to keep)
-    a.store_phase = a.store_frame = (observable || env->store_opd_atm) ? 1 : 0;
+    a.store_frame = (observable || env->store_opd_atm) ? 1 : 0;
+    a.store_phase = (a.store_frame || rec) ? 1 : 0;
     a.signal = env->as<float>(env->signal);
     a.wfs_max = env->as<float>(env->wfs_max);
     a.fac_m = env->as<float>(env->fac_m);
@@ -974,6 +991,90 @@ int delay_loop_end(AoEnv* env, const T* d_action, int n_steps, hipStream_t st) {
     return 0;
 }
 
+// ---- wavefront modes (wavefront.hpp, wavefront_kernels.hip) --------------------------------------------------------------------------
+// K above which a float32 projection leaves k_wf_project_mfma for the split-K GEMM plus the finish kernel.
+// profiles/wavefront_timing.json, measured by scripts/time_wavefront.py at C2 (256 envs, R^2 = 14400): the new tile wins at K = 10
+// (11.8 us per call against 35.8), 30 (15.4 against 40.4) and 64 (22.0 against 41.3) and loses at K = 100 (43.7 against 41.9) and
+// 500 (79.8 against 57.1); up to 64 modes a wave's tile takes every mode in one pass over X, above that X is read once per 64-mode tile.  The macro is for
+// that script's A/B builds alone, which time either route at every K (make FLAGS_env=-D..., AOENV_LIB).
+#ifndef AOENV_WF_GEMM_ABOVE_MODES
+#define AOENV_WF_GEMM_ABOVE_MODES 64
+#endif
+constexpr int kWfGemmAboveModes = AOENV_WF_GEMM_ABOVE_MODES;
+// the split-K slabs of that route, from (R^2, K) alone like the slices of wf_plan: gemm_splits as it cuts for a shard of 256 envs,
+// whatever the shard's size, so that an env's sum has one order in every shard
+static int wf_gemm_splits(int r2, int n_modes) { return gemm_splits(256, n_modes, r2); }
+
+// The projection of the buffers as they stand: `what` bits in the order residual, atmosphere, into out [W][E][K].  Its launches are
+// not attributed by aoenv_profile.
+template <typename T>
+int wf_project(AoEnv* env, int what, void* out, hipStream_t st) {
+    const AoEnv::Wavefront& wf = env->wf;
+    WfArgs<T> a{};
+    int w = 0;
+    if (what & AOENV_WF_RESIDUAL) {
+        a.x[w] = env->as<T>(env->phase);
+        a.scale[w] = (T)(env->c.src_wavelength / (2.0 * M_PI));
+        a.use_scale[w] = 1;
+        ++w;
+    }
+    if (what & AOENV_WF_ATMOSPHERE) {
+        a.x[w] = env->as<T>(env->opd_atm);
+        a.scale[w] = (T)1;
+        a.use_scale[w] = 0;
+        ++w;
+    }
+    a.n_w = w;
+    a.p = env->as<T>(wf.p);
+    a.slabs = env->as<T>(wf.slabs);
+    a.out = static_cast<T*>(out);
+    a.n_env = env->E;
+    a.r2 = env->R * env->R;
+    a.ld = wf_row_stride(a.r2);
+    a.n_modes = wf.K;
+    a.n_slices = wf.plan.n_slices;
+    a.slice_len = wf.plan.slice_len;
+    if constexpr (std::is_same<T, float>::value) {
+        if (wf.K > kWfGemmAboveModes && !(env->force_path & AOENV_PATH_WF_GENERAL)) {
+            // above one 64-mode tile: operand by operand through the 64 x 64 split-K tile of launch_gemm_nt_mfma into the slabs,
+            // then the same finish kernel
+            for (int v = 0; v < w; ++v) {
+                WfArgs<T> b = a;
+                b.n_w = 1;
+                b.x[0] = a.x[v];
+                b.scale[0] = a.scale[v];
+                b.use_scale[0] = a.use_scale[v];
+                b.out = a.out + (size_t)v * a.n_env * a.n_modes;
+                b.n_slices = wf_gemm_splits(a.r2, a.n_modes);
+                AO_TRY(launch_gemm_nt_mfma(b.x[0], b.p, b.slabs, b.n_env, b.n_modes, b.r2, b.r2, b.ld, b.n_slices, st));
+                AO_TRY(launch_wf_finish<T>(b, st));
+            }
+            return 0;
+        }
+    }
+    return launch_wf_project<T>(a, sizeof(T) == 8 || (env->force_path & AOENV_PATH_WF_GENERAL) != 0, st);
+}
+
+// frame i of a stepped loop into its slot of the record, if one is attached (the window was checked before the first launch)
+template <typename T>
+int wf_record_step(AoEnv* env, int i, hipStream_t st) {
+    const AoEnv::Wavefront& wf = env->wf;
+    if (!wf.rec) return 0;
+    const int W = (wf.rec_what & AOENV_WF_RESIDUAL ? 1 : 0) + (wf.rec_what & AOENV_WF_ATMOSPHERE ? 1 : 0);
+    if (i < wf.i_base || i - wf.i_base >= wf.n_slots) return fail("frame %d outside the wavefront record's window [%d, %d)", i, wf.i_base, wf.i_base + wf.n_slots);
+    return wf_project<T>(env, wf.rec_what, static_cast<T*>(wf.rec) + (size_t)(i - wf.i_base) * W * env->E * wf.K, st);
+}
+
+// what every stepped call checks before its first launch: frames [i0, i0 + n) inside the window of an attached record
+static int wf_window_check(const AoEnv* env, int i0, int n) {
+    const AoEnv::Wavefront& wf = env->wf;
+    if (!wf.rec || n <= 0) return 0;
+    if (i0 < wf.i_base || (int64_t)i0 + n > (int64_t)wf.i_base + wf.n_slots)
+        return fail("frames [%d, %lld) leave the window [%d, %d) of the attached wavefront record", i0, (long long)i0 + n, wf.i_base,
+                    wf.i_base + wf.n_slots);
+    return 0;
+}
+
 template <typename T>
 int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
            double gain, bool observable, hipStream_t st) {
@@ -985,12 +1086,14 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
     if (fused_step) {
         AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, observable, st));
         env->step_cmd = nullptr;
+        AO_TRY(wf_record_step<T>(env, i, st));
         if (d_frame)
             AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                                   hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    AO_TRY(run_phase<T>(env, 1, env->store_opd_atm ? 1 : 0, st));
+    AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE)) ? 1 : 0, st));
+    AO_TRY(wf_record_step<T>(env, i, st));                         // (the phase kernel has written what the sensor is about to see)
     env->step_cmd = nullptr;                                       // the integration below, and a dense DM's next surface: the pure command
     // one workgroup per env re-reads the factors from L2: wins while launch latency dominates (measured: 19.5 us vs
     // 32.5 us at 256 envs, 96 us vs 75 us at 2048), the batched MFMA GEMM path takes over for large shards
@@ -1386,8 +1489,15 @@ int aoenv_destroy(AoEnv* env) {
     if (env->star.amp) (void)hipFree(env->star.amp);
     if (env->star.thr) (void)hipFree(env->star.thr);
     if (env->modal.base) (void)hipFree(env->modal.base);
+    if (env->wf.base) (void)hipFree(env->wf.base);
     delete env;
     return 0;
+}
+
+// no wavefront basis (wavefront.hpp): the projector and the slabs freed, the record detached
+static void wf_forget(AoEnv* env) {
+    if (env->wf.base) (void)hipFree(env->wf.base);
+    env->wf = AoEnv::Wavefront{};
 }
 
 int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
@@ -1405,6 +1515,7 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             env->amp_pupil_dirty = true;
             env->n_pupil = 0;
             for (size_t i = 0; i < R2; ++i) env->n_pupil += pu[i] != 0;
+            wf_forget(env);                                         // a wavefront basis is indexed by the pupil's pixels
             break;
         }
         case AOENV_C_AB:
@@ -2099,6 +2210,7 @@ int aoenv_step(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_fra
     if (i < 0 || i >= env->c.n_loop) return fail("frame index %d outside [0, n_loop=%d)", i, env->c.n_loop);
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    AO_TRY(wf_window_check(env, i, 1));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (env->delay.d == 0) return AO_DISPATCH(env, step_t, env, i, d_action, d_obs, d_frame, d_reward, d_strehl, 0.0, true, st);
     const void* applied = nullptr;                                 // the caller's tensor may be reused at once: it is copied
@@ -2116,6 +2228,7 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
     if (i0 < 0 || n_steps < 0 || i0 + n_steps > env->c.n_loop) return fail("frames [%d, %d) outside [0, n_loop=%d)", i0, i0 + n_steps, env->c.n_loop);
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    AO_TRY(wf_window_check(env, i0, n_steps));
     hipStream_t st = static_cast<hipStream_t>(stream);
     // only the last step's residual phase and camera frame can be read afterwards (aoenv_buffer, aoenv_download, aoenv_compute_psf,
     // d_frame, checkpoints: all of them between calls): the fused step leaves the stores of the other steps out
@@ -2448,6 +2561,7 @@ int aoenv_step_modal(AoEnv* env, int i, const void* d_action, void* d_obs, void*
     if (i < 0 || i >= env->c.n_loop) return fail("frame index %d outside [0, n_loop=%d)", i, env->c.n_loop);
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    AO_TRY(wf_window_check(env, i, 1));
     return AO_DISPATCH(env, step_modal_t, env, i, d_action, false, d_obs, d_frame, d_reward, d_strehl, true, static_cast<hipStream_t>(stream));
 }
 
@@ -2460,11 +2574,105 @@ int aoenv_run_integrator_modal(AoEnv* env, int i0, int n_steps, void* d_obs, voi
     if (i0 < 0 || n_steps < 0 || i0 + n_steps > env->c.n_loop) return fail("frames [%d, %d) outside [0, n_loop=%d)", i0, i0 + n_steps, env->c.n_loop);
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
+    AO_TRY(wf_window_check(env, i0, n_steps));
     hipStream_t st = static_cast<hipStream_t>(stream);
     // (only the last step's residual phase and camera frame can be read afterwards, as after aoenv_run_integrator)
     for (int k = 0; k < n_steps; ++k)
         AO_TRY(AO_DISPATCH(env, step_modal_t, env, i0 + k, d_obs, true, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward, d_strehl,
                            k == n_steps - 1, st));
+    return 0;
+}
+
+// ---- wavefront modes (wavefront.hpp) ----------------------------------------------------------------------------------------------
+static_assert(kWfMaxModes == AOENV_MAX_WF_MODES, "wavefront.hpp and aoenv.h disagree");
+constexpr int kWfSlabsAtLeast = kMaxSplits;                        // (the GEMM route writes up to kMaxSplits slabs)
+
+extern "C++" {
+template <typename T>
+static int wf_set_basis(AoEnv* env, const AoWavefrontBasis* cfg, hipStream_t st) {
+    const int R2 = env->R * env->R;
+    const bool have_pupil = env->h_pupil.size() == (size_t)R2;
+    size_t where = 0;
+    switch (wf_validate<T>(cfg->n_modes, cfg->n_pix, have_pupil ? env->h_pupil.data() : nullptr, R2, cfg->h_opd2m, &where)) {
+        case kWfOk: break;
+        case kWfPix: return fail("aoenv_set_wavefront_basis: n_pix %d is not positive", cfg->n_pix);
+        case kWfModes: return fail("aoenv_set_wavefront_basis: n_modes %d outside [1, min(n_pix=%d, %d)]", cfg->n_modes, cfg->n_pix, kWfMaxModes);
+        case kWfNoPupil: return fail("aoenv_set_wavefront_basis: the pupil has not been uploaded");
+        case kWfPupilCount: return fail("aoenv_set_wavefront_basis: n_pix %d, the pupil has %d pixels", cfg->n_pix, env->n_pupil);
+        case kWfNullTable: return fail("aoenv_set_wavefront_basis: null opd2m");
+        case kWfNotFinite: return fail("aoenv_set_wavefront_basis: opd2m[%zu] is not finite in the env dtype", where);
+    }
+    const int K = cfg->n_modes;
+    const WfPlan pl = wf_plan(R2, K);
+    const size_t ld = (size_t)wf_row_stride(R2), np = (size_t)K * ld, ns = (size_t)std::max(pl.n_slices, kWfSlabsAtLeast) * 2 * env->E * K;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    std::vector<T> table(np);
+    wf_scatter<T>(cfg->h_opd2m, K, cfg->n_pix, env->h_pupil.data(), R2, table.data());
+    AO_HIP(hipStreamSynchronize(st));                              // a projection in flight reads the table in place
+    void* p = nullptr;
+    if (hipMalloc(&p, al(np * sizeof(T)) + al(ns * sizeof(T))) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("aoenv_set_wavefront_basis: no device memory for %zu bytes of projector and slabs", al(np * sizeof(T)) + al(ns * sizeof(T)));
+    }
+    if (hipMemcpy(p, table.data(), np * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return fail("aoenv_set_wavefront_basis: the copy of the projector failed");
+    }
+    wf_forget(env);                                                // (a new basis detaches the record of the previous one)
+    AoEnv::Wavefront& wf = env->wf;
+    wf.base = wf.p = p;
+    wf.slabs = static_cast<char*>(p) + al(np * sizeof(T));
+    wf.K = K;
+    wf.plan = pl;
+    wf.set = true;
+    return 0;
+}
+}  // extern "C++"
+
+int aoenv_set_wavefront_basis(AoEnv* env, const AoWavefrontBasis* cfg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!cfg) {
+        AO_HIP(hipStreamSynchronize(st));
+        wf_forget(env);
+        return 0;
+    }
+    return env->c.dtype == AOENV_F32 ? wf_set_basis<float>(env, cfg, st) : wf_set_basis<double>(env, cfg, st);
+}
+
+static int wf_one_or_two_bits(int what) { return what != 0 && (what & ~(AOENV_WF_RESIDUAL | AOENV_WF_ATMOSPHERE)) == 0; }
+
+int aoenv_project_wavefront(AoEnv* env, int what, void* d_out, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->wf.set) return fail("aoenv_project_wavefront: no wavefront basis is set (aoenv_set_wavefront_basis)");
+    if (what != AOENV_WF_RESIDUAL && what != AOENV_WF_ATMOSPHERE)
+        return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE", what);
+    if (!d_out) return fail("aoenv_project_wavefront: null output");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (what == AOENV_WF_ATMOSPHERE && env->L > 0 && !env->atm_user_defined && !env->store_opd_atm) {
+        // not written by the step kernels unless asked to: re-derived from the screens now, as aoenv_download(AOENV_B_OPD_ATM) does
+        AO_TRY(require_step_constants(env, false));
+        AO_TRY(AO_DISPATCH(env, run_phase, env, 1, 1, st, 0));
+    }
+    return AO_DISPATCH(env, wf_project, env, what, d_out, st);
+}
+
+int aoenv_set_wavefront_record(AoEnv* env, int what, void* d_rec, int i_base, int n_slots) {
+    AO_CHECK_ENV(env);
+    AoEnv::Wavefront& wf = env->wf;
+    if (!d_rec) {
+        wf.rec = nullptr;
+        wf.rec_what = wf.i_base = wf.n_slots = 0;
+        return 0;
+    }
+    if (!wf.set) return fail("aoenv_set_wavefront_record: no wavefront basis is set (aoenv_set_wavefront_basis)");
+    if (!wf_one_or_two_bits(what)) return fail("aoenv_set_wavefront_record: what = %d is no combination of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE", what);
+    if (i_base < 0 || n_slots < 1) return fail("aoenv_set_wavefront_record: window [%d, %d + %d) is empty or negative", i_base, i_base, n_slots);
+    wf.rec = d_rec;
+    wf.rec_what = what;
+    wf.i_base = i_base;
+    wf.n_slots = n_slots;
     return 0;
 }
 
@@ -2570,7 +2778,7 @@ static int rollout_check(AoEnv* env, const AoRollout* cfg, const void* d_obs, co
     if (!(cfg->gain >= 0) || !std::isfinite(cfg->gain)) return fail("%s: gain must be finite and >= 0", who);
     AO_TRY(require_step_constants(env, true));
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
-    return 0;
+    return wf_window_check(env, cfg->i0, cfg->n_steps);
 }
 
 // the inverse of AOENV_C_ACT_IDX on the device
@@ -3076,7 +3284,8 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             env->wind_pixels = value;
             return 0;
         case AOENV_OPT_FORCE_PATH:
-            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN))
+            if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN |
+                          AOENV_PATH_WF_GENERAL))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

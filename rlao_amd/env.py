@@ -252,6 +252,63 @@ def resolve_modal(n_modes, m2c, cm, n_valid_act: int, n_signal: int, m2c_cl=None
     return {"m2c": np.ascontiguousarray(B).copy(), "cm": np.ascontiguousarray(M).copy()}
 
 
+def resolve_wavefront_basis(m2opd, opd2m, n_modes, n_pix: int) -> np.ndarray:
+    """The projector of a ``set_wavefront_basis`` call as the library is handed it: float64 ``[K, n_pix]``, C-contiguous.
+    ``m2opd`` ``[n_pix, >= K]`` (the reference's ``M2OPD_*.npy``: the modes sampled at the pupil pixels, columns) is inverted with
+    ``np.linalg.pinv`` in float64 on its first ``n_modes`` columns (all of them without ``n_modes``), as every read-out of the
+    reference does (``opd2m = pinv(M2OPD)``, MAIN_CODE/OOPAOEnv/SinEnv.py:150-204); ``opd2m`` ``[K', n_pix]`` is taken as given, cut
+    to its first ``n_modes`` rows.  Raises ``ValueError`` for both or neither, wrong shapes, K outside [1, min(n_pix, 1024)] and
+    values that are not finite."""
+    if (m2opd is None) == (opd2m is None):
+        raise ValueError("give exactly one of m2opd [n_pix, K] and opd2m [K, n_pix]")
+    if n_modes is not None and (isinstance(n_modes, bool) or not isinstance(n_modes, (int, np.integer))):
+        raise ValueError("n_modes must be an int")
+
+    def table(a, name):
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        try:
+            a = np.array(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be numeric") from None
+        if a.ndim != 2 or not np.isfinite(a).all():
+            raise ValueError(f"{name} must be a finite 2-d table")
+        return a
+
+    if m2opd is not None:
+        a = table(m2opd, "m2opd")
+        if a.shape[0] != n_pix:
+            raise ValueError(f"m2opd must have shape ({n_pix}, K): one row per pupil pixel, got {a.shape}")
+        K = a.shape[1] if n_modes is None else int(n_modes)
+        if K < 1 or K > a.shape[1] or K > min(n_pix, L.MAX_WF_MODES):
+            raise ValueError(f"n_modes {K} outside [1, {min(a.shape[1], n_pix, L.MAX_WF_MODES)}]")
+        out = np.linalg.pinv(a[:, :K])
+    else:
+        a = table(opd2m, "opd2m")
+        if a.shape[1] != n_pix:
+            raise ValueError(f"opd2m must have shape (K, {n_pix}): one column per pupil pixel, got {a.shape}")
+        K = a.shape[0] if n_modes is None else int(n_modes)
+        if K < 1 or K > a.shape[0] or K > min(n_pix, L.MAX_WF_MODES):
+            raise ValueError(f"n_modes {K} outside [1, {min(a.shape[0], n_pix, L.MAX_WF_MODES)}]")
+        out = a[:K]
+    return np.ascontiguousarray(out, dtype=np.float64)
+
+
+_WF_BITS = {"residual": L.WF_RESIDUAL, "atmosphere": L.WF_ATMOSPHERE}
+
+
+def wavefront_bits(what) -> int:
+    """``what`` of ``project_wavefront`` / ``record_wavefront`` as AoWavefront bits: a name or a sequence of names out of
+    "residual" and "atmosphere" (the record keeps the library's order, residual first, whatever the order given)."""
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if not names or any(n not in _WF_BITS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"what must name 'residual' and / or 'atmosphere' once each, got {what!r}")
+    bits = 0
+    for n in names:
+        bits |= _WF_BITS[n]
+    return bits
+
+
 def resolve_modal_gain(g, env_ids, n_envs: int, n_modes: int, current=None):
     """The gains of the modal integrator after a ``set_modal_gain`` call: ``(gain, per_env)`` with ``gain`` float64 ``[K]``
     (``per_env`` False: every env the same) or ``[n_envs, K]``.  ``g``: a scalar, ``[K]`` or ``[n_envs, K]``; with ``env_ids``
@@ -952,6 +1009,8 @@ class BatchedAOEnv:
         self._modal_gain = None                                    # resolve_modal_gain()'s array while modal gains are set
         self._mobs = None                                          # the modal observation run_integrator_modal goes on from
         self._surface = "zonal"                                    # which surface the last observation came from: "zonal" | "modal"
+        self._wf = None                                            # resolve_wavefront_basis()'s table while a wavefront basis is set
+        self._wf_rec = None                                        # the tensor of an attached wavefront record (kept alive here)
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
         self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
         self.source = self.ngs = None
@@ -1065,6 +1124,7 @@ class BatchedAOEnv:
         self._dm_per_env, self._dm_misreg = False, None              # ... and one mirror, the calibrated one
         self._mag_env = self._thr_env = None                         # ... and one star, the calibrated one
         self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
+        self._wf = self._wf_rec = None                               # ... and no wavefront basis (it is indexed by the pupil's pixels)
         self._surface = "zonal"
         sh = self._shard
         at = self._atm_tables
@@ -1619,6 +1679,68 @@ class BatchedAOEnv:
             self._shard.h, int(i0), int(n_steps), C.c_void_p(self._mobs.data_ptr()), None,
             C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._strehl.data_ptr()), C.c_void_p(self._stream())))
         return self._mobs, self._reward, self._strehl
+
+    # -- wavefront modes (aoenv_set_wavefront_basis; the reference's opd2m @ tel.OPD[pupil]) ---------------------------------------
+    def set_wavefront_basis(self, m2opd=None, opd2m=None, n_modes=None):
+        """The modes the wavefront is read out in: ``project_wavefront`` and ``record_wavefront`` then give
+        ``opd2m @ OPD[e][tel.pupil == 1]`` of the residual (``tel.OPD``, metres) and of the atmosphere (``atm.OPD``) on the device,
+        what the reference forms on the host (MAIN_CODE/OOPAOEnv/SinEnv.py:150-204, predictiveControl/EOF/EOF_POL.py:105-123,
+        make_dataset.py:84-103, Plots/AO_plots.py ``zernike_dist``).  ``m2opd`` ``[n_pix, >= K]`` as the reference's ``M2OPD_*.npy``
+        (inverted with ``np.linalg.pinv`` on its first ``n_modes`` columns) or ``opd2m`` ``[K, n_pix]`` directly; pixel p is the
+        p-th of ``np.where(tel.pupil == 1)``.  A new basis detaches a record.  Not part of ``get_state``: after ``set_state`` on a
+        new env call this again."""
+        table = resolve_wavefront_basis(m2opd, opd2m, n_modes, int(np.count_nonzero(self.pupil)))
+        cfg = L.AoWavefrontBasis(n_modes=table.shape[0], n_pix=table.shape[1], h_opd2m=table.ctypes.data_as(C.c_void_p))
+        L.check(self._shard.lib.aoenv_set_wavefront_basis(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        self._wf, self._wf_rec = table, None
+
+    def clear_wavefront_basis(self):
+        """No wavefront basis: the projector and its device memory are gone, a record is detached."""
+        L.check(self._shard.lib.aoenv_set_wavefront_basis(self._shard.h, None, C.c_void_p(self._stream())))
+        self._wf = self._wf_rec = None
+
+    @property
+    def n_wavefront_modes(self) -> int:
+        """The number of modes of the wavefront basis, 0 while none is set."""
+        return 0 if self._wf is None else int(self._wf.shape[0])
+
+    def _require_wavefront(self):
+        if self._wf is None:
+            raise L.AoEnvError("no wavefront basis is set: call set_wavefront_basis() first")
+
+    def project_wavefront(self, what="residual"):
+        """The modal coefficients ``[n_envs, K]`` (metres; a NumPy vector for the single-env flavour) of the wavefront as it stands
+        -- after ``reset_soft``, ``measure``, a step, ``atm.OPD = ...`` or ``tel.resetOPD()``: ``what="residual"`` those of
+        ``tel.OPD``, ``what="atmosphere"`` those of the pupil-masked ``atm.OPD``.  A new tensor every call."""
+        self._require_wavefront()
+        bits = wavefront_bits(what)
+        if bits not in (L.WF_RESIDUAL, L.WF_ATMOSPHERE):
+            raise ValueError("project_wavefront takes one of 'residual' and 'atmosphere'; record_wavefront takes both")
+        out = _torch().empty((self.n_envs, self.n_wavefront_modes), device=self.device, dtype=self.tdtype)
+        L.check(self._shard.lib.aoenv_project_wavefront(self._shard.h, bits, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream())))
+        return self._out(out)
+
+    def record_wavefront(self, i0: int, n_steps: int, what=("residual",)):
+        """Attaches a record ``[n_steps, W, n_envs, K]`` (a new device tensor, returned; W = len(what), residual first) that every
+        stepped frame ``i0 <= i < i0 + n_steps`` -- of ``step``, ``step_modal``, ``run_integrator``, ``run_integrator_modal``,
+        ``rollout`` and ``policy_rollout`` -- fills with the coefficients of the wavefront the sensor saw in that frame: slot
+        ``i - i0`` is what ``project_wavefront`` gives after that step.  The loops' results do not change by a bit.  A call whose
+        frames leave the window is refused; ``stop_wavefront_record()`` detaches (the tensor stays the caller's)."""
+        self._require_wavefront()
+        bits = wavefront_bits(what)
+        W = bin(bits).count("1")
+        if int(n_steps) < 1 or int(i0) < 0:
+            raise ValueError("record_wavefront: i0 >= 0 and n_steps >= 1")
+        rec = _torch().zeros((int(n_steps), W, self.n_envs, self.n_wavefront_modes), device=self.device, dtype=self.tdtype)
+        L.check(self._shard.lib.aoenv_set_wavefront_record(self._shard.h, bits, C.c_void_p(rec.data_ptr()), int(i0), int(n_steps)))
+        self._wf_rec = rec
+        return rec
+
+    def stop_wavefront_record(self):
+        """Detaches the record; the loops run as without one.  Work already enqueued still writes the tensor: it stays alive with
+        the caller's reference."""
+        L.check(self._shard.lib.aoenv_set_wavefront_record(self._shard.h, 0, None, 0, 0))
+        self._wf_rec = None
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

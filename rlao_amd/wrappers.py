@@ -118,6 +118,27 @@ class TorchWrapper:
         """``BatchedAOEnv.run_integrator_modal`` in this wrapper's return convention: float32 tensors."""
         return tuple(_torch().as_tensor(t).float() for t in self._env.run_integrator_modal(i0, n_steps))
 
+    def set_wavefront_basis(self, m2opd=None, opd2m=None, n_modes=None):
+        return self._env.set_wavefront_basis(m2opd=m2opd, opd2m=opd2m, n_modes=n_modes)
+
+    def clear_wavefront_basis(self):
+        return self._env.clear_wavefront_basis()
+
+    @property
+    def n_wavefront_modes(self):
+        return self._env.n_wavefront_modes
+
+    def project_wavefront(self, what="residual"):
+        """``BatchedAOEnv.project_wavefront`` in this wrapper's return convention: a float32 tensor."""
+        return _torch().as_tensor(self._env.project_wavefront(what), dtype=_torch().float32)
+
+    def record_wavefront(self, i0, n_steps, what=("residual",)):
+        """``BatchedAOEnv.record_wavefront``: the record itself, in the env dtype (the library writes into this very tensor)."""
+        return self._env.record_wavefront(i0, n_steps, what)
+
+    def stop_wavefront_record(self):
+        return self._env.stop_wavefront_record()
+
     def rollout(self, i0, n_steps, sigma, gain=None, seed=None, sigma_env=None):
         """``BatchedAOEnv.rollout`` in this wrapper's return convention: float32 tensors."""
         torch = _torch()
@@ -215,6 +236,19 @@ class TimeDelayEnv:
     def set_r0_per_env(self, r0, env_ids=None):
         return self._env.set_r0_per_env(r0, env_ids)
 
+    def set_wavefront_basis(self, m2opd=None, opd2m=None, n_modes=None):
+        return self._env.set_wavefront_basis(m2opd=m2opd, opd2m=opd2m, n_modes=n_modes)
+
+    def clear_wavefront_basis(self):
+        return self._env.clear_wavefront_basis()
+
+    @property
+    def n_wavefront_modes(self):
+        return self._env.n_wavefront_modes
+
+    def project_wavefront(self, what="residual"):
+        return self._env.project_wavefront(what)
+
     def step(self, i, action):
         self.action_buffer.append(action)
         out = self._env.step(i, self.action_buffer[0])
@@ -308,6 +342,19 @@ class HistoryEnv:
 
     def __getattr__(self, name):
         return getattr(self._env, name)
+
+    def set_wavefront_basis(self, m2opd=None, opd2m=None, n_modes=None):
+        return self._env.set_wavefront_basis(m2opd=m2opd, opd2m=opd2m, n_modes=n_modes)
+
+    def clear_wavefront_basis(self):
+        return self._env.clear_wavefront_basis()
+
+    @property
+    def n_wavefront_modes(self):
+        return self._env.n_wavefront_modes
+
+    def project_wavefront(self, what="residual"):
+        return self._env.project_wavefront(what)
 
     def _alloc(self):
         torch = _torch()
