@@ -141,6 +141,12 @@ __device__ inline const LayerTaps& layer_taps(const PhaseArgs& pa, int l, int e)
     return pa.env_taps ? pa.env_taps[(size_t)l * pa.n_env + e] : pa.taps[l];
 }
 
+// float64 sum over the wave, in lane 0 (a fixed order: bitwise reproducible)
+__device__ inline double wave_sum_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
 }  // namespace ao
 
 // ---- device entry points implemented in the kernel translation units -----------------------------

@@ -19,16 +19,11 @@
 //     repeated between tiles, and Gx^T of the tile's columns sits in LDS
 //   * Sum x, Sum x^2 of the atmosphere and residual OPD over the pupil are accumulated in float64 and
 //     written per tile; the epilogue kernel adds the tiles in a fixed order (bitwise reproducible).
-#include "common.hpp"
+#include "phase_device.hpp"
 
 namespace ao {
 
 constexpr int kTY = 16, kTXmax = 128;
-
-__device__ inline double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
@@ -123,10 +118,8 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
                     const int y = ly + 4 * j;
                     if (x < txe && y < tye) {
                         const T* h = ht + y * TX + x;
-                        T v = ((wy0 * h[0] + wy1 * h[TX]) + wy2 * h[2 * TX]) + wy3 * h[3 * TX];
-                        // skimage clip=True: clamp to the input range, keep exact zeros when 0 is outside it
-                        if (!(zero_outside && v == (T)0)) v = v < lo ? lo : (v > hi ? hi : v);
-                        sup[i][j] += v * wl;
+                        const T v = ((wy0 * h[0] + wy1 * h[TX]) + wy2 * h[2 * TX]) + wy3 * h[3 * TX];
+                        sup[i][j] += clip_to_range(v, lo, hi, zero_outside) * wl;
                     }
                 }
             }
@@ -134,7 +127,7 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
     }
     __syncthreads();                                          // s1 / gxt complete (and tiles done)
 
-    double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
+    PupilSums sums;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int x = lx + 64 * i;
@@ -158,29 +151,12 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
                 } else {
                     dm = a.pb.dm_opd[pix0 + q];
                 }
-                const bool in = a.pb.pupil[q] != 0;
-                const T res = in ? (atm + dm) : (T)0;
-                if (a.pa.store_phase) a.pb.phase[pix0 + q] = res * a.src_scale;
-                if (in) {
-                    const double da = (double)atm, dr = (double)res;
-                    s_atm += da;
-                    q_atm += da * da;
-                    s_res += dr;
-                    q_res += dr * dr;
-                }
+                const T phi = residual_pixel(atm, dm, a.pb.pupil[q] != 0, a.src_scale, sums);
+                if (a.pa.store_phase) a.pb.phase[pix0 + q] = phi;
             }
         }
     }
-    s_atm = wave_sum(s_atm);
-    q_atm = wave_sum(q_atm);
-    s_res = wave_sum(s_res);
-    q_res = wave_sum(q_res);
-    if (lx == 0) {
-        red[0][ly] = s_atm;
-        red[1][ly] = q_atm;
-        red[2][ly] = s_res;
-        red[3][ly] = q_res;
-    }
+    reduce_pupil_sums(sums, red, lx, ly);
     __syncthreads();
     if (tid < 4 && a.pa.store_phase) {
         const int tile = blockIdx.y * gridDim.x + blockIdx.x, n_tiles = gridDim.x * gridDim.y;
@@ -197,44 +173,6 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
 // Per MFMA (1024 MACs) a lane reads one s1 and one Gx^T value from LDS -- 32x less LDS traffic than the
 // per-pixel dot products of the generic kernel, which were the bottleneck there.
 // ---------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// s1 tile rows on the matrix cores (see k_phase_mfma).  KS = k steps held in registers (n_act <= 4 KS).  Every load is
-// unconditional from a clamped index: a predicated load compiles to a branch, and a run of them to a chain of latencies.
-template <int KS>
-__device__ inline void s1_tiles_mfma(const float* __restrict__ gya, int ga_stride, const float* cimg, float* s1, int y0, int R,
-                                     int nA, int nAp, int SS, int lc, int lq, int wave) {
-    float av[KS];
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(gya) + (size_t)(y0 >> 4) * (ga_stride >> 2) * 64 + (lq * 16 + lc);
-#pragma unroll
-        for (int q4 = 0; q4 < KS / 4; ++q4) {
-            const f32x4 t = src[4 * q4 < ga_stride ? 64 * q4 : 0];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) av[4 * q4 + d] = 4 * q4 < ga_stride ? t[d] : 0.f;     // A[i = lane & 15 -> row][k = lane >> 4]
-        }
-    }
-    for (int ct = wave; 16 * ct < nA; ct += 4) {
-        const int ix = 16 * ct + lc;
-        float bv[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int iy = lq + 4 * ks;
-            const bool ok = iy < nA && ix < nA;
-            const float t = cimg[ok ? iy * nA + ix : 0];
-            bv[ks] = ok ? t : 0.f;                           // B[k = lane >> 4][j = lane & 15]
-        }
-        f32x4 d = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            if (4 * ks < nAp) d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ks], bv[ks], d, 0, 0, 0);
-        if (ix < nA) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s1[(4 * lq + r) * SS + ix] = d[r];
-        }
-    }
-}
-
 __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int R = a.R, nA = a.n_act;
@@ -257,34 +195,8 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
 
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && a.pa.store_phase) a.pb.wfs_max[e] = 0.f;
 
-    if (rows_given) {
-    } else if (a.pb.coefs_img) {
-        for (int i = tid; i < kTY * SS; i += 256) s1[i] = 0.f;
-        // batches of 8 independent loads per lane (a load-then-store loop pays one memory latency per iteration)
-        const float* ci = a.pb.coefs_img + (size_t)e * nA * nA;
-        for (int i0 = tid; i0 < nA * nA; i0 += 8 * 256) {
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = ci[i0 + 256 * q < nA * nA ? i0 + 256 * q : i0];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) if (i0 + 256 * q < nA * nA) cimg[i0 + 256 * q] = v[q];
-        }
-    } else {
-        for (int i = tid; i < kTY * SS; i += 256) s1[i] = 0.f;
-        for (int i = tid; i < nA * nA; i += 256) cimg[i] = 0.f;
-        __syncthreads();
-        const float* cf = a.pb.coefs + (size_t)e * a.n_valid_act;
-        for (int k = tid; k < a.n_valid_act; k += 256) cimg[a.pb.act_idx[k]] = cf[k];
-    }
-    __syncthreads();
-    // s1[y][ix] = sum_iy gy[y0 + y][iy] C[iy][ix] on the matrix cores: 16 x 16 output tiles over the command columns,
-    // wave w takes the tiles w, w + 4, ...; the A operands (the tile's 16 rows of gy) are the same for every column tile
-    // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
-    // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
-    if (!rows_given) {
-        if (nAp <= 32) s1_tiles_mfma<8>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-        else s1_tiles_mfma<32>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-    }
+    // the command image and s1 = Gy[tile rows] C
+    stage_command_and_rows(a, cimg, s1, gya, rows_given, e, y0, tid, nA, nAp, SS, lc, lq, ly);
 
     // lane's pixels: sub-tile tt (x = 16 (2 ly + tt) + lc), rows y = 4 lq + r
     float sup[2][4];
@@ -339,9 +251,8 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float v = ((wy0 * h[r] + wy1 * h[r + 1]) + wy2 * h[r + 2]) + wy3 * h[r + 3];
-                    if (!(zero_outside && v == 0.f)) v = v < lo ? lo : (v > hi ? hi : v);
-                    sup[tt][r] += v * wl;
+                    const float v = ((wy0 * h[r] + wy1 * h[r + 1]) + wy2 * h[r + 2]) + wy3 * h[r + 3];
+                    sup[tt][r] += clip_to_range(v, lo, hi, zero_outside) * wl;
                 }
             }
         }
@@ -359,7 +270,7 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
             const uint8_t t = a.pb.pupil[okp ? (size_t)(y0 + y) * R + (x0 + xl) : 0];
             pup[tt][r] = okp && t != 0;
         }
-    double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
+    PupilSums sums;
     // A[i = lane & 15 -> tile row][k = lane >> 4 + 4 s] = (Gy C)[y0 + i][k] from the operand-layout rows k_dm_rows wrote:
     // ga_stride / 4 16-byte loads per lane (<= 8: n_act <= 128), all in flight together
     constexpr int NQ = 8;
@@ -410,29 +321,12 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
                 } else {
                     atm = a.pb.opd_atm[pix0 + q];
                 }
-                const bool in = pup[tt][r];
-                const float res = in ? (atm + dmv[r]) : 0.f;
-                if (a.pa.store_phase) a.pb.phase[pix0 + q] = res * a.src_scale;
-                if (in) {
-                    const double da = (double)atm, dr = (double)res;
-                    s_atm += da;
-                    q_atm += da * da;
-                    s_res += dr;
-                    q_res += dr * dr;
-                }
+                const float phi = residual_pixel(atm, dmv[r], pup[tt][r], a.src_scale, sums);
+                if (a.pa.store_phase) a.pb.phase[pix0 + q] = phi;
             }
         }
     }
-    s_atm = wave_sum(s_atm);
-    q_atm = wave_sum(q_atm);
-    s_res = wave_sum(s_res);
-    q_res = wave_sum(q_res);
-    if (lx == 0) {
-        red[0][ly] = s_atm;
-        red[1][ly] = q_atm;
-        red[2][ly] = s_res;
-        red[3][ly] = q_res;
-    }
+    reduce_pupil_sums(sums, red, lx, ly);
     __syncthreads();
     if (tid < 4 && a.pa.store_phase) {
         const int tile = blockIdx.y * gridDim.x + blockIdx.x, n_tiles = gridDim.x * gridDim.y;
@@ -444,8 +338,10 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
 // product are swapped -- gx as A, the Gy C row as B -- so that the matrix cores' output layout gives a lane FOUR CONSECUTIVE pixels
 // of ONE row (the lane -> pixel map of the fused step kernel's stage A): the layer tile is staged with 3 float4 loads per lane
 // instead of 10 dword loads, its taps are read as float4 from LDS, the pupil flags of 4 pixels are one load, the phase (and OPD)
-// rows are written as float4 -- the vector-memory path takes ~16 cycles per wave-instruction whatever its width.  Same arithmetic
-// per pixel (the same taps in the same order, the same k order of the product): results are bit-identical to k_phase_mfma.
+// rows are written as float4 -- the vector-memory path takes ~16 cycles per wave-instruction whatever its width.  The pixel,
+// the pupil sums and the Gy C rows are the functions k_phase_mfma calls, the tile load the one stage A of the step kernel calls
+// (phase_device.hpp); what remains this kernel's own against k_phase_mfma is the tap layout of its warp (warp_row4's text, written
+// out) and the swapped product (the same k order), and test_phase_kernel_with_16_byte_accesses_is_bit_identical holds the two together.
 // BAND (one layer): the layer tile of the WHOLE band -- 19 rows x (R + 4) columns, 37 KB at R = 480 -- is staged once, all its loads
 // in flight together, instead of a 19 x 132 tile per 128-column chunk: one memory latency and one pair of barriers per workgroup
 // instead of four (ELT size: a wave lived 43 us, 56 % of it waiting).
@@ -473,36 +369,10 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 
     if (blockIdx.y == 0 && tid == 0 && a.pa.store_phase) a.pb.wfs_max[e] = 0.f;
 
-    if (rows_given) {
-    } else if (a.pb.coefs_img) {
-        for (int i = tid; i < kTY * SS; i += 256) s1[i] = 0.f;
-        // batches of 8 independent loads per lane (a load-then-store loop pays one memory latency per iteration)
-        const float* ci = a.pb.coefs_img + (size_t)e * nA * nA;
-        for (int i0 = tid; i0 < nA * nA; i0 += 8 * 256) {
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = ci[i0 + 256 * q < nA * nA ? i0 + 256 * q : i0];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) if (i0 + 256 * q < nA * nA) cimg[i0 + 256 * q] = v[q];
-        }
-    } else {
-        for (int i = tid; i < kTY * SS; i += 256) s1[i] = 0.f;
-        for (int i = tid; i < nA * nA; i += 256) cimg[i] = 0.f;
-        __syncthreads();
-        const float* cf = a.pb.coefs + (size_t)e * a.n_valid_act;
-        for (int k = tid; k < a.n_valid_act; k += 256) cimg[a.pb.act_idx[k]] = cf[k];
-    }
-    __syncthreads();
-    // s1[y][ix] = sum_iy gy[y0 + y][iy] C[iy][ix] on the matrix cores: 16 x 16 output tiles over the command columns,
-    // wave w takes the tiles w, w + 4, ...; the A operands (the tile's 16 rows of gy) are the same for every column tile
-    // and are loaded once, all loads in flight together.  (As a per-output dot product through LDS this was 2/3 of the
-    // kernel at 81 actuators across: a chain of nA LDS latencies per output.)
-    if (!rows_given) {
-        if (nAp <= 32) s1_tiles_mfma<8>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-        else s1_tiles_mfma<32>(gya, a.pb.ga_stride, cimg, s1, y0, R, nA, nAp, SS, lc, lq, ly);
-    }
+    // the command image and s1 = Gy[tile rows] C
+    stage_command_and_rows(a, cimg, s1, gya, rows_given, e, y0, tid, nA, nAp, SS, lc, lq, ly);
 
-    double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
+    PupilSums sums;
     // (Gy C)[y0 + i][k] of the band from the operand-layout rows k_dm_rows wrote, ONCE for all its column chunks (as separate
     // 16 x 128 tile workgroups every chunk re-read them: a quarter of the kernel's HBM traffic at 81 actuators across):
     // ga_stride / 4 16-byte loads per lane (<= 8: n_act <= 128), all in flight together
@@ -519,24 +389,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     auto tile4 = [&](const float* map, const LayerTaps& tp, int S, int idx, int mw4, int nr, int nc, int r0, int c0) {
         const int r = idx / mw4, c = 4 * (idx - r * mw4);
         const int rr = r0 + r, cc = c0 + c;
-        const bool need = r < nr && c < nc && rr >= 0 && rr < S && cc >= 0 && cc < S;
-        int pr = rr + tp.oy, pc = cc + tp.ox;                   // torus: physical = (logical + origin) mod S
-        pr = pr >= S ? pr - S : pr;
-        pc = pc >= S ? pc - S : pc;
-        const bool ok = need && cc + 3 < S && pc + 3 < S;        // the 4 columns are contiguous in memory
-        f32x4 t;
-        __builtin_memcpy(&t, map + (ok ? (size_t)pr * S + pc : 0), 16);
-        f32x4 v = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
-        if (need && !ok) {
-            // a float4 that straddles the wrap of the torus or the edge of the screen: element by element
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                int pd = pc + d;
-                pd = pd >= S ? pd - S : pd;
-                if (cc + d < S) v[d] = map[(size_t)pr * S + pd];
-            }
-        }
-        return v;
+        return torus_tile4(map, S, tp.oy, tp.ox, rr, cc, r < nr && c < nc && rr >= 0 && rr < S && cc >= 0 && cc < S);
     };
     if (BAND && a.pa.update_atm) {
         const LayerTaps& tp = layer_taps(a.pa, 0, e);
@@ -556,12 +409,10 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
     }
     for (int xb = 0; xb < (R + TX - 1) / TX; ++xb) {
     const int x0 = xb * TX, txe = min(TX, R - x0);
-    // lane's pixels: sub-tile tt (x = 16 (2 ly + tt) + lc), rows y = 4 lq + r
-    float sup[2][4];
+    // lane's pixels: sub-tile tt, row lc, the four columns x = 16 (2 ly + tt) + 4 lq + r
+    f32x4 sup[2];
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sup[tt][r] = 0.f;
+    for (int tt = 0; tt < 2; ++tt) sup[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (a.pa.update_atm) {
         for (int l = 0; l < (BAND ? 1 : a.pa.n_layer); ++l) {
@@ -593,7 +444,7 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
                 const int xt = 16 * (2 * ly + tt) + 4 * lq;     // tile column of the first tap of the lane's first pixel
-                // the 4 rows x 8 columns of taps (7 used) as 16-byte LDS reads; horizontal pass per row, then vertical
+                // warp_row4 (phase_device.hpp) written out: called from here, the BAND instantiations took 2 more VGPRs
                 float h[4][4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -658,35 +509,13 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
             const size_t q = (size_t)(y0 + lc) * R + (x0 + xl);
             f32x4 atm, phi;
             if (!a.pa.update_atm) atm = *reinterpret_cast<const f32x4*>(a.pb.opd_atm + pix0 + q);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (a.pa.update_atm) atm[r] = sup[tt][r] * a.atm_scale;
-                const bool in = pup[tt][r];
-                const float res = in ? (atm[r] + dmv[r]) : 0.f;
-                phi[r] = res * a.src_scale;
-                if (in) {
-                    const double da = (double)atm[r], dr = (double)res;
-                    s_atm += da;
-                    q_atm += da * da;
-                    s_res += dr;
-                    q_res += dr * dr;
-                }
-            }
+            residual_pixel4(a.pa.update_atm, sup[tt], dmv, pup[tt], a.atm_scale, a.src_scale, atm, phi, sums);
             if (a.pa.update_atm && a.pa.store_atm) *reinterpret_cast<f32x4*>(a.pb.opd_atm + pix0 + q) = atm;
             if (a.pa.store_phase) *reinterpret_cast<f32x4*>(a.pb.phase + pix0 + q) = phi;
         }
     }
     }
-    s_atm = wave_sum(s_atm);
-    q_atm = wave_sum(q_atm);
-    s_res = wave_sum(s_res);
-    q_res = wave_sum(q_res);
-    if (lx == 0) {
-        red[0][ly] = s_atm;
-        red[1][ly] = q_atm;
-        red[2][ly] = s_res;
-        red[3][ly] = q_res;
-    }
+    reduce_pupil_sums(sums, red, lx, ly);
     __syncthreads();
     if (tid < 4 && a.pa.store_phase) {
         // (the telemetry buffer has one slot per 16 x 128 tile, phase_tiles(): the band's sums go to its first slot)

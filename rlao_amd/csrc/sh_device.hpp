@@ -48,11 +48,6 @@ __device__ inline void atomic_max_nonneg(double* addr, double v) {
     if (bits > __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a, bits);
 }
 
-__device__ inline double wave_sum_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
 namespace fast6 {
 constexpr int P = 6, N = 12, LO = 3, HP = 3, SPW = 21, EST = P * P + 1;
 // cos(k pi / 12), k = 0 .. 23

@@ -18,13 +18,16 @@
 //            binning (sh_device.hpp), frame store, workgroup max -> threshold -> centre of gravity in registers
 //   stage C  t = M s, o = -M2C t, integrator, observation image, reward, telemetry (tail_from_slopes)
 //
-// Arithmetic is the same as in the separate kernels (phase_kernel.hip, sh_kernels.hip); only summation orders of the
-// centroid and of the telemetry differ (float32 / float64 rounding level).  No atomics: bitwise reproducible.
+// Stage A's tile load, warp, pixel and pupil sums are the functions of phase_device.hpp that the batched kernels call; against
+// the separate kernels (phase_kernel.hip, sh_kernels.hip) the results differ at rounding level: here the residual OPD is one
+// contracted fma of the layer sum, there a rounded product and an add, and the summation orders of the centroid
+// and of the telemetry differ.  No atomics: bitwise reproducible.
 // (the body of the kernel and its launcher: step_kernel_general.hip, _nocam.hip, _photon.hip and _camera.hip instantiate one
 // value of SPEC each, step_kernel_star.hip the one with per-env guide stars, step_kernel.hip holds the layout and the dispatch)
 #pragma once
 #include "step_kernel.hpp"
 
+#include "phase_device.hpp"
 #include "sh_device.hpp"
 #include "detector.hpp"
 #include "ring_device.hpp"
@@ -249,7 +252,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
     // That is the output layout of the matrix cores for D[x][y] = sum_k Gx^T[k][x] s1[y][k] (rows 4 (lane >> 4) + r = x,
     // column lane & 15 = y), and it makes every global access of the pass a 16-byte one (the vector-memory path takes
     // ~16 cycles per wave-instruction whatever the width: dword accesses were 3/4 of this kernel's time).
-    double s_atm = 0.0, q_atm = 0.0, s_res = 0.0, q_res = 0.0;
+    PupilSums sums;
     for (int pass = 0; pass < (R + PR - 1) / PR; ++pass) {
         const int y0 = pass * PR;
         const int tye = min(PR, R - y0);
@@ -291,23 +294,7 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                     const int r = idx / WC4, c = 4 * (idx - r * WC4);
                     const int rr = rw0 + r, cc = cw0 + c;
                     const bool need = idx < WR * WC4 && 16 * band + r < tye + 3 && 32 * cg + c < R + 3 && rr >= 0 && rr < S && cc >= 0 && cc < S;
-                    int pr = rr + tp.oy, pc = cc + tp.ox;         // torus: physical = (logical + origin) mod S
-                    pr = pr >= S ? pr - S : pr;
-                    pc = pc >= S ? pc - S : pc;
-                    const bool ok = need && cc + 3 < S && pc + 3 < S;      // the 4 columns are contiguous in memory
-                    const float* src = map + (ok ? (size_t)pr * S + pc : 0);
-                    f32x4s t;                                     // the screen rows are only 4-byte aligned (S = R + 6)
-                    __builtin_memcpy(&t, src, 16);
-                    v[q] = ok ? t : f32x4s{0.f, 0.f, 0.f, 0.f};
-                    if (need && !ok) {
-                        // a float4 that straddles the wrap of the torus or the edge of the screen: element by element
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            int pd = pc + d;
-                            pd = pd >= S ? pd - S : pd;
-                            if (cc + d < S) v[q][d] = map[(size_t)pr * S + pd];
-                        }
-                    }
+                    v[q] = torus_tile4(map, S, tp.oy, tp.ox, rr, cc, need);
                 }
 #pragma unroll
                 for (int q = 0; q < NV4; ++q) {
@@ -316,30 +303,14 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
                 }
             }
             asm volatile("" ::: "memory");
-            const float wx0 = (float)tp.wx[0], wx1 = (float)tp.wx[1], wx2 = (float)tp.wx[2], wx3 = (float)tp.wx[3];
-            const float wy0 = (float)tp.wy[0], wy1 = (float)tp.wy[1], wy2 = (float)tp.wy[2], wy3 = (float)tp.wy[3];
+            const float wx[4] = {(float)tp.wx[0], (float)tp.wx[1], (float)tp.wx[2], (float)tp.wx[3]};
+            const float wy[4] = {(float)tp.wy[0], (float)tp.wy[1], (float)tp.wy[2], (float)tp.wy[3]};
             const float lo = lohi[l][0], hi = lohi[l][1], wl = (float)tp.weight;
             const bool zero_outside = (lo > 0.f || hi < 0.f);
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
                 const int xt = 16 * tt + 4 * lq;                  // wave-tile column of the first tap of the lane's first pixel
-                // the 4 rows x 8 columns of taps (7 used) as 16-byte LDS reads; horizontal pass per row, then vertical
-                float h[4][4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float* m = mapt + (lc + q) * WC + xt;
-                    const f32x4s m0 = *reinterpret_cast<const f32x4s*>(m), m1 = *reinterpret_cast<const f32x4s*>(m + 4);
-                    const float t[7] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2]};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[q][r] = ((wx0 * t[r] + wx1 * t[r + 1]) + wx2 * t[r + 2]) + wx3 * t[r + 3];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = ((wy0 * h[0][r] + wy1 * h[1][r]) + wy2 * h[2][r]) + wy3 * h[3][r];
-                    // skimage clip=True: clamp to the input range, keep exact zeros when 0 is outside it
-                    if (!(zero_outside && v == 0.f)) v = v < lo ? lo : (v > hi ? hi : v);
-                    sup[tt][r] += v * wl;
-                }
+                warp_row4(mapt, WC, lc, xt, wx, wy, lo, hi, zero_outside, wl, sup[tt]);
             }
         }
 
@@ -356,20 +327,8 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
             if (row_ok && x < R) {
                 const size_t q = (size_t)y * R + x;
                 f32x4s atm, phi;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    atm[r] = sup[tt][r] * k.atm_scale;
-                    const bool in = apv[tt][r] >= 0.f;
-                    const float res = in ? (atm[r] + dmv[r]) : 0.f;
-                    phi[r] = res * k.src_scale;
-                    if (in) {
-                        const double da = (double)atm[r], dr = (double)res;
-                        s_atm += da;
-                        q_atm += da * da;
-                        s_res += dr;
-                        q_res += dr * dr;
-                    }
-                }
+                const bool in[4] = {apv[tt][0] >= 0.f, apv[tt][1] >= 0.f, apv[tt][2] >= 0.f, apv[tt][3] >= 0.f};   // -1 = outside the pupil
+                residual_pixel4(true, sup[tt], dmv, in, k.atm_scale, k.src_scale, atm, phi, sums);
                 if (k.pa.store_atm) *reinterpret_cast<f32x4s*>(k.pb.opd_atm + pix0 + q) = atm;
                 if (a.store_phase) *reinterpret_cast<f32x4s*>(k.pb.phase + pix0 + q) = phi;   // only where it can be read (StepArgs)
                 // lenslet (i, j) element E[a][b] = phase[i p + b][j p + a]: the reference tiles phase.T
@@ -397,15 +356,12 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
         }
     }
     // telemetry: waves in a fixed order
-    s_atm = wave_sum_f64(s_atm);
-    q_atm = wave_sum_f64(q_atm);
-    s_res = wave_sum_f64(s_res);
-    q_res = wave_sum_f64(q_res);
+    sums.wave_reduce();                                        // (red stored here, not through reduce_pupil_sums: DESIGN.md 4.3a)
     if (lane == 0) {
-        red[0][w] = s_atm;
-        red[1][w] = q_atm;
-        red[2][w] = s_res;
-        red[3][w] = q_res;
+        red[0][w] = sums.s_atm;
+        red[1][w] = sums.q_atm;
+        red[2][w] = sums.s_res;
+        red[3][w] = sums.q_res;
     }
     lds_barrier();                                             // E0 complete, red complete, cimg / s1 / layer tiles dead
     // the camera's tables on their way into LDS (no registers, nobody waits): they land while the spots are computed
