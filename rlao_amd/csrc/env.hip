@@ -2860,7 +2860,7 @@ int aoenv_set_policy(AoEnv* env, const AoPolicy* cfg, void* stream) {
     AoEnv::Policy p;
     p.H = H; p.F = F; p.Kp = Kp;
     p.slope = cfg->negative_slope; p.clamp_abs = cfg->clamp_abs; p.b3 = cfg->h_b3[0];
-    p.mfma = env->esz == 4 && cfg->path == 0 && F % 16 == 0 && policy_mfma_fits(env->nAct, C1) && policy_mfma_fits(env->nAct, F);
+    p.mfma = policy_uses_mfma(env->esz, cfg->path, F, env->nAct, C1);
     const size_t z = env->esz, hid = (size_t)env->E * F * env->nAct * env->nAct * z;
     auto build = [&]() -> int {
         AO_TRY(dmalloc(env, &p.w1, n1 * z, false)); AO_TRY(upload_real(env, p.w1, cfg->h_w1, n1));

@@ -63,6 +63,11 @@ inline size_t policy_conv_lds(int n_act, int c_in) {
 }
 // (n_act >= 2: the staging loop divides by multiplication, whose constants need divisors above 1)
 inline bool policy_mfma_fits(int n_act, int c_in) { return n_act >= 2 && n_act <= kPolicyBandPixels && policy_conv_lds(n_act, c_in) <= kPolicyLdsMax; }
+// which convolution kernel a policy gets (aoenv_set_policy): the MFMA kernel on a float32 shard unless path = 1 asks for the
+// general one, the filters are no whole N tiles, or a band of either wide layer (c1 = 2H - 1 and n_filt input channels) does not fit
+inline bool policy_uses_mfma(size_t esz, int path, int n_filt, int n_act, int c1) {
+    return esz == 4 && path == 0 && n_filt % 16 == 0 && policy_mfma_fits(n_act, c1) && policy_mfma_fits(n_act, n_filt);
+}
 
 // y = leaky(conv3x3(x) + b) on the matrix cores, float32.  wt: the weights in operand order [kstep][F / 16][64] (policy_relayout)
 int launch_policy_conv_mfma(const ConvIn<float>& in, const float* wt, const float* bias, float* out, int n_act, int n_filt,
@@ -72,7 +77,16 @@ template <typename T>
 int launch_policy_conv_general(const ConvIn<T>& in, const T* w, const T* bias, T* out, int n_act, int n_filt, T slope, int n_env,
                                hipStream_t st);
 // host: torch layout [F][C][3][3] (float64) -> operand order, float32, zero in the K padding
-void policy_relayout(const double* w, int n_filt, int c_in, std::vector<float>& out);
+inline void policy_relayout(const double* w, int n_filt, int c_in, std::vector<float>& out) {
+    const int K = 9 * c_in, ksteps = policy_ksteps(c_in), nt = n_filt / 16;
+    out.assign((size_t)ksteps * nt * 64, 0.0f);
+    for (int ks = 0; ks < ksteps; ++ks)
+        for (int t = 0; t < nt; ++t)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int k = 4 * ks + (lane >> 4), f = 16 * t + (lane & 15);
+                if (k < K) out[((size_t)ks * nt + t) * 64 + lane] = (float)w[(size_t)f * K + k];
+            }
+}
 
 // last stage: conv3 + bias + clamp at the valid actuators, the factored projection, exploration noise, scatter
 template <typename T>
@@ -92,7 +106,10 @@ struct PolicyActionArgs {
     int n_act, n_valid_act, n_filt, proj_rank, n_filter;
     uint32_t seed_lo, seed_hi, counter, env_offset;
 };
-size_t policy_action_lds(int n_valid_act, int proj_rank, int n_filter, size_t esz);
+// LDS of the last stage: two vectors over the valid actuators (padded to 4) and the inner vector of the wider factor pair
+inline size_t policy_action_lds(int n_valid_act, int proj_rank, int n_filter, size_t esz) {
+    return ((size_t)2 * ((n_valid_act + 3) & ~3) + std::max(proj_rank, n_filter)) * esz;
+}
 template <typename T>
 int launch_policy_action(const PolicyActionArgs<T>& a, int n_env, hipStream_t st);
 

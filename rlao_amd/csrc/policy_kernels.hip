@@ -299,21 +299,6 @@ template int launch_policy_conv_general<float>(const ConvIn<float>&, const float
 template int launch_policy_conv_general<double>(const ConvIn<double>&, const double*, const double*, double*, int, int, double, int,
                                                 hipStream_t);
 
-void policy_relayout(const double* w, int n_filt, int c_in, std::vector<float>& out) {
-    const int K = 9 * c_in, ksteps = policy_ksteps(c_in), nt = n_filt / 16;
-    out.assign((size_t)ksteps * nt * 64, 0.0f);
-    for (int ks = 0; ks < ksteps; ++ks)
-        for (int t = 0; t < nt; ++t)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int k = 4 * ks + (lane >> 4), f = 16 * t + (lane & 15);
-                if (k < K) out[((size_t)ks * nt + t) * 64 + lane] = (float)w[(size_t)f * K + k];
-            }
-}
-
-size_t policy_action_lds(int n_valid_act, int proj_rank, int n_filter, size_t esz) {
-    return ((size_t)2 * ((n_valid_act + 3) & ~3) + std::max(proj_rank, n_filter)) * esz;
-}
-
 template <typename T>
 int launch_policy_action(const PolicyActionArgs<T>& a, int n_env, hipStream_t st) {
     const size_t lds = policy_action_lds(a.n_valid_act, a.proj_rank, a.n_filter, sizeof(T));

@@ -1,7 +1,9 @@
 """CPU: the host side of the on-device policy (aoenv_set_policy / aoenv_policy_forward / aoenv_run_policy_rollout): the ctypes
 mirror of AoPolicy against the compiled header, the float64 restatement of tests/_policy_ref.py against a torch module of the
 reference's shape, the weight extraction of rlao_amd.env.policy_arrays, and the history roll against the literal lines of
-MAIN/PO4AO/mbrl.py:80-81."""
+MAIN/PO4AO/mbrl.py:80-81.  The host model of the MFMA convolution (rlao_amd/csrc/policy.hpp: the band plan, the kernel selection,
+the weight relayout, the channel gather) through the stand-alone driver tests/native/policy_driver.cpp against NumPy
+restatements, over every image size and channel count the ABI allows; the driver once more under ASan + UBSan."""
 import ctypes as C
 import os
 import subprocess
@@ -112,3 +114,162 @@ def test_history_roll_equals_the_trainer_loop(n_steps):
         new = torch.as_tensor(traj[k])
         past = torch.cat([past[:, 1:, :, :], new.unsqueeze(1)], dim=1)          # mbrl.py:80 with a leading env dimension
     assert np.array_equal(P.roll(past0, traj, n_steps), past.numpy())
+
+
+# ---- the host model of the MFMA convolution: rlao_amd/csrc/policy.hpp through tests/native/policy_driver.cpp ---------------------
+CHANNELS = list(range(1, 64, 2)) + list(range(16, 129, 16))          # 2H - 1 for H = 1 .. 32, and n_filt in whole N tiles
+DOMAIN = [(a, c) for a in range(2, 257) for c in CHANNELS]
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = P.build_driver(tmp_path_factory.mktemp("policy"))
+    if exe is None:
+        pytest.skip("hipcc not available")
+    return exe
+
+
+@pytest.fixture(scope="module")
+def plans(driver):
+    got, _ = P.host_plans(driver, DOMAIN)
+    return got
+
+
+def test_band_plan_is_the_restatement_and_keeps_its_invariants(driver, plans):
+    rows, bands, lds, lds1, fits, ksteps = plans.T
+    a, c = np.array(DOMAIN).T
+    want = np.array([P.bands(*p) + (P.conv_lds(*p), P.conv_lds_rows(*p, 1), int(P.mfma_fits(*p)), P.ksteps(p[1])) for p in DOMAIN])
+    assert np.array_equal(plans, want)
+    ok = fits == 1
+    assert ((bands - 1) * rows < a)[ok].all() and (a <= bands * rows)[ok].all() and (rows >= 1).all() and (bands >= 1).all()   # no empty band
+    assert ((rows * a <= P.BAND_PIXELS) | (rows == 1))[ok].all()
+    assert (rows * a <= P.BAND_PIXELS)[ok].all()                    # (a <= 256: one row is a band, too)
+    assert (lds <= P.LDS_MAX)[ok].all()
+    # two workgroups share a CU exactly when one row fits in half a CU
+    assert np.array_equal((lds <= P.LDS_MAX // 2)[ok], (lds1 <= P.LDS_MAX // 2)[ok])
+    assert (ksteps == -(-9 * c // 4)).all()
+    # the MFMA kernel is refused for an image above 256 or below 2 across and for an LDS overflow, and for nothing else
+    assert np.array_equal(fits == 0, lds > P.LDS_MAX)
+    extra = [(1, 1), (1, 128), (257, 1), (300, 16), (256, 1), (2, 1)]
+    got, _ = P.host_plans(driver, extra)
+    assert got[:, 4].tolist() == [0, 0, 0, 0, 1, 1] and (got[:4, 2] <= P.LDS_MAX).any()
+    first = lambda ch: min(x for (x, cc), f in zip(DOMAIN, fits) if cc == ch and not f)
+    assert first(128) == 102 and first(64) == 208
+
+
+def test_staging_divides_exactly_by_multiplication(plans):
+    """The staging loop of k_policy_conv_mfma splits i < C span into (channel, row, column) with two multiplications by
+    ceil(2^32 / span) and ceil(2^32 / a) (the high word).  span: the source rows of a band, clipped to the image.  For every band
+    of every fitting plan both are the true quotients (grouped by divisor: the longest range of a divisor covers the shorter)."""
+    span_range, act_range, largest = {}, {}, 0
+    for (a, c), (rows, bands, _, _, fits, _) in zip(DOMAIN, plans.tolist()):
+        if not fits:
+            continue
+        for b in {0, 1, bands - 2, bands - 1} & set(range(bands)):
+            y0 = b * rows
+            r = min(rows, a - y0)
+            span = (min(y0 + r + 1, a) - max(y0 - 1, 0)) * a
+            span_range[span] = max(span_range.get(span, 0), c * span)
+            act_range[a] = max(act_range.get(a, 0), span)
+            largest = max(largest, c * span)
+    assert largest < 128 * 768                                      # the range the kernel's comment claims
+    for ranges in (span_range, act_range):
+        for d, n in ranges.items():
+            i = np.arange(n, dtype=np.uint64)
+            m = np.uint64(((1 << 32) + d - 1) // d)
+            assert np.array_equal((i * m) >> np.uint64(32), i // np.uint64(d)), d
+
+
+@pytest.mark.parametrize("c_in", [1, 3, 5, 11, 63, 16, 128])
+def test_relayout_puts_every_weight_in_its_lane(driver, c_in):
+    """Weight (f, k) lands at [k / 4][f / 16][16 (k % 4) + f % 16]; the K padding is zero"""
+    n_filt = 128 if c_in == 128 else (48 if c_in == 11 else 16)
+    K = 9 * c_in
+    w = (np.arange(n_filt * K, dtype=np.float64) + 1).reshape(n_filt, c_in, 3, 3)     # every weight its own value, exact in float32
+    got, _ = P.host_relayout(driver, w)
+    assert got.shape == (P.ksteps(c_in), n_filt // 16, 64) and got.dtype == np.float32
+    f, k = np.divmod(np.arange(n_filt * K), K)
+    want = np.zeros_like(got)
+    want[k // 4, f // 16, 16 * (k % 4) + f % 16] = w.ravel()
+    assert np.array_equal(got, want)
+    assert (got != 0).sum() == n_filt * K and got.size - n_filt * K == n_filt * (4 * P.ksteps(c_in) - K)
+
+
+@pytest.mark.parametrize("H", [1, 2, 4, 32])
+def test_channel_gather_is_the_window_of_the_restatement(driver, H):
+    """k below, at and above H - 1: every channel of the first layer comes from where _policy_ref.window takes it"""
+    E = 3
+    for k in sorted({0, 1, max(H - 2, 0), H - 1, H, H + 3}):
+        # arrays of labels: value = kind * 10000 + index * 10 + env
+        label = lambda kind, idx, e: kind * 10000 + idx * 10 + e
+        traj = {kind: np.array([[label(kind, s, e) for e in range(E)] for s in range(k + 1)], dtype=np.float64)[:, :, None, None]
+                for kind in (1, 2)}
+        past = {kind: np.array([[label(kind, r, e) for r in range(H - 1)] for e in range(E)], dtype=np.float64).reshape(E, H - 1, 1, 1)
+                for kind in (3, 4)}
+        want = np.concatenate([traj[1][k][:, None], P.window(past[3], traj[1], k), P.window(past[4], traj[2], k)], axis=1)[:, :, 0, 0]
+        for e in range(E):
+            got, _ = P.host_channels(driver, H, k, E, e)
+            assert len(got) == 2 * H - 1
+            names = {"O": 1, "A": 2, "PO": 3, "PA": 4}
+            assert [label(names[kind], idx, e) for kind, idx in got] == want[e].astype(int).tolist(), (H, k, e)
+
+
+def test_exact_case_reference_is_the_restatement():
+    """The reference of the GPU sweep's exact cases (_policy_ref.exact_case: the convolutions as matrix products) against the
+    restatement the tests above pin to torch: the same bits on exact data, with and without the projection."""
+    a, H, n_filt, n = 7, 3, 16, 3
+    idx = np.sort(np.random.RandomState(3).choice(a * a, 37, replace=False))
+    w = P.exact_weights(H, n_filt, seed=1)
+    x = P.exact_inputs(n, H, a, seed=2)
+    fr, fl = P.exact_factors(idx.size, seed=3)
+    assert (np.abs(fr) > 0).sum(axis=1).max() <= 8 and set(np.unique(w["w2"])) == {-1.0, 0.0, 1.0} and np.abs(x[0]).max() == 2
+    case = P.exact_case(w, x, idx, (fr, fl))
+    assert np.array_equal(P.layers(w, *x)[2], P.network(w, *x))
+    assert np.array_equal(case["plain"], P.policy(w, *x, idx, None, case["clamp"]))
+    assert np.array_equal(case["proj"], P.policy(w, *x, idx, fl @ fr, case["clamp"]))
+    assert np.log2(case["clamp"]) % 1 == 0 and max(case["quanta"]) < 2 ** 24
+
+
+SWEEP = [(a, H, F) for a, cases in P.SWEEP_CASES.items() for H, F in cases]
+GENERAL = [(4, 1, 64, 21, 39), (8, 0, 64, 21, 39), (4, 0, 24, 9, 5), (4, 0, 72, 9, 5), (4, 0, 128, 102, 7), (4, 0, 16, 300, 5),
+           (4, 0, 64, 300, 63), (8, 1, 16, 9, 1)]                   # path 1, float64, n_filt % 16, LDS overflow, a > 256
+
+
+def test_kernel_selection(driver):
+    """Every case of the GPU sweep takes the MFMA kernel on a float32 shard with path 0 -- so the sweep cannot pass through the
+    general kernel -- and path 1, a float64 shard, a ragged filter count and an image that does not fit take the general one."""
+    got, _ = P.host_select(driver, [(4, 0, F, a, 2 * H - 1) for a, H, F in SWEEP])
+    assert len(got) == 20 and all(got)
+    for esz, path in ((4, 1), (8, 0), (8, 1)):
+        got, _ = P.host_select(driver, [(esz, path, F, a, 2 * H - 1) for a, H, F in SWEEP])
+        assert not any(got), (esz, path)
+    got, _ = P.host_select(driver, GENERAL)
+    assert not any(got)
+    got, _ = P.host_select(driver, [(4, 0, 128, 101, 7), (4, 0, 64, 207, 7), (4, 0, 16, 256, 1), (4, 0, 16, 2, 1)])
+    assert all(got)
+
+
+def test_driver_is_clean_under_asan_and_ubsan(driver, tmp_path):
+    """The same requests in a stand-alone sanitized program, run directly: a clean exit, no report, the same answers."""
+    exe = P.build_driver(tmp_path, sanitize=True)
+    if exe is None:
+        pytest.skip("hipcc not available")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    clean = lambda err: "ERROR: AddressSanitizer" not in err and "runtime error" not in err
+    pairs = DOMAIN[::7] + [(1, 1), (300, 16)]
+    got, err = P.host_plans(exe, pairs, env=env)
+    assert clean(err), err
+    assert np.array_equal(got, P.host_plans(driver, pairs)[0])
+    sel = [(4, 0, F, a, 2 * H - 1) for a, H, F in SWEEP] + GENERAL
+    got, err = P.host_select(exe, sel, env=env)
+    assert clean(err), err
+    assert got == [True] * len(SWEEP) + [False] * len(GENERAL)
+    for c_in, n_filt in ((1, 16), (63, 16), (128, 128)):
+        w = (np.arange(n_filt * 9 * c_in, dtype=np.float64) + 1).reshape(n_filt, c_in, 3, 3)
+        got, err = P.host_relayout(exe, w, env=env)
+        assert clean(err), err
+        assert np.array_equal(got, P.host_relayout(driver, w)[0])
+    for H, k in ((1, 0), (1, 5), (2, 0), (4, 2), (4, 3), (32, 0), (32, 31), (32, 40)):
+        got, err = P.host_channels(exe, H, k, 3, 2, env=env)
+        assert clean(err), err
+        assert got == P.host_channels(driver, H, k, 3, 2)[0]
