@@ -588,8 +588,52 @@ int aoenv_run_policy_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void
 /* Replaces: tel.computePSF(zeroPaddingFactor) (OOPAO/Telescope.py:258-357) of the current residual phase (tel.src.phase):
  * d_psf [n_env][M][M], M = zero_padding * R (even), env dtype: the short-exposure PSF of every env.  As the reference does for even
  * image sizes (oversampling 2, :303-305), the field is transformed at N = 2 M and |fftshift(fft2(E phasor)) / N|^2 is sum-binned 2 x 2.
+ * For odd R (M still even) the reference pads ceil((2 M - R) / 2) on both sides and transforms at 2 M + 1 (:320-325): the image is then
+ * formed as the science window below with W = M, not by the 2 M-point transform.
  * Science-path rendering (MAIN/OOPAOEnv/OOPAOEnv.py:473-482, integrator_network.py:93-95); not part of the step. */
 int aoenv_compute_psf(AoEnv* env, int zero_padding, void* d_psf, void* stream);
+
+/* Replaces: the long-exposure PSF and its Strehl ratio as the reference's evaluation scripts form them on the host from one full
+ * render per step,
+ *     env.tel.computePSF(4); SE_PSFs.append(env.tel.PSF[175:-175, 175:-175]); LE_SR = max(mean(SE_PSFs)) / psf_model_max
+ * (MAIN_CODE/predictiveControl/POL_error_CL.py; MAIN_CODE/integrator_network.py:134-138), and the mean of log10(PSF) over the frames
+ * current_i > 15 of render4plot (MAIN_CODE/OOPAOEnv/OOPAOEnv.py:473-482).  The model is rlao_amd/csrc/science.hpp: the W x W window
+ * around the core of tel.computePSF(zero_padding) -- output pixel (a, b) is pixel (M/2 - W/2 + a, M/2 - W/2 + b) of the M x M image,
+ * M = zero_padding * R -- without the full transform: the 2 W oversampled rows the window needs are the rows of a table F [2W][R],
+ * into which the reference's padding offset, ifftshift and even-size phasor fold (OOPAO/Telescope.py:320-332), and
+ *     window = bin2x2(|F E F^T|^2) / n_fft^2,   E = amp * exp(i phase)   (R x R),
+ * two small complex products per env: on the fp32 matrix cores for float32 shards (k_science_window_mfma), as fma chains for
+ * float64 shards, under AOENV_PATH_SCI_GENERAL and where the matrix-core plan refuses (k_science_window).  n_fft is the reference's
+ * transform length, 2 M for even R and 2 M + 1 for odd R (its padding is ceil((2 M - R) / 2) on both sides).  The order of every sum
+ * depends on (R, W) alone and there are no atomics: an env has the same bits in any shard and at any place in it.
+ * aoenv_set_science copies the table (evaluated in float64 on the reduced integer angle, rounded once to the env dtype; or h_dft
+ * in its place) and the amplitude to the device before it returns and waits for the stream once.  The amplitude is that of
+ * aoenv_compute_psf: AOENV_C_WFS_AMP, times sqrt(pyr_n_theta) on a Pyramid shard; per-env flux does not enter.  Like the wavefront
+ * basis it is configuration: in no checkpoint buffer.  A NULL cfg forgets it and detaches the accumulators; so do a new
+ * configuration and an upload of AOENV_C_PUPIL or AOENV_C_WFS_AMP.
+ * Refused, with nothing changed: zero_padding outside [1, 8], zero_padding * R odd, window odd or outside [2, zero_padding * R],
+ * first_frame < 0, an unknown flag, an entry of h_dft that is not finite in the env dtype, no amplitude uploaded.
+ * No buffer id, no profiled kernel and no ABI version go with it. */
+enum AoScienceFlag { AOENV_SCI_LOG10 = 1 };
+typedef struct AoScience {
+    int32_t zero_padding;   /* zp */
+    int32_t window;         /* W */
+    int32_t first_frame;    /* stepped frames i >= first_frame are accumulated (reference: current_i > 15 -> 16) */
+    int32_t flags;
+    const double* h_dft;    /* NULL: the library's table; else [2W][R][2] (re, im), used in its place */
+} AoScience;
+int aoenv_set_science(AoEnv* env, const AoScience* cfg, void* stream);
+/* The window of AOENV_B_PHASE as it is now (flat != 0: of a zero phase, the diffraction-limited PSF the Strehl ratio divides by)
+ * into d_out [n_env][W][W], env dtype.  One launch, no scratch, no wait.  Refused: nothing set, a null d_out. */
+int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream);
+/* The long exposure.  d_sum and d_sum_log10 [n_env][W][W] (env dtype) and d_count [n_env] are caller-owned device buffers, zeroed
+ * by the caller; the library holds the pointers only.  While attached, every stepped frame i >= first_frame of aoenv_step,
+ * aoenv_step_modal, aoenv_run_integrator, aoenv_run_integrator_modal, aoenv_run_rollout and aoenv_run_policy_rollout adds the
+ * window of the residual the sensor saw in that step (the content AOENV_B_PHASE has after it) to d_sum, its log10 to d_sum_log10,
+ * and 1 to d_count: one extra launch per accumulated step.  Such a loop step stores the phase it otherwise skips, not the
+ * camera frame; the loop's state and every output are bit for bit what they are without it, and a fused shard stays fused.
+ * d_sum_log10 must be non-null exactly when AOENV_SCI_LOG10 is set.  NULL d_sum detaches; no stream is waited for. */
+int aoenv_set_science_accumulator(AoEnv* env, void* d_sum, void* d_sum_log10, int32_t* d_count);
 
 /* Replaces: the WFS camera settings wfs.cam.{photonNoise, readoutNoise, QE, darkCurrent, integrationTime, FWC, bits, gain,
  * sensor} (OOPAO/Detector.py:19-60; Papyrus: photonNoise = True, MAIN/OOPAOEnv/OOPAOEnv.py:379; Razor:
@@ -663,7 +707,7 @@ enum AoOption {
                                  lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
                                  whose winds stay below one pixel per frame nothing: the same launches */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN and AOENV_PATH_WF_GENERAL also keeps the shard off the fused step
+                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL and AOENV_PATH_SCI_GENERAL also keeps the shard off the fused step
                                  kernel; other bits are rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
@@ -679,6 +723,9 @@ enum AoPath {
     AOENV_PATH_WF_GENERAL = 8192,      /* the wavefront projection (aoenv_project_wavefront, the record) as one fma chain per (env, mode,
                                           slice) on float32 shards too, instead of the matrix-core kernel.  Like AOENV_PATH_MODAL_GEMM
                                           it touches nothing inside the step and leaves the shard on the fused step kernel */
+    AOENV_PATH_SCI_GENERAL = 16384,    /* the science window (aoenv_science_psf, the long exposure) as fma chains on float32 shards
+                                          too, instead of the matrix-core kernel.  Like AOENV_PATH_WF_GENERAL it touches nothing
+                                          inside the step and leaves the shard on the fused step kernel */
     AOENV_PATH_SH_PLAIN = 4096         /* the general instantiation of the fused step kernel (run-time camera and trig tests, the
                                           pixel-by-pixel stage A epilogue) and the plain C++ lenslet transform, there and in the
                                           batched spots kernel, instead of the forms specialised for the launch and the register-pair

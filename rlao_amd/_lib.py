@@ -26,6 +26,8 @@ OPT_FORCE_PATH = 99
 MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
 PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN, PATH_WF_GENERAL = 256, 512, 1024, 2048, 4096, 8192
+PATH_SCI_GENERAL = 16384
+SCI_LOG10 = 1                                                      # enum AoScienceFlag
 WF_RESIDUAL, WF_ATMOSPHERE = 1, 2                                  # enum AoWavefront
 MAX_WF_MODES = 1024                                                # AOENV_MAX_WF_MODES
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
@@ -69,6 +71,11 @@ class AoModal(C.Structure):
 
 class AoWavefrontBasis(C.Structure):
     _fields_ = [("n_modes", C.c_int32), ("n_pix", C.c_int32), ("h_opd2m", C.c_void_p)]
+
+
+class AoScience(C.Structure):
+    _fields_ = [("zero_padding", C.c_int32), ("window", C.c_int32), ("first_frame", C.c_int32), ("flags", C.c_int32),
+                ("h_dft", C.c_void_p)]
 
 
 EXPORTS = {
@@ -124,6 +131,9 @@ EXPORTS = {
     "aoenv_run_policy_rollout": (C.c_int, [C.c_void_p, C.POINTER(AoRollout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_compute_psf": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "aoenv_set_science": (C.c_int, [C.c_void_p, C.POINTER(AoScience), C.c_void_p]),
+    "aoenv_science_psf": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "aoenv_set_science_accumulator": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

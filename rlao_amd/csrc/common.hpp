@@ -464,6 +464,24 @@ int launch_wf_project(const WfArgs<T>& a, bool general, hipStream_t st);
 template <typename T>
 int launch_wf_finish(const WfArgs<T>& a, hipStream_t st);
 
+// science window (science_kernels.hip; the model, the table and the plan are science.hpp): the W x W core of every env's
+// short-exposure PSF, stored to `out` or added to the long-exposure accumulators -- exactly one of `out` and `sum` is set.
+// general: the fma-chain kernel also on float32 (AOENV_PATH_SCI_GENERAL); float64, and a plan the matrix-core kernel refuses, take it
+template <typename T>
+struct SciArgs {
+    const T* phase;        // [E][R][R] AOENV_B_PHASE; not read when flat
+    const T* amp;          // [R][R] the field's amplitude, 0 outside the pupil
+    const T* table;        // [2][up][rp] (science.hpp)
+    T* out;                // [E][W][W], or null
+    T* sum;                // [E][W][W] += the window, or null
+    T* sum_log10;          // [E][W][W] += log10(window), or null
+    int32_t* count;        // [E] += 1 (with sum), or null
+    T scale;               // 1 / n_fft^2
+    int n_env, R, W, flat;
+};
+template <typename T>
+int launch_science_window(const SciArgs<T>& a, bool general, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

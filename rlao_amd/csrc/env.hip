@@ -16,6 +16,7 @@
 #include "modal.hpp"
 #include "policy.hpp"
 #include "sh_device.hpp"
+#include "science.hpp"
 #include "star_env.hpp"
 #include "wavefront.hpp"
 
@@ -165,6 +166,19 @@ struct AoEnv {
         int rec_what = 0, i_base = 0, n_slots = 0;
         int recorded() const { return rec ? rec_what : 0; }
     } wf;
+    // science camera (aoenv_set_science, science.hpp): configuration like the wavefront basis, in ONE allocation of its own (not in
+    // `allocs`: a NULL config frees it); the long-exposure accumulators are the caller's memory
+    struct Science {
+        bool set = false;
+        SciGeom g{};
+        int first_frame = 0, flags = 0;
+        void* base = nullptr;
+        void* table = nullptr;              // [2][up][rp] the DFT rows of the window
+        void* amp = nullptr;                // [R*R] the field's amplitude (aoenv_compute_psf's)
+        void *sum = nullptr, *sum_log10 = nullptr;   // caller-owned [E][W][W] each, or null: nothing is accumulated
+        int32_t* count = nullptr;           // caller-owned [E]
+        bool accumulates(int i) const { return sum && i >= first_frame; }
+    } sci;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -820,7 +834,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL)) == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -890,7 +904,8 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     StepArgs a{};
     PhaseArgs pa;
     PhaseBuffers<float> pb;
-    // (a wavefront record reads the phase -- and the atmosphere, if it records it -- of EVERY step: both stores, not the frame's)
+    // (a wavefront record reads the phase -- and the atmosphere, if it records it -- of EVERY step: both stores, not the frame's;
+    // the long exposure reads the phase of every frame it accumulates)
     const int rec = env->wf.recorded();
     fill_phase_args<float>(env, pa, pb, 1, (env->store_opd_atm || (rec & AOENV_WF_ATMOSPHERE)) ? 1 : 0, 1);
     a.k = make_phase_kargs<float>(pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
@@ -901,7 +916,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.frame = env->as<float>(env->frame);
     // (atm.OPD written every step is the state-inspection mode: every step is then observable, there is no fast path to keep)
     a.store_frame = (observable || env->store_opd_atm) ? 1 : 0;
-    a.store_phase = (a.store_frame || rec) ? 1 : 0;
+    a.store_phase = (a.store_frame || rec || env->sci.accumulates(i)) ? 1 : 0;
     a.signal = env->as<float>(env->signal);
     a.wfs_max = env->as<float>(env->wfs_max);
     a.fac_m = env->as<float>(env->fac_m);
@@ -1075,6 +1090,37 @@ static int wf_window_check(const AoEnv* env, int i0, int n) {
     return 0;
 }
 
+// ---- science camera (science.hpp, science_kernels.hip) -----------------------------------------------------------------------------
+// The window of the phase buffer as it stands (flat: of a zero phase), stored to `out` or -- out == null -- added to the attached
+// accumulators.  One launch, not attributed by aoenv_profile.
+template <typename T>
+int sci_window(AoEnv* env, int flat, void* out, hipStream_t st) {
+    const AoEnv::Science& sc = env->sci;
+    SciArgs<T> a{};
+    a.phase = env->as<T>(env->phase);
+    a.amp = env->as<T>(sc.amp);
+    a.table = env->as<T>(sc.table);
+    a.out = static_cast<T*>(out);
+    if (!out) {
+        a.sum = env->as<T>(sc.sum);
+        a.sum_log10 = env->as<T>(sc.sum_log10);
+        a.count = sc.count;
+    }
+    a.scale = sci_scale<T>(sc.g);
+    a.n_env = env->E;
+    a.R = env->R;
+    a.W = sc.g.W;
+    a.flat = flat ? 1 : 0;
+    return launch_science_window<T>(a, (env->force_path & AOENV_PATH_SCI_GENERAL) != 0, st);
+}
+
+// frame i of a stepped loop into the long exposure, if accumulators are attached and the frame counts
+template <typename T>
+int sci_accumulate_step(AoEnv* env, int i, hipStream_t st) {
+    if (!env->sci.accumulates(i)) return 0;
+    return sci_window<T>(env, 0, nullptr, st);
+}
+
 template <typename T>
 int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
            double gain, bool observable, hipStream_t st) {
@@ -1087,6 +1133,7 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
         AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, observable, st));
         env->step_cmd = nullptr;
         AO_TRY(wf_record_step<T>(env, i, st));
+        AO_TRY(sci_accumulate_step<T>(env, i, st));
         if (d_frame)
             AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                                   hipMemcpyDeviceToDevice, st));
@@ -1094,6 +1141,7 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
     }
     AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE)) ? 1 : 0, st));
     AO_TRY(wf_record_step<T>(env, i, st));                         // (the phase kernel has written what the sensor is about to see)
+    AO_TRY(sci_accumulate_step<T>(env, i, st));
     env->step_cmd = nullptr;                                       // the integration below, and a dense DM's next surface: the pure command
     // one workgroup per env re-reads the factors from L2: wins while launch latency dominates (measured: 19.5 us vs
     // 32.5 us at 256 envs, 96 us vs 75 us at 2048), the batched MFMA GEMM path takes over for large shards
@@ -1490,6 +1538,7 @@ int aoenv_destroy(AoEnv* env) {
     if (env->star.thr) (void)hipFree(env->star.thr);
     if (env->modal.base) (void)hipFree(env->modal.base);
     if (env->wf.base) (void)hipFree(env->wf.base);
+    if (env->sci.base) (void)hipFree(env->sci.base);
     delete env;
     return 0;
 }
@@ -1498,6 +1547,12 @@ int aoenv_destroy(AoEnv* env) {
 static void wf_forget(AoEnv* env) {
     if (env->wf.base) (void)hipFree(env->wf.base);
     env->wf = AoEnv::Wavefront{};
+}
+
+// no science camera (science.hpp): the table and the amplitude freed, the accumulators detached
+static void sci_forget(AoEnv* env) {
+    if (env->sci.base) (void)hipFree(env->sci.base);
+    env->sci = AoEnv::Science{};
 }
 
 int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
@@ -1516,6 +1571,7 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             env->n_pupil = 0;
             for (size_t i = 0; i < R2; ++i) env->n_pupil += pu[i] != 0;
             wf_forget(env);                                         // a wavefront basis is indexed by the pupil's pixels
+            sci_forget(env);                                        // ... and the science camera looks through it
             break;
         }
         case AOENV_C_AB:
@@ -1570,6 +1626,7 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             AO_TRY(upload_real(env, env->amp, d, R2));
             env->h_amp.assign(d, d + R2);
             env->amp_pupil_dirty = true;
+            sci_forget(env);                                        // the science camera holds a copy of the amplitude
             break;
         case AOENV_C_SH_SUBAP_IDX: {
             AO_TRY(need((size_t)env->nVal * 4));
@@ -2676,6 +2733,95 @@ int aoenv_set_wavefront_record(AoEnv* env, int what, void* d_rec, int i_base, in
     return 0;
 }
 
+// ---- science camera (science.hpp) --------------------------------------------------------------------------------------------------
+static_assert(kSciLog10 == AOENV_SCI_LOG10, "science.hpp and aoenv.h disagree");
+
+extern "C++" {
+template <typename T>
+static int sci_set(AoEnv* env, const AoScience* cfg, hipStream_t st) {
+    const int R = env->R;
+    const size_t R2 = (size_t)R * R;
+    size_t where = 0;
+    switch (sci_validate<T>(R, cfg->zero_padding, cfg->window, cfg->first_frame, cfg->flags, cfg->h_dft, &where)) {
+        case kSciOk: break;
+        case kSciZp: return fail("aoenv_set_science: zeroPaddingFactor %d outside [1, %d]", cfg->zero_padding, kSciMaxZp);
+        case kSciOddImage: return fail("aoenv_set_science: odd image sizes are not built (zero_padding %d x resolution %d)", cfg->zero_padding, R);
+        case kSciWindowOdd: return fail("aoenv_set_science: window %d is odd", cfg->window);
+        case kSciWindowRange: return fail("aoenv_set_science: window %d outside [2, zero_padding * resolution = %d]", cfg->window, cfg->zero_padding * R);
+        case kSciFirstFrame: return fail("aoenv_set_science: first_frame %d is negative", cfg->first_frame);
+        case kSciFlags: return fail("aoenv_set_science: flags %d: only AOENV_SCI_LOG10 is known", cfg->flags);
+        case kSciNotFinite: return fail("aoenv_set_science: dft[%zu] is not finite in the env dtype", where);
+    }
+    if (env->h_amp.size() != R2) return fail("aoenv_set_science: the WFS amplitude has not been uploaded");
+    const SciGeom g = sci_geom(R, cfg->zero_padding, cfg->window);
+    const SciPlan pl = sci_plan(R, cfg->window);
+    const size_t nt = sci_table_elems(pl);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    std::vector<T> host(al(nt * sizeof(T)) / sizeof(T) + R2);
+    sci_fill_table<T>(g, pl, cfg->h_dft, host.data());
+    // the amplitude of aoenv_compute_psf: pupil * sqrt(src.fluxMap), all modulation points of a Pyramid together
+    const double scale = env->c.wfs_type == AOENV_WFS_PYRAMID ? std::sqrt((double)env->c.pyr_n_theta) : 1.0;
+    T* amp = host.data() + al(nt * sizeof(T)) / sizeof(T);
+    for (size_t q = 0; q < R2; ++q) amp[q] = (T)(env->h_amp[q] * scale);
+    AO_HIP(hipStreamSynchronize(st));                              // a window in flight reads the table in place
+    void* p = nullptr;
+    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("aoenv_set_science: no device memory for %zu bytes of table and amplitude", host.size() * sizeof(T));
+    }
+    if (hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return fail("aoenv_set_science: the copy of the table failed");
+    }
+    sci_forget(env);                                               // (a new configuration detaches the accumulators of the previous one)
+    AoEnv::Science& sc = env->sci;
+    sc.base = sc.table = p;
+    sc.amp = static_cast<char*>(p) + al(nt * sizeof(T));
+    sc.g = g;
+    sc.first_frame = cfg->first_frame;
+    sc.flags = cfg->flags;
+    sc.set = true;
+    return 0;
+}
+}  // extern "C++"
+
+int aoenv_set_science(AoEnv* env, const AoScience* cfg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!cfg) {
+        AO_HIP(hipStreamSynchronize(st));
+        sci_forget(env);
+        return 0;
+    }
+    return env->c.dtype == AOENV_F32 ? sci_set<float>(env, cfg, st) : sci_set<double>(env, cfg, st);
+}
+
+int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->sci.set) return fail("aoenv_science_psf: no science camera is set (aoenv_set_science)");
+    if (!d_out) return fail("aoenv_science_psf: null output");
+    return AO_DISPATCH(env, sci_window, env, flat, d_out, static_cast<hipStream_t>(stream));
+}
+
+int aoenv_set_science_accumulator(AoEnv* env, void* d_sum, void* d_sum_log10, int32_t* d_count) {
+    AO_CHECK_ENV(env);
+    AoEnv::Science& sc = env->sci;
+    if (!d_sum) {
+        sc.sum = sc.sum_log10 = nullptr;
+        sc.count = nullptr;
+        return 0;
+    }
+    if (!sc.set) return fail("aoenv_set_science_accumulator: no science camera is set (aoenv_set_science)");
+    if (!d_count) return fail("aoenv_set_science_accumulator: null count");
+    if ((sc.flags & AOENV_SCI_LOG10) && !d_sum_log10) return fail("aoenv_set_science_accumulator: AOENV_SCI_LOG10 is set and d_sum_log10 is null");
+    if (!(sc.flags & AOENV_SCI_LOG10) && d_sum_log10) return fail("aoenv_set_science_accumulator: d_sum_log10 given without AOENV_SCI_LOG10");
+    sc.sum = d_sum;
+    sc.sum_log10 = d_sum_log10;
+    sc.count = d_count;
+    return 0;
+}
+
 // ---- the control delay (delay.hpp) ------------------------------------------------------------------------------------------------
 static_assert(kMaxDelay == AOENV_MAX_DELAY, "delay.hpp and aoenv.h disagree");
 int aoenv_set_delay(AoEnv* env, int delay, void* stream) {
@@ -3016,8 +3162,42 @@ int aoenv_run_policy_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void
 }
 
 extern "C++" {
+// Odd R: the reference pads ceil((2 M - R) / 2) pixels on both sides and transforms at 2 M + 1 (Telescope.py:320-325), a length
+// the transform below (2 M points, the field centred on one of them) does not take.  The whole image is then the science window
+// with W = M (science.hpp: the DFT rows as a table, two products per env), from scratch of this call.
+template <typename T>
+static int compute_psf_odd_t(AoEnv* env, int zp, void* d_psf, hipStream_t st) {
+    const int R = env->R, M = zp * R;
+    const size_t R2 = (size_t)R * R;
+    if (env->h_amp.size() != R2) return fail("the WFS amplitude has not been uploaded");
+    const SciGeom g = sci_geom(R, zp, M);
+    const SciPlan pl = sci_plan(R, M);
+    const size_t nt = sci_table_elems(pl);
+    std::vector<T> host(nt + R2);
+    sci_fill_table<T>(g, pl, nullptr, host.data());
+    const double scale = env->c.wfs_type == AOENV_WFS_PYRAMID ? std::sqrt((double)env->c.pyr_n_theta) : 1.0;
+    for (size_t q = 0; q < R2; ++q) host[nt + q] = (T)(env->h_amp[q] * scale);
+    TmpFree tmp;
+    T* d_tab;
+    AO_TRY(tmp.get((void**)&d_tab, host.size() * sizeof(T)));
+    AO_HIP(hipMemcpyAsync(d_tab, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    SciArgs<T> a{};
+    a.phase = env->as<T>(env->phase);
+    a.table = d_tab;
+    a.amp = d_tab + nt;
+    a.out = static_cast<T*>(d_psf);
+    a.scale = sci_scale<T>(g);
+    a.n_env = env->E;
+    a.R = R;
+    a.W = M;
+    AO_TRY(launch_science_window<T>(a, (env->force_path & AOENV_PATH_SCI_GENERAL) != 0, st));
+    AO_HIP(hipStreamSynchronize(st));                              // the scratch is released on return
+    return 0;
+}
+
 template <typename T>
 static int compute_psf_t(AoEnv* env, int zp, void* d_psf, hipStream_t st) {
+    if (env->R % 2) return compute_psf_odd_t<T>(env, zp, d_psf, st);
     // the reference runs the transform at oversampling 2 for every even image size and sum-bins |.|^2 2 x 2 (Telescope.py:303-305)
     const int R = env->R, N = 2 * zp * R;
     const size_t R2 = (size_t)R * R;
@@ -3285,7 +3465,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             return 0;
         case AOENV_OPT_FORCE_PATH:
             if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN |
-                          AOENV_PATH_WF_GENERAL))
+                          AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

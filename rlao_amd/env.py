@@ -294,6 +294,28 @@ def resolve_wavefront_basis(m2opd, opd2m, n_modes, n_pix: int) -> np.ndarray:
     return np.ascontiguousarray(out, dtype=np.float64)
 
 
+def resolve_science(R: int, zero_padding=4, window=None, first_frame=16, log10=False, dft=None) -> dict:
+    """The configuration of a ``set_science`` call as the library is handed it: ``zero_padding``, ``window`` (default: the
+    reference's 130 where the image has that many pixels, else the whole image), ``first_frame``, ``flags`` and ``dft`` -- None, or
+    float64 ``[2 W, R, 2]`` (re, im), C-contiguous; a complex ``[2 W, R]`` array is split.  What has no meaning raises here; what the
+    library's own validation refuses (an odd window, one larger than the image, ...) is left to it."""
+    zp, R = int(zero_padding), int(R)
+    if window is None:
+        window = 130 if zp * R >= 130 else zp * R
+    W = int(window)
+    if int(first_frame) < 0:
+        raise ValueError("set_science: first_frame >= 0")
+    if dft is not None:
+        a = np.asarray(dft)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (2 * W, R, 2):
+            raise ValueError(f"set_science: dft has shape {a.shape}, expected (2 * window, resolution, 2) = {(2 * W, R, 2)}")
+        dft = a
+    return dict(zero_padding=zp, window=W, first_frame=int(first_frame), flags=L.SCI_LOG10 if log10 else 0, dft=dft)
+
+
 _WF_BITS = {"residual": L.WF_RESIDUAL, "atmosphere": L.WF_ATMOSPHERE}
 
 
@@ -1011,6 +1033,8 @@ class BatchedAOEnv:
         self._surface = "zonal"                                    # which surface the last observation came from: "zonal" | "modal"
         self._wf = None                                            # resolve_wavefront_basis()'s table while a wavefront basis is set
         self._wf_rec = None                                        # the tensor of an attached wavefront record (kept alive here)
+        self._sci = None                                           # resolve_science()'s dict while a science camera is set
+        self._le = None                                            # (sum, sum_log10 or None, count) of an attached long exposure
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
         self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
         self.source = self.ngs = None
@@ -1125,6 +1149,7 @@ class BatchedAOEnv:
         self._mag_env = self._thr_env = None                         # ... and one star, the calibrated one
         self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
         self._wf = self._wf_rec = None                               # ... and no wavefront basis (it is indexed by the pupil's pixels)
+        self._sci = self._le = None                                  # ... and no science camera (it holds the pupil's amplitude)
         self._surface = "zonal"
         sh = self._shard
         at = self._atm_tables
@@ -1741,6 +1766,115 @@ class BatchedAOEnv:
         the caller's reference."""
         L.check(self._shard.lib.aoenv_set_wavefront_record(self._shard.h, 0, None, 0, 0))
         self._wf_rec = None
+
+    # -- science camera (aoenv_set_science; the reference's windowed tel.computePSF and its long exposure) ---------------------------
+    def set_science(self, zero_padding=4, window=None, first_frame=16, log10=False, dft=None):
+        """The science camera: ``science_psf()`` then gives the ``window`` x ``window`` core of ``tel.computePSF(zero_padding)``
+        -- ``tel.PSF[M/2 - W/2 : M/2 + W/2]`` on both axes, the reference's ``PSF[175:-175, 175:-175]`` at its geometry -- from two
+        small matrix products per env instead of the full transform, and ``start_long_exposure()`` accumulates it in every loop
+        (MAIN_CODE/predictiveControl/POL_error_CL.py, integrator_network.py:134-138, OOPAOEnv.py:473-482).  ``window``: even, at
+        most ``zero_padding * resolution``; default 130 where the image is that large, else the whole image.  ``first_frame``:
+        stepped frames ``i >= first_frame`` are accumulated (the reference's ``current_i > 15``).  ``log10``: also accumulate
+        ``log10`` of the window (``render4plot``'s quantity).  ``dft``: a table ``[2 W, R]`` complex (or ``[2 W, R, 2]``) used in
+        place of the library's DFT rows.  A new configuration detaches a long exposure.  Not part of ``get_state``: ``set_state``
+        does not restore it."""
+        cfg = resolve_science(self.R, zero_padding, window, first_frame, log10, dft)
+        c = L.AoScience(zero_padding=cfg["zero_padding"], window=cfg["window"], first_frame=cfg["first_frame"], flags=cfg["flags"],
+                        h_dft=None if cfg["dft"] is None else cfg["dft"].ctypes.data_as(C.c_void_p))
+        L.check(self._shard.lib.aoenv_set_science(self._shard.h, C.byref(c), C.c_void_p(self._stream())))
+        self._sci, self._le = cfg, None
+
+    def clear_science(self):
+        """No science camera: the table and its device memory are gone, a long exposure is detached."""
+        L.check(self._shard.lib.aoenv_set_science(self._shard.h, None, C.c_void_p(self._stream())))
+        self._sci = self._le = None
+
+    @property
+    def science(self):
+        """The configuration of the science camera (``resolve_science``'s dict), None while none is set."""
+        return None if self._sci is None else dict(self._sci)
+
+    def _require_science(self):
+        if self._sci is None:
+            raise L.AoEnvError("no science camera is set: call set_science() first")
+
+    def _require_long_exposure(self):
+        if self._le is None:
+            raise L.AoEnvError("no long exposure is attached: call start_long_exposure() first")
+
+    def _science_window(self, flat):
+        W = self._sci["window"]
+        out = _torch().empty((self.n_envs, W, W), device=self.device, dtype=self.tdtype)
+        L.check(self._shard.lib.aoenv_science_psf(self._shard.h, 1 if flat else 0, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream())))
+        return out
+
+    def science_psf(self, flat=False):
+        """The window ``[n_envs, W, W]`` of the short-exposure PSF of the residual phase as it stands (``flat=True``: of a flat
+        wavefront, the diffraction-limited PSF).  A new tensor every call; a float64 NumPy ``[W, W]`` for the single-env flavour,
+        as ``tel.computePSF``."""
+        self._require_science()
+        return self._out(self._science_window(flat))
+
+    def start_long_exposure(self):
+        """Allocates, zeroes and attaches the long-exposure accumulators: from here on every stepped frame ``i >= first_frame`` of
+        ``step``, ``step_modal``, ``run_integrator``, ``run_integrator_modal``, ``rollout`` and ``policy_rollout`` adds its window
+        (one extra launch per accumulated step; the loops' results do not change by a bit).  ``reset_envs`` does not touch the
+        accumulators: zero the restarted envs with ``zero_long_exposure(env_ids)`` where an episode's exposure is wanted."""
+        self._require_science()
+        torch = _torch()
+        W = self._sci["window"]
+        acc = torch.zeros((self.n_envs, W, W), device=self.device, dtype=self.tdtype)
+        acc_log = torch.zeros_like(acc) if self._sci["flags"] & L.SCI_LOG10 else None
+        count = torch.zeros((self.n_envs,), device=self.device, dtype=torch.int32)
+        L.check(self._shard.lib.aoenv_set_science_accumulator(
+            self._shard.h, C.c_void_p(acc.data_ptr()), None if acc_log is None else C.c_void_p(acc_log.data_ptr()),
+            C.c_void_p(count.data_ptr())))
+        self._le = (acc, acc_log, count)
+
+    def zero_long_exposure(self, env_ids=None):
+        """Zeroes the accumulators (sum, log10 sum and count) of the chosen envs, all of them by default."""
+        self._require_long_exposure()
+        if env_ids is None:
+            for t in self._le:
+                if t is not None:
+                    t.zero_()
+            return
+        ids = normalize_env_ids(env_ids, self.n_envs)
+        sel = _torch().as_tensor(np.asarray(ids).astype(np.int64), device=self.device)
+        for t in self._le:
+            if t is not None:
+                t.index_fill_(0, sel, 0)
+
+    def stop_long_exposure(self):
+        """Detaches the accumulators; the loops run as without them.  The read-outs keep answering from what was accumulated until
+        the next ``start_long_exposure`` / ``set_science``."""
+        L.check(self._shard.lib.aoenv_set_science_accumulator(self._shard.h, None, None, None))
+
+    def _le_mean(self, acc, count):
+        torch = _torch()
+        n = count.to(acc.dtype)[:, None, None]
+        return torch.where(n > 0, acc / torch.clamp(n, min=1), torch.zeros_like(acc))
+
+    def long_exposure(self):
+        """``(sum / count, count)``: the mean window ``[n_envs, W, W]`` over the accumulated frames (zeros where the count is 0) and
+        the per-env frame count."""
+        self._require_long_exposure()
+        acc, _, count = self._le
+        return self._le_mean(acc, count), count.clone()
+
+    def long_exposure_log10(self):
+        """The mean of ``log10`` of the window over the accumulated frames: ``render4plot``'s ``LE_PSF``, on the window."""
+        self._require_long_exposure()
+        acc, acc_log, count = self._le
+        if acc_log is None:
+            raise L.AoEnvError("the science camera was set without log10=True")
+        return self._le_mean(acc_log, count)
+
+    def long_exposure_strehl(self):
+        """``amax(long exposure) / amax(science_psf(flat=True))`` per env: the scripts' ``LE_SR``."""
+        self._require_long_exposure()
+        le, _ = self.long_exposure()
+        return le.amax(dim=(1, 2)) / self._science_window(True).amax(dim=(1, 2))
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

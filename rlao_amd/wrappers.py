@@ -139,6 +139,37 @@ class TorchWrapper:
     def stop_wavefront_record(self):
         return self._env.stop_wavefront_record()
 
+    def set_science(self, zero_padding=4, window=None, first_frame=16, log10=False, dft=None):
+        return self._env.set_science(zero_padding=zero_padding, window=window, first_frame=first_frame, log10=log10, dft=dft)
+
+    def clear_science(self):
+        return self._env.clear_science()
+
+    @property
+    def science(self):
+        return self._env.science
+
+    def science_psf(self, flat=False):
+        return self._env.science_psf(flat)
+
+    def long_exposure(self):
+        return self._env.long_exposure()
+
+    def long_exposure_log10(self):
+        return self._env.long_exposure_log10()
+
+    def long_exposure_strehl(self):
+        return self._env.long_exposure_strehl()
+
+    def start_long_exposure(self):
+        return self._env.start_long_exposure()
+
+    def zero_long_exposure(self, env_ids=None):
+        return self._env.zero_long_exposure(env_ids)
+
+    def stop_long_exposure(self):
+        return self._env.stop_long_exposure()
+
     def rollout(self, i0, n_steps, sigma, gain=None, seed=None, sigma_env=None):
         """``BatchedAOEnv.rollout`` in this wrapper's return convention: float32 tensors."""
         torch = _torch()
@@ -249,6 +280,28 @@ class TimeDelayEnv:
     def project_wavefront(self, what="residual"):
         return self._env.project_wavefront(what)
 
+    def set_science(self, zero_padding=4, window=None, first_frame=16, log10=False, dft=None):
+        return self._env.set_science(zero_padding=zero_padding, window=window, first_frame=first_frame, log10=log10, dft=dft)
+
+    def clear_science(self):
+        return self._env.clear_science()
+
+    @property
+    def science(self):
+        return self._env.science
+
+    def science_psf(self, flat=False):
+        return self._env.science_psf(flat)
+
+    def long_exposure(self):
+        return self._env.long_exposure()
+
+    def long_exposure_log10(self):
+        return self._env.long_exposure_log10()
+
+    def long_exposure_strehl(self):
+        return self._env.long_exposure_strehl()
+
     def step(self, i, action):
         self.action_buffer.append(action)
         out = self._env.step(i, self.action_buffer[0])
@@ -355,6 +408,28 @@ class HistoryEnv:
 
     def project_wavefront(self, what="residual"):
         return self._env.project_wavefront(what)
+
+    def set_science(self, zero_padding=4, window=None, first_frame=16, log10=False, dft=None):
+        return self._env.set_science(zero_padding=zero_padding, window=window, first_frame=first_frame, log10=log10, dft=dft)
+
+    def clear_science(self):
+        return self._env.clear_science()
+
+    @property
+    def science(self):
+        return self._env.science
+
+    def science_psf(self, flat=False):
+        return self._env.science_psf(flat)
+
+    def long_exposure(self):
+        return self._env.long_exposure()
+
+    def long_exposure_log10(self):
+        return self._env.long_exposure_log10()
+
+    def long_exposure_strehl(self):
+        return self._env.long_exposure_strehl()
 
     def _alloc(self):
         torch = _torch()
