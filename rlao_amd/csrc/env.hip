@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "delay.hpp"
+#include "dev_block.hpp"
 #include "dm_tables.hpp"
 #include "detector.hpp"
 #include "disturb.hpp"
@@ -74,6 +75,18 @@ struct Layer {
 
 using namespace ao;
 
+// The primitives of the owner of every device allocation (DevBlock, dev_block.hpp) on HIP.  A failure leaves no error pending.
+struct HipMem {
+    static bool ok(hipError_t e) { if (e != hipSuccess) (void)hipGetLastError(); return e == hipSuccess; }
+    static bool alloc(void** p, size_t bytes) { return ok(hipMalloc(p, bytes)); }
+    static void free(void* p) { (void)hipFree(p); }              // (waits for the device)
+    static bool zero(void* p, size_t bytes) { return ok(hipMemset(p, 0, bytes)); }
+    static bool copy_in(void* dst, const void* src, size_t bytes) { return ok(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); }
+};
+using Block = DevBlock<HipMem>;
+
+#define AO_DISPATCH(env, fn, ...) ((env)->c.dtype == AOENV_F32 ? fn<float>(__VA_ARGS__) : fn<double>(__VA_ARGS__))
+
 struct AoEnv {
     AoCfg c{};
     int device = 0;
@@ -128,6 +141,7 @@ struct AoEnv {
         bool set = false;
         int M = 0, J = 0;
         int64_t t0 = 0;
+        Block mem;                          // both tables; replaced by a larger block when either must grow
         void* modes_t = nullptr;            // [M][A] B transposed, env dtype
         double* par = nullptr;              // amp, freq, phase: [E][M][J] float64 each, one after the other
         size_t modes_cap = 0, par_cap = 0;  // elements the two are sized for
@@ -138,13 +152,13 @@ struct AoEnv {
     void* delay_ring = nullptr;
     size_t delay_stride = 0;                // elements between slots
     void* delay_slot(int slot) const { return static_cast<char*>(delay_ring) + (size_t)slot * delay_stride * esz; }
-    // modal control surface (aoenv_set_modal, modal.hpp): configuration like the disturbance, in ONE allocation of its own (not in
-    // `allocs`: a NULL basis frees it)
+    // modal control surface (aoenv_set_modal, modal.hpp): configuration like the disturbance, in ONE block of its own (a NULL basis
+    // frees it)
     struct Modal {
         bool set = false, have_gain = false;
         int K = 0;
         size_t gain_env = 0;                // 0: one gain row for every env, K: a row per env
-        void* base = nullptr;
+        Block mem;
         void* m2c_t = nullptr;              // [K][A] M2C transposed
         void* cm = nullptr;                 // [K][nSig] modal command matrix
         void* gain = nullptr;               // [E][K] (the first row alone when gain_env == 0)
@@ -153,26 +167,26 @@ struct AoEnv {
         void* zscal = nullptr;              // [2][E] its reward, and a Strehl row nobody asked for
         void* slabs = nullptr;              // [splits][E][K] products of the GEMM path
     } modal;
-    // wavefront modes (aoenv_set_wavefront_basis, wavefront.hpp): configuration like the modal basis, in ONE allocation of its own
-    // (not in `allocs`: a NULL basis frees it); the record is the caller's memory
+    // wavefront modes (aoenv_set_wavefront_basis, wavefront.hpp): configuration like the modal basis, in ONE block of its own (a NULL
+    // basis frees it); the record is the caller's memory
     struct Wavefront {
         bool set = false;
         int K = 0;
         WfPlan plan{};
-        void* base = nullptr;
+        Block mem;
         void* p = nullptr;                  // [K][wf_row_stride(R^2)] the projector on the full grid
         void* slabs = nullptr;              // [n_slices][2][E][K]
         void* rec = nullptr;                // caller-owned [n_slots][W][E][K], or null: nothing is recorded
         int rec_what = 0, i_base = 0, n_slots = 0;
         int recorded() const { return rec ? rec_what : 0; }
     } wf;
-    // science camera (aoenv_set_science, science.hpp): configuration like the wavefront basis, in ONE allocation of its own (not in
-    // `allocs`: a NULL config frees it); the long-exposure accumulators are the caller's memory
+    // science camera (aoenv_set_science, science.hpp): configuration like the wavefront basis, in ONE block of its own (a NULL config
+    // frees it); the long-exposure accumulators are the caller's memory
     struct Science {
         bool set = false;
         SciGeom g{};
         int first_frame = 0, flags = 0;
-        void* base = nullptr;
+        Block mem;
         void* table = nullptr;              // [2][up][rp] the DFT rows of the window
         void* amp = nullptr;                // [R*R] the field's amplitude (aoenv_compute_psf's)
         void *sum = nullptr, *sum_log10 = nullptr;   // caller-owned [E][W][W] each, or null: nothing is accumulated
@@ -196,18 +210,19 @@ struct AoEnv {
     float* gxa = nullptr;                   // gx / gy re-laid out as MFMA operand tables (ga_index(), common.hpp), zero padded to Rpad128
     float* gya = nullptr;
     int ga_stride = 8;                      // k steps per (row, q), a multiple of 4 (16-byte loads), >= ceil(nAct / 4)
-    // per-env mirrors (aoenv_set_dm_env): E blocks of every layout of the shared tables (dm_tables.hpp) in ONE allocation of its own
-    // (not in `allocs`: returning to the shared tables frees it); the kernels are handed these pointers and the block sizes as
-    // per-env strides while `on`, the shared tables and stride 0 otherwise
+    // per-env mirrors (aoenv_set_dm_env): E blocks of every layout of the shared tables (dm_tables.hpp) in ONE block of its own
+    // (returning to the shared tables frees it); the kernels are handed these pointers and the block sizes as per-env strides while
+    // `on`, the shared tables and stride 0 otherwise
     struct DmEnv {
         bool on = false;
-        void* base = nullptr;
+        Block mem;
         void *gx = nullptr, *gy = nullptr, *gxt = nullptr;
         float *gxa = nullptr, *gya = nullptr;
     } dm_env;
-    // per-env guide stars (aoenv_set_flux_env / aoenv_set_threshold_env, star_env.hpp): [E] each in the env dtype, an allocation of
-    // its own each (not in `allocs`: NULL frees it); absent = null, and the kernels are then handed null pointers
+    // per-env guide stars (aoenv_set_flux_env / aoenv_set_threshold_env, star_env.hpp): [E] each in the env dtype, a block of its
+    // own each (NULL frees it); absent = null, and the kernels are then handed null pointers
     struct StarDev {
+        Block amp_mem, thr_mem;
         void* amp = nullptr;                // sqrt of the env's flux relative to the uploaded AOENV_C_WFS_AMP
         void* thr = nullptr;                // the env's centroid threshold
     } star;
@@ -226,7 +241,8 @@ struct AoEnv {
     void* fac_m2c_t = nullptr;              // [K][A]    transposed M2C
     void* fac_m2c = nullptr;                // [A][Kp]   M2C, rows zero padded to Kp = n_modes rounded up to 4 (16-byte rows)
     void* tbuf = nullptr;                   // [splits][E][Kp] modal coefficients t = M s of the factored reconstruction
-    size_t fac_cap = 0;                     // modes the two buffers above are sized for
+    Block fac_mem;                          // the two buffers above; replaced by a larger block when the rank outgrows it
+    size_t fac_cap = 0;                     // modes it is sized for
     bool use_factored_recon = true;         // aoenv_set_option(AOENV_OPT_FACTORED_RECON)
     int n_modes = 0;
     // Pyramid
@@ -248,6 +264,7 @@ struct AoEnv {
     // exploration rollout (aoenv_run_rollout): the noise filter F = Fl Fr in factored form, the inverse of act_idx, the stream position
     void* noise_fr = nullptr;               // [K][A]
     void* noise_fl_t = nullptr;             // [K][A] Fl transposed
+    Block noise_mem;                        // the two factors; replaced by a larger block when they must grow
     size_t noise_cap = 0;                   // elements each of the two is sized for
     int noise_K = 0;                        // 0: no filter (n = z)
     std::vector<int32_t> h_act_idx;         // host copy of AOENV_C_ACT_IDX
@@ -257,16 +274,17 @@ struct AoEnv {
     uint32_t explore_counter = 0;           // word 1 of AOENV_B_COUNTERS
     uint64_t explore_seed = 0;
     bool explore_seeded = false;            // false: the counter (0, or an uploaded checkpoint's) belongs to the next call's seed
-    // the policy (aoenv_set_policy): weights in the env dtype (torch layout), the two wide layers re-laid for the MFMA kernel,
-    // the projection factors, the two hidden images [E][n_filt][nAct^2]
+    // the policy (aoenv_set_policy), in ONE block: weights in the env dtype (torch layout), the two wide layers re-laid for the MFMA
+    // kernel, the projection factors, the two hidden images [E][n_filt][nAct^2]
     struct Policy {
         bool set = false, mfma = false;
+        Block mem;
         int H = 0, F = 0, Kp = 0;
         double slope = 0, clamp_abs = 0, b3 = 0;
         void *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *wt1 = nullptr, *wt2 = nullptr;
         void *proj_fr = nullptr, *proj_fl_t = nullptr, *hid1 = nullptr, *hid2 = nullptr;
     } policy;
-    std::vector<void*> allocs;
+    std::vector<Block> allocs;              // what dmalloc handed out: for the shard's life
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool use_fast_wfs = true;               // aoenv_set_option(AOENV_OPT_FAST_WFS)
     bool use_mfma = true;                   // aoenv_set_option(AOENV_OPT_MFMA_GEMM)
@@ -301,13 +319,24 @@ static int alloc_dm_rows(AoEnv* env) {
     }
     return 0;
 }
+// what every block of `parts` that cannot be had reports, unless its caller has words of its own
+int block_alloc(Block& b, std::initializer_list<size_t> parts, bool zero) {
+    return b.alloc(parts, zero) ? fail("no device memory for %zu bytes", dev_layout(parts).total) : 0;
+}
 int dmalloc(AoEnv* env, void** p, size_t bytes, bool zero) {
-    if (bytes == 0) bytes = 16;
-    AO_HIP(hipMalloc(p, bytes));
-    env->allocs.push_back(*p);
-    if (zero) AO_HIP(hipMemset(*p, 0, bytes));
+    Block b;
+    AO_TRY(block_alloc(b, {bytes ? bytes : 16}, zero));
+    *p = b.part(0);
+    env->allocs.push_back(std::move(b));
     return 0;
 }
+// Scratch of one reset, released on every exit path.  The resets return with the kernels that read it still queued on the stream:
+// the free of a block waits for the device (dev_block.hpp), which is what keeps this safe.
+struct TmpFree {
+    std::vector<Block> p;
+    int get(std::initializer_list<size_t> parts) { p.emplace_back(); return block_alloc(p.back(), parts, false); }   // one more block ...
+    template <typename T> T* part(int k) const { return static_cast<T*>(p.back().part(k)); }                         // ... and its part k
+};
 
 // Wraps one kernel launch in a hipEvent pair when profiling is enabled (events are recorded on the same
 // stream as the kernel, so the elapsed time is that kernel's device time plus its launch gap).
@@ -334,8 +363,31 @@ int upload_f64(void* dst, const double* src, size_t n) {
     return 0;
 }
 
-int upload_real(AoEnv* env, void* dst, const double* src, size_t n) {
-    return env->c.dtype == AOENV_F32 ? upload_f64<float>(dst, src, n) : upload_f64<double>(dst, src, n);
+int upload_real(AoEnv* env, void* dst, const double* src, size_t n) { return AO_DISPATCH(env, upload_f64, dst, src, n); }
+
+// ... and back: n values of the env dtype on the device as float64 on the host
+template <typename T>
+int download_f64(double* dst, const void* src, size_t n) {
+    std::vector<T> tmp(n);
+    AO_HIP(hipMemcpy(tmp.data(), src, n * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) dst[i] = (double)tmp[i];
+    return 0;
+}
+int download_real(AoEnv* env, double* dst, const void* src, size_t n) { return AO_DISPATCH(env, download_f64, dst, src, n); }
+
+// src [rows][cols] on the host into dst [cols][rows] in the env dtype
+int upload_transposed(AoEnv* env, void* dst, const double* src, size_t rows, size_t cols) {
+    std::vector<double> t(rows * cols);
+    for (size_t r = 0; r < rows; ++r)
+        for (size_t c = 0; c < cols; ++c) t[c * rows + r] = src[r * cols + c];
+    return upload_real(env, dst, t.data(), t.size());
+}
+
+// index of the first entry of h[0, n) that is not finite; n when every entry is
+size_t first_not_finite(const double* h, size_t n) {
+    size_t i = 0;
+    while (i < n && std::isfinite(h[i])) ++i;
+    return i;
 }
 
 double sgn(double v) { return (v > 0) - (v < 0); }
@@ -1259,6 +1311,11 @@ int step_modal_t(AoEnv* env, int i, const void* d_coef, bool use_gain, void* d_o
 }
 
 template <typename T>
+int reset_soft_t(AoEnv* env, void* d_obs, hipStream_t st) {
+    return run_recon<T>(env, nullptr, static_cast<T*>(d_obs), nullptr, nullptr, -1, 0, 0.0, st);
+}
+
+template <typename T>
 int reset_soft_modal_t(AoEnv* env, void* d_obs, hipStream_t st) {
     AO_TRY(run_recon<T>(env, nullptr, env->as<T>(env->modal.zobs), nullptr, nullptr, -1, 0, 0.0, st));
     return modal_project<T>(env, d_obs, nullptr, nullptr, st);
@@ -1345,8 +1402,6 @@ int atm_update_t(AoEnv* env, hipStream_t st) {
     env->atm_user_defined = false;
     return run_phase<T>(env, 1, 1, st);
 }
-
-#define AO_DISPATCH(env, fn, ...) ((env)->c.dtype == AOENV_F32 ? fn<float>(__VA_ARGS__) : fn<double>(__VA_ARGS__))
 
 extern "C" {
 
@@ -1532,27 +1587,8 @@ int aoenv_destroy(AoEnv* env) {
     if (!env) return 0;
     DeviceGuard ao_device_guard(env->device);
     for (auto& e : env->prof_ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (void* p : env->allocs) (void)hipFree(p);
-    if (env->dm_env.base) (void)hipFree(env->dm_env.base);
-    if (env->star.amp) (void)hipFree(env->star.amp);
-    if (env->star.thr) (void)hipFree(env->star.thr);
-    if (env->modal.base) (void)hipFree(env->modal.base);
-    if (env->wf.base) (void)hipFree(env->wf.base);
-    if (env->sci.base) (void)hipFree(env->sci.base);
-    delete env;
+    delete env;                                                    // every block frees itself, on the env's device
     return 0;
-}
-
-// no wavefront basis (wavefront.hpp): the projector and the slabs freed, the record detached
-static void wf_forget(AoEnv* env) {
-    if (env->wf.base) (void)hipFree(env->wf.base);
-    env->wf = AoEnv::Wavefront{};
-}
-
-// no science camera (science.hpp): the table and the amplitude freed, the accumulators detached
-static void sci_forget(AoEnv* env) {
-    if (env->sci.base) (void)hipFree(env->sci.base);
-    env->sci = AoEnv::Science{};
 }
 
 int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
@@ -1570,8 +1606,8 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             env->amp_pupil_dirty = true;
             env->n_pupil = 0;
             for (size_t i = 0; i < R2; ++i) env->n_pupil += pu[i] != 0;
-            wf_forget(env);                                         // a wavefront basis is indexed by the pupil's pixels
-            sci_forget(env);                                        // ... and the science camera looks through it
+            env->wf = AoEnv::Wavefront{};                           // a wavefront basis is indexed by the pupil's pixels
+            env->sci = AoEnv::Science{};                            // ... and the science camera looks through it
             break;
         }
         case AOENV_C_AB:
@@ -1626,7 +1662,7 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             AO_TRY(upload_real(env, env->amp, d, R2));
             env->h_amp.assign(d, d + R2);
             env->amp_pupil_dirty = true;
-            sci_forget(env);                                        // the science camera holds a copy of the amplitude
+            env->sci = AoEnv::Science{};                            // the science camera holds a copy of the amplitude
             break;
         case AOENV_C_SH_SUBAP_IDX: {
             AO_TRY(need((size_t)env->nVal * 4));
@@ -1665,15 +1701,13 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             if (K < 1 || K > kMaxModes) return fail("reconstructor rank %d outside [1, %d]", K, kMaxModes);
             AO_TRY(upload_real(env, env->fac_m, d, (size_t)K * env->nSig));
             const double* m2c = d + (size_t)K * env->nSig;
-            std::vector<double> t((size_t)K * env->A);
-            for (int a = 0; a < env->A; ++a)
-                for (int k = 0; k < K; ++k) t[(size_t)k * env->A + a] = m2c[(size_t)a * K + k];
-            AO_TRY(upload_real(env, env->fac_m2c_t, t.data(), t.size()));
+            AO_TRY(upload_transposed(env, env->fac_m2c_t, m2c, env->A, K));
             // the same factors for the batched (non-fused) reconstruction: M with zero rows up to Kp, M2C as [A][Kp]
             const int Kp = (K + 3) & ~3;
             if ((size_t)Kp > env->fac_cap) {
-                AO_TRY(dmalloc(env, &env->fac_m2c, (size_t)env->A * Kp * env->esz));
-                AO_TRY(dmalloc(env, &env->tbuf, (size_t)kMaxSplits * env->E * Kp * env->esz));
+                AO_TRY(block_alloc(env->fac_mem, {(size_t)env->A * Kp * env->esz, (size_t)kMaxSplits * env->E * Kp * env->esz}, true));
+                env->fac_m2c = env->fac_mem.part(0);
+                env->tbuf = env->fac_mem.part(1);
                 env->fac_cap = (size_t)Kp;
             }
             if (Kp > K && Kp <= kMaxModes)
@@ -1709,17 +1743,8 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
 static int alloc_env_clocks(AoEnv* env) {
     if (env->env_taps) return 0;
     const size_t n = (size_t)env->L * env->E;
-    for (int b = 0; b < 2; ++b) {
-        void* p_ = nullptr;
-        AO_HIP(hipMalloc(&p_, n * sizeof(EnvClock)));
-        env->allocs.push_back(p_);
-        env->env_clk[b] = static_cast<EnvClock*>(p_);
-    }
-    void* t = nullptr;
-    AO_HIP(hipMalloc(&t, n * sizeof(LayerTaps)));
-    env->allocs.push_back(t);
-    env->env_taps = static_cast<LayerTaps*>(t);
-    return 0;
+    for (int b = 0; b < 2; ++b) AO_TRY(dmalloc(env, (void**)&env->env_clk[b], n * sizeof(EnvClock), false));
+    return dmalloc(env, (void**)&env->env_taps, n * sizeof(LayerTaps), false);
 }
 
 // host copy of the clocks -> device (current buffer) + the taps they imply (no ring pending), and every layer's round count
@@ -1901,12 +1926,7 @@ int aoenv_set_r0_env(AoEnv* env, const double* h_r0, double r0_tables, void* str
         if (!(h_r0[e] > 0) || !std::isfinite(h_r0[e])) return fail("aoenv_set_r0_env: r0[%zu] = %g, must be positive and finite", e, h_r0[e]);
     std::vector<double> sg(E);
     for (size_t e = 0; e < E; ++e) sg[e] = std::pow(r0_tables / h_r0[e], 5.0 / 6);
-    if (!env->xi_scale) {
-        void* p_ = nullptr;
-        AO_HIP(hipMalloc(&p_, E * sizeof(double)));
-        env->allocs.push_back(p_);
-        env->xi_scale = static_cast<double*>(p_);
-    }
+    if (!env->xi_scale) AO_TRY(dmalloc(env, (void**)&env->xi_scale, E * sizeof(double), false));
     // ordered on the stream behind the launches that read the old factors (a deferred ring was computed from them and is scattered
     // as it is)
     AO_HIP(hipMemcpyAsync(env->xi_scale, sg.data(), E * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1940,23 +1960,12 @@ static int require_step_constants(AoEnv* env, bool atmosphere) {
 }
 
 namespace {
-// Scratch of one reset, released on every exit path.  The resets return with the kernels that read it still queued on the stream:
-// hipFree waits for the device before it releases a buffer, which is what keeps this safe (a stream-ordered or pooled free would not).
-struct TmpFree {
-    std::vector<void*> p;
-    ~TmpFree() { for (void* q : p) (void)hipFree(q); }
-    int get(void** out, size_t bytes) {
-        AO_HIP(hipMalloc(out, bytes));
-        p.push_back(*out);
-        return 0;
-    }
-};
-
 // host arrays of 32-bit words (an index list, seeds) back to back in one scratch buffer, in one upload
 int upload_words(TmpFree& tmp, std::initializer_list<std::pair<const void*, size_t>> parts, uint32_t** d_out) {
     std::vector<uint32_t> pack;
     for (const auto& p : parts) pack.insert(pack.end(), static_cast<const uint32_t*>(p.first), static_cast<const uint32_t*>(p.first) + p.second);
-    AO_TRY(tmp.get((void**)d_out, pack.size() * 4));
+    AO_TRY(tmp.get({pack.size() * 4}));
+    *d_out = tmp.part<uint32_t>(0);
     AO_HIP(hipMemcpy(*d_out, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
     return 0;
 }
@@ -2073,21 +2082,16 @@ int make_screen_gen(TmpFree& tmp, int N, int n_env, double r0, double L0, double
     sa.delta = pixel_size;
     const size_t per_env = 40 * N2;                                // normals + complex scratch + real screen, float64
     const int EC = g->ec = (int)std::min<size_t>((size_t)n_env, std::max<size_t>(1, ((size_t)1 << 30) / per_env));
-    double *d_amp = nullptr, *d_sub = nullptr, *d_tw = nullptr, *d_nrm = nullptr, *d_hi = nullptr;
-    void* d_scr = nullptr;
-    AO_TRY(tmp.get((void**)&d_amp, N2 * 8));
-    AO_TRY(tmp.get((void**)&d_sub, 36 * 8));
-    AO_TRY(tmp.get((void**)&d_tw, 2 * (size_t)N * 8));
-    AO_TRY(tmp.get((void**)&d_nrm, (size_t)EC * 2 * N2 * 8));
-    AO_TRY(tmp.get(&d_scr, (size_t)EC * N2 * 16));
-    AO_TRY(tmp.get((void**)&d_hi, (size_t)EC * N2 * 8));
-    AO_TRY(tmp.get((void**)&g->mt, (size_t)EC * kMtN * 4));
-    AO_TRY(tmp.get((void**)&g->pos, (size_t)EC * 4));
+    AO_TRY(tmp.get({N2 * 8, 36 * 8, 2 * (size_t)N * 8, (size_t)EC * 2 * N2 * 8, (size_t)EC * N2 * 16, (size_t)EC * N2 * 8, (size_t)EC * kMtN * 4,
+                    (size_t)EC * 4}));
+    double *d_amp = tmp.part<double>(0), *d_sub = tmp.part<double>(1), *d_tw = tmp.part<double>(2);
     AO_HIP(hipMemcpy(d_amp, amp.data(), N2 * 8, hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(d_sub, sub.data(), 36 * 8, hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
-    sa.amp = d_amp; sa.sub = d_sub; sa.tw = d_tw; sa.nrm = d_nrm; sa.hi = d_hi;
-    sa.scratch = reinterpret_cast<cx<double>*>(d_scr);
+    sa.amp = d_amp; sa.sub = d_sub; sa.tw = d_tw; sa.nrm = tmp.part<double>(3); sa.hi = tmp.part<double>(5);
+    sa.scratch = tmp.part<cx<double>>(4);
+    g->mt = tmp.part<uint32_t>(6);
+    g->pos = tmp.part<int>(7);
     return 0;
 }
 }  // namespace
@@ -2255,9 +2259,7 @@ int aoenv_reset_soft(AoEnv* env, void* d_obs, void* stream) {
     if (!d_obs) return fail("null obs");
     if (!env->have[AOENV_C_RECON]) return fail("the reconstructor has not been uploaded");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (env->c.dtype == AOENV_F32)
-        return run_recon<float>(env, nullptr, static_cast<float*>(d_obs), nullptr, nullptr, -1, 0, 0.0, st);
-    return run_recon<double>(env, nullptr, static_cast<double*>(d_obs), nullptr, nullptr, -1, 0, 0.0, st);
+    return AO_DISPATCH(env, reset_soft_t, env, d_obs, st);
 }
 
 int aoenv_step(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, void* d_reward, void* d_strehl,
@@ -2317,22 +2319,15 @@ int aoenv_set_noise_filter(AoEnv* env, const double* h_factors, int K, void* str
     const int A = env->A;
     if (K < 1 || K > A) return fail("aoenv_set_noise_filter: rank %d outside [1, A=%d]", K, A);
     const size_t n = (size_t)K * A;
-    for (size_t i = 0; i < 2 * n; ++i)
-        if (!std::isfinite(h_factors[i])) return fail("aoenv_set_noise_filter: entry %zu is not finite", i);
+    if (const size_t i = first_not_finite(h_factors, 2 * n); i < 2 * n) return fail("aoenv_set_noise_filter: entry %zu is not finite", i);
     AO_HIP(hipStreamSynchronize(st));                              // a rollout in flight reads the factors in place
     if (n > env->noise_cap) {
-        void *fr = nullptr, *fl = nullptr;
-        AO_TRY(dmalloc(env, &fr, n * env->esz, false));
-        AO_TRY(dmalloc(env, &fl, n * env->esz, false));
-        env->noise_fr = fr; env->noise_fl_t = fl; env->noise_cap = n;
+        AO_TRY(block_alloc(env->noise_mem, {n * env->esz, n * env->esz}, false));
+        env->noise_fr = env->noise_mem.part(0); env->noise_fl_t = env->noise_mem.part(1); env->noise_cap = n;
     }
-    std::vector<double> t(n);                                      // Fl [A][K] -> [K][A]
-    const double* fl = h_factors + n;
-    for (int a = 0; a < A; ++a)
-        for (int k = 0; k < K; ++k) t[(size_t)k * A + a] = fl[(size_t)a * K + k];
     env->noise_K = 0;                                              // (a failed copy leaves no half-written filter in use)
     AO_TRY(upload_real(env, env->noise_fr, h_factors, n));
-    AO_TRY(upload_real(env, env->noise_fl_t, t.data(), n));
+    AO_TRY(upload_transposed(env, env->noise_fl_t, h_factors + n, A, K));   // Fl [A][K] -> [K][A]
     env->noise_K = K;
     return 0;
 }
@@ -2349,31 +2344,22 @@ int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream) {
     if (J < 1 || J > kDisturbMaxLines) return fail("aoenv_set_disturbance: n_lines %d outside [1, %d]", J, kDisturbMaxLines);
     if (!cfg->h_modes || !cfg->h_amp || !cfg->h_freq || !cfg->h_phase) return fail("aoenv_set_disturbance: null modes / amp / freq / phase");
     const size_t nb = (size_t)A * M, np = (size_t)env->E * M * J;
-    for (size_t i = 0; i < nb; ++i)
-        if (!std::isfinite(cfg->h_modes[i])) return fail("aoenv_set_disturbance: modes[%zu] is not finite", i);
+    if (const size_t i = first_not_finite(cfg->h_modes, nb); i < nb) return fail("aoenv_set_disturbance: modes[%zu] is not finite", i);
     const struct { const double* p; const char* name; } arrays[] = {{cfg->h_amp, "amp"}, {cfg->h_freq, "freq"}, {cfg->h_phase, "phase"}};
     for (const auto& a : arrays)
-        for (size_t i = 0; i < np; ++i)
-            if (!std::isfinite(a.p[i])) return fail("aoenv_set_disturbance: %s[%zu] is not finite", a.name, i);
+        if (const size_t i = first_not_finite(a.p, np); i < np) return fail("aoenv_set_disturbance: %s[%zu] is not finite", a.name, i);
     for (size_t i = 0; i < np; ++i)
         if (cfg->h_amp[i] < 0) return fail("aoenv_set_disturbance: amp[%zu] is negative", i);
     AO_HIP(hipStreamSynchronize(st));                              // a loop in flight reads the tables in place
     AoEnv::Disturb& d = env->disturb;
-    if (nb > d.modes_cap) {
-        void* p = nullptr;
-        AO_TRY(dmalloc(env, &p, nb * env->esz, false));
-        d.modes_t = p; d.modes_cap = nb;
+    if (nb > d.modes_cap || np > d.par_cap) {                      // (neither table ever shrinks)
+        const size_t cb = std::max(nb, d.modes_cap), cp = std::max(np, d.par_cap);
+        AO_TRY(block_alloc(d.mem, {cb * env->esz, 3 * cp * sizeof(double)}, false));
+        d.modes_t = d.mem.part(0); d.modes_cap = cb;
+        d.par = static_cast<double*>(d.mem.part(1)); d.par_cap = cp;
     }
-    if (np > d.par_cap) {
-        void* p = nullptr;
-        AO_TRY(dmalloc(env, &p, 3 * np * sizeof(double), false));
-        d.par = static_cast<double*>(p); d.par_cap = np;
-    }
-    std::vector<double> t(nb);                                     // B [A][M] -> [M][A]
-    for (int a = 0; a < A; ++a)
-        for (int m = 0; m < M; ++m) t[(size_t)m * A + a] = cfg->h_modes[(size_t)a * M + m];
     d.set = false;                                                 // (a failed copy leaves no half-written disturbance in use)
-    AO_TRY(upload_real(env, d.modes_t, t.data(), nb));
+    AO_TRY(upload_transposed(env, d.modes_t, cfg->h_modes, A, M));  // B [A][M] -> [M][A]
     AO_HIP(hipMemcpy(d.par, cfg->h_amp, np * sizeof(double), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(d.par + np, cfg->h_freq, np * sizeof(double), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(d.par + 2 * np, cfg->h_phase, np * sizeof(double), hipMemcpyHostToDevice));
@@ -2389,26 +2375,20 @@ template <typename T>
 int set_dm_env_t(AoEnv* env, const double* h_gx, const double* h_gy, hipStream_t st) {
     const DmLayout dl = env->dm_layout();
     const size_t E = (size_t)env->E;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t bg = al(E * dl.g_elems() * sizeof(T)), bt = al(E * dl.gxt_elems() * sizeof(T)), ba = al(E * dl.ga_elems() * sizeof(float));
-    const size_t bytes = 2 * bg + bt + 2 * ba;
+    const size_t bg = E * dl.g_elems() * sizeof(T), bt = E * dl.gxt_elems() * sizeof(T), ba = E * dl.ga_elems() * sizeof(float);
+    const std::initializer_list<size_t> parts = {bg, bg, bt, ba, ba};
     DmHostTables<T> h;
     dm_relayout<T>(dl, env->E, h_gx, h_gy, h);
     AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the tables in place
     AoEnv::DmEnv& de = env->dm_env;
-    if (!de.base) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail("aoenv_set_dm_env: no device memory for %zu bytes of per-env DM tables (%d envs x %zu)", bytes, env->E, dl.bytes(sizeof(T)));
-        }
-        char* c = static_cast<char*>(p);
-        de.base = p;
-        de.gx = c;
-        de.gy = c + bg;
-        de.gxt = c + 2 * bg;
-        de.gxa = reinterpret_cast<float*>(c + 2 * bg + bt);
-        de.gya = reinterpret_cast<float*>(c + 2 * bg + bt + ba);
+    if (!de.mem) {
+        if (de.mem.alloc(parts, false))
+            return fail("aoenv_set_dm_env: no device memory for %zu bytes of per-env DM tables (%d envs x %zu)", dev_layout(parts).total, env->E, dl.bytes(sizeof(T)));
+        de.gx = de.mem.part(0);
+        de.gy = de.mem.part(1);
+        de.gxt = de.mem.part(2);
+        de.gxa = static_cast<float*>(de.mem.part(3));
+        de.gya = static_cast<float*>(de.mem.part(4));
     }
     de.on = false;                                                 // (a failed copy leaves no half-written mirror in use)
     AO_HIP(hipMemcpy(de.gx, h.gx.data(), h.gx.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -2417,17 +2397,6 @@ int set_dm_env_t(AoEnv* env, const double* h_gx, const double* h_gy, hipStream_t
     AO_HIP(hipMemcpy(de.gxa, h.gxa.data(), h.gxa.size() * sizeof(float), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(de.gya, h.gya.data(), h.gya.size() * sizeof(float), hipMemcpyHostToDevice));
     de.on = true;
-    return 0;
-}
-template <typename T>
-int get_dm_env_t(AoEnv* env, double* h_gx, double* h_gy) {
-    const size_t n = (size_t)env->E * env->dm_layout().g_elems();
-    std::vector<T> t(n);
-    const struct { const void* src; double* dst; } both[] = {{env->dm_env.gx, h_gx}, {env->dm_env.gy, h_gy}};
-    for (const auto& b : both) {
-        AO_HIP(hipMemcpy(t.data(), b.src, n * sizeof(T), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) b.dst[i] = (double)t[i];
-    }
     return 0;
 }
 }  // namespace
@@ -2439,19 +2408,15 @@ int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* s
     if (!h_gx != !h_gy) return fail("aoenv_set_dm_env: one of gx / gy is null (both, or neither for the shared tables)");
     if (h_gx && !env->c.dm_separable) return fail("aoenv_set_dm_env: this shard's DM is dense (dm_separable == 0): it has no factors");
     if (!h_gx) {
-        if (env->dm_env.base) {
-            AO_HIP(hipStreamSynchronize(st));
-            (void)hipFree(env->dm_env.base);                       // (waits for the device)
-        }
+        if (env->dm_env.mem) AO_HIP(hipStreamSynchronize(st));
         env->dm_env = AoEnv::DmEnv{};
         return 0;
     }
     const size_t n = (size_t)env->E * env->R * env->nAct;
-    for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(h_gx[i])) return fail("aoenv_set_dm_env: gx[%zu] is not finite", i);
-        if (!std::isfinite(h_gy[i])) return fail("aoenv_set_dm_env: gy[%zu] is not finite", i);
-    }
-    return env->c.dtype == AOENV_F32 ? set_dm_env_t<float>(env, h_gx, h_gy, st) : set_dm_env_t<double>(env, h_gx, h_gy, st);
+    const size_t ix = first_not_finite(h_gx, n), iy = first_not_finite(h_gy, n);   // (the lower index is reported, gx first)
+    if (ix < n && ix <= iy) return fail("aoenv_set_dm_env: gx[%zu] is not finite", ix);
+    if (iy < n) return fail("aoenv_set_dm_env: gy[%zu] is not finite", iy);
+    return AO_DISPATCH(env, set_dm_env_t, env, h_gx, h_gy, st);
 }
 
 int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
@@ -2459,44 +2424,32 @@ int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
     if (!h_gx || !h_gy) return fail("aoenv_get_dm_env: null destination");
     if (!env->dm_env.on) return fail("aoenv_get_dm_env: the shard shares one mirror (aoenv_set_dm_env has not been called)");
     AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return env->c.dtype == AOENV_F32 ? get_dm_env_t<float>(env, h_gx, h_gy) : get_dm_env_t<double>(env, h_gx, h_gy);
+    const size_t n = (size_t)env->E * env->dm_layout().g_elems();
+    AO_TRY(download_real(env, h_gx, env->dm_env.gx, n));
+    return download_real(env, h_gy, env->dm_env.gy, n);
 }
 
 // ---- per-env guide stars (star_env.hpp) ------------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
-// one [E] array of the env dtype in an allocation of its own: `h` (already validated) through `fill`, or freed when h is null
+// one [E] array of the env dtype in a block of its own: `h` (already validated) through `fill`, or freed when h is null
 template <typename T, typename Fill>
-int set_star_row_t(AoEnv* env, void** slot, const double* h, Fill fill, const char* who, hipStream_t st) {
+int set_star_row_t(AoEnv* env, Block& mem, void*& slot, const double* h, Fill fill, const char* who, hipStream_t st) {
     std::vector<T> t((size_t)env->E);
     fill(h, env->E, t.data());
     AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the array in place
-    void* p = *slot;
-    if (!p && hipMalloc(&p, t.size() * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("%s: no device memory for %d values", who, env->E);
-    }
-    if (hipMemcpy(p, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        if (!*slot) (void)hipFree(p);
+    Block fresh;
+    if (!mem && fresh.alloc({t.size() * sizeof(T)}, false)) return fail("%s: no device memory for %d values", who, env->E);
+    if ((mem ? mem : fresh).upload(0, t.data(), t.size() * sizeof(T)))
         return fail("%s: the copy to the device failed", who);     // (an array already held keeps being used: same size, same place)
-    }
-    *slot = p;
+    if (!mem) mem = std::move(fresh);
+    slot = mem.part(0);
     return 0;
 }
-int clear_star_row(void** slot, hipStream_t st) {
-    if (*slot) {
-        AO_HIP(hipStreamSynchronize(st));
-        (void)hipFree(*slot);
-        *slot = nullptr;
-    }
-    return 0;
-}
-template <typename T>
-int get_star_row_t(const AoEnv* env, const void* src, double* dst) {
-    std::vector<T> t((size_t)env->E);
-    AO_HIP(hipMemcpy(t.data(), src, t.size() * sizeof(T), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < t.size(); ++i) dst[i] = (double)t[i];
+int clear_star_row(Block& mem, void*& slot, hipStream_t st) {
+    if (mem) AO_HIP(hipStreamSynchronize(st));
+    mem.reset();
+    slot = nullptr;
     return 0;
 }
 }  // namespace
@@ -2505,11 +2458,12 @@ int get_star_row_t(const AoEnv* env, const void* src, double* dst) {
 int aoenv_set_flux_env(AoEnv* env, const double* h_scale, void* stream) {
     AO_CHECK_ENV(env);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h_scale) return clear_star_row(&env->star.amp, st);
+    AoEnv::StarDev& s = env->star;
+    if (!h_scale) return clear_star_row(s.amp_mem, s.amp, st);
     char msg[96];
     if (star_flux_check(h_scale, env->E, msg, sizeof msg)) return fail("aoenv_set_flux_env: %s", msg);
-    return env->c.dtype == AOENV_F32 ? set_star_row_t<float>(env, &env->star.amp, h_scale, star_amp_factors<float>, "aoenv_set_flux_env", st)
-                                     : set_star_row_t<double>(env, &env->star.amp, h_scale, star_amp_factors<double>, "aoenv_set_flux_env", st);
+    const auto fill = [](const double* h, int n, auto* out) { star_amp_factors(h, n, out); };
+    return AO_DISPATCH(env, set_star_row_t, env, s.amp_mem, s.amp, h_scale, fill, "aoenv_set_flux_env", st);
 }
 
 int aoenv_get_flux_env(AoEnv* env, double* h_amp, void* stream) {
@@ -2517,18 +2471,19 @@ int aoenv_get_flux_env(AoEnv* env, double* h_amp, void* stream) {
     if (!h_amp) return fail("aoenv_get_flux_env: null destination");
     if (!env->star.amp) return fail("aoenv_get_flux_env: the shard has one star (aoenv_set_flux_env has not been called)");
     AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return env->c.dtype == AOENV_F32 ? get_star_row_t<float>(env, env->star.amp, h_amp) : get_star_row_t<double>(env, env->star.amp, h_amp);
+    return download_real(env, h_amp, env->star.amp, (size_t)env->E);
 }
 
 int aoenv_set_threshold_env(AoEnv* env, const double* h_thr, void* stream) {
     AO_CHECK_ENV(env);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h_thr) return clear_star_row(&env->star.thr, st);
+    AoEnv::StarDev& s = env->star;
+    if (!h_thr) return clear_star_row(s.thr_mem, s.thr, st);
     if (const char* why = star_threshold_refusal(env->c.wfs_type == AOENV_WFS_PYRAMID, env->c.max_group)) return fail("aoenv_set_threshold_env: %s", why);
     char msg[96];
     if (star_threshold_check(h_thr, env->E, msg, sizeof msg)) return fail("aoenv_set_threshold_env: %s", msg);
-    return env->c.dtype == AOENV_F32 ? set_star_row_t<float>(env, &env->star.thr, h_thr, star_thresholds<float>, "aoenv_set_threshold_env", st)
-                                     : set_star_row_t<double>(env, &env->star.thr, h_thr, star_thresholds<double>, "aoenv_set_threshold_env", st);
+    const auto fill = [](const double* h, int n, auto* out) { star_thresholds(h, n, out); };
+    return AO_DISPATCH(env, set_star_row_t, env, s.thr_mem, s.thr, h_thr, fill, "aoenv_set_threshold_env", st);
 }
 
 int aoenv_get_threshold_env(AoEnv* env, double* h_thr, void* stream) {
@@ -2536,7 +2491,7 @@ int aoenv_get_threshold_env(AoEnv* env, double* h_thr, void* stream) {
     if (!h_thr) return fail("aoenv_get_threshold_env: null destination");
     if (!env->star.thr) return fail("aoenv_get_threshold_env: the shard has one threshold (aoenv_set_threshold_env has not been called)");
     AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return env->c.dtype == AOENV_F32 ? get_star_row_t<float>(env, env->star.thr, h_thr) : get_star_row_t<double>(env, env->star.thr, h_thr);
+    return download_real(env, h_thr, env->star.thr, (size_t)env->E);
 }
 
 // ---- the modal control surface (modal.hpp) ----------------------------------------------------------------------------------------
@@ -2546,7 +2501,6 @@ int aoenv_set_modal(AoEnv* env, const AoModal* cfg, void* stream) {
     AoEnv::Modal& mo = env->modal;
     if (!cfg) {
         AO_HIP(hipStreamSynchronize(st));                          // a step in flight reads the tables in place
-        if (mo.base) (void)hipFree(mo.base);
         mo = AoEnv::Modal{};
         return 0;
     }
@@ -2554,32 +2508,18 @@ int aoenv_set_modal(AoEnv* env, const AoModal* cfg, void* stream) {
     if (K < 1 || K > A) return fail("aoenv_set_modal: n_modes %d outside [1, A=%d]", K, A);
     if (!cfg->h_m2c || !cfg->h_cm) return fail("aoenv_set_modal: null m2c / cm");
     const size_t nm = (size_t)A * K, nc = (size_t)K * env->nSig, E = (size_t)env->E, img = (size_t)env->nAct * env->nAct;
-    for (size_t i = 0; i < nm; ++i)
-        if (!std::isfinite(cfg->h_m2c[i])) return fail("aoenv_set_modal: m2c[%zu] is not finite", i);
-    for (size_t i = 0; i < nc; ++i)
-        if (!std::isfinite(cfg->h_cm[i])) return fail("aoenv_set_modal: cm[%zu] is not finite", i);
+    if (const size_t i = first_not_finite(cfg->h_m2c, nm); i < nm) return fail("aoenv_set_modal: m2c[%zu] is not finite", i);
+    if (const size_t i = first_not_finite(cfg->h_cm, nc); i < nc) return fail("aoenv_set_modal: cm[%zu] is not finite", i);
     const size_t z = env->esz, n_slab = (z == 4 ? (size_t)kMaxSplits : 1) * E * K;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t part[] = {al(nm * z), al(nc * z), al(E * K * z), al(E * img * z), al(E * img * z), al(2 * E * z), al(n_slab * z)};
-    size_t bytes = 0;
-    for (size_t b : part) bytes += b;
+    const std::initializer_list<size_t> parts = {nm * z, nc * z, E * K * z, E * img * z, E * img * z, 2 * E * z, n_slab * z};
     AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the tables in place
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("aoenv_set_modal: no device memory for %zu bytes of modal tables and scratch", bytes);
-    }
-    if (mo.base) (void)hipFree(mo.base);
-    mo = AoEnv::Modal{};
-    mo.base = p;
+    Block mem;                                                     // zeroed whole
+    if (mem.alloc(parts, true)) return fail("aoenv_set_modal: no device memory for %zu bytes of modal tables and scratch", dev_layout(parts).total);
+    mo = AoEnv::Modal{};                                           // (frees the basis held so far)
+    mo.mem = std::move(mem);
     void** field[] = {&mo.m2c_t, &mo.cm, &mo.gain, &mo.image, &mo.zobs, &mo.zscal, &mo.slabs};
-    char* c = static_cast<char*>(p);
-    for (int k = 0; k < 7; ++k) { *field[k] = c; c += part[k]; }
-    AO_HIP(hipMemset(p, 0, bytes));
-    std::vector<double> t(nm);                                     // M2C [A][K] -> [K][A]
-    for (int a = 0; a < A; ++a)
-        for (int m = 0; m < K; ++m) t[(size_t)m * A + a] = cfg->h_m2c[(size_t)a * K + m];
-    AO_TRY(upload_real(env, mo.m2c_t, t.data(), nm));
+    for (int k = 0; k < 7; ++k) *field[k] = mo.mem.part(k);
+    AO_TRY(upload_transposed(env, mo.m2c_t, cfg->h_m2c, A, K));    // M2C [A][K] -> [K][A]
     AO_TRY(upload_real(env, mo.cm, cfg->h_cm, nc));
     mo.K = K;
     mo.set = true;
@@ -2662,24 +2602,18 @@ static int wf_set_basis(AoEnv* env, const AoWavefrontBasis* cfg, hipStream_t st)
     const int K = cfg->n_modes;
     const WfPlan pl = wf_plan(R2, K);
     const size_t ld = (size_t)wf_row_stride(R2), np = (size_t)K * ld, ns = (size_t)std::max(pl.n_slices, kWfSlabsAtLeast) * 2 * env->E * K;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const std::initializer_list<size_t> parts = {np * sizeof(T), ns * sizeof(T)};
     std::vector<T> table(np);
     wf_scatter<T>(cfg->h_opd2m, K, cfg->n_pix, env->h_pupil.data(), R2, table.data());
     AO_HIP(hipStreamSynchronize(st));                              // a projection in flight reads the table in place
-    void* p = nullptr;
-    if (hipMalloc(&p, al(np * sizeof(T)) + al(ns * sizeof(T))) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("aoenv_set_wavefront_basis: no device memory for %zu bytes of projector and slabs", al(np * sizeof(T)) + al(ns * sizeof(T)));
-    }
-    if (hipMemcpy(p, table.data(), np * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return fail("aoenv_set_wavefront_basis: the copy of the projector failed");
-    }
-    wf_forget(env);                                                // (a new basis detaches the record of the previous one)
+    Block mem;                                                     // (built whole before the basis in use is given up)
+    if (mem.alloc(parts, false)) return fail("aoenv_set_wavefront_basis: no device memory for %zu bytes of projector and slabs", dev_layout(parts).total);
+    if (mem.upload(0, table.data(), np * sizeof(T))) return fail("aoenv_set_wavefront_basis: the copy of the projector failed");
     AoEnv::Wavefront& wf = env->wf;
-    wf.base = wf.p = p;
-    wf.slabs = static_cast<char*>(p) + al(np * sizeof(T));
+    wf = AoEnv::Wavefront{};                                       // (a new basis detaches the record of the previous one)
+    wf.mem = std::move(mem);
+    wf.p = wf.mem.part(0);
+    wf.slabs = wf.mem.part(1);
     wf.K = K;
     wf.plan = pl;
     wf.set = true;
@@ -2692,10 +2626,10 @@ int aoenv_set_wavefront_basis(AoEnv* env, const AoWavefrontBasis* cfg, void* str
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!cfg) {
         AO_HIP(hipStreamSynchronize(st));
-        wf_forget(env);
+        env->wf = AoEnv::Wavefront{};
         return 0;
     }
-    return env->c.dtype == AOENV_F32 ? wf_set_basis<float>(env, cfg, st) : wf_set_basis<double>(env, cfg, st);
+    return AO_DISPATCH(env, wf_set_basis, env, cfg, st);
 }
 
 static int wf_one_or_two_bits(int what) { return what != 0 && (what & ~(AOENV_WF_RESIDUAL | AOENV_WF_ATMOSPHERE)) == 0; }
@@ -2756,28 +2690,22 @@ static int sci_set(AoEnv* env, const AoScience* cfg, hipStream_t st) {
     const SciGeom g = sci_geom(R, cfg->zero_padding, cfg->window);
     const SciPlan pl = sci_plan(R, cfg->window);
     const size_t nt = sci_table_elems(pl);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    std::vector<T> host(al(nt * sizeof(T)) / sizeof(T) + R2);
-    sci_fill_table<T>(g, pl, cfg->h_dft, host.data());
+    const std::initializer_list<size_t> parts = {nt * sizeof(T), R2 * sizeof(T)};
+    std::vector<T> table(nt), amp(R2);
+    sci_fill_table<T>(g, pl, cfg->h_dft, table.data());
     // the amplitude of aoenv_compute_psf: pupil * sqrt(src.fluxMap), all modulation points of a Pyramid together
     const double scale = env->c.wfs_type == AOENV_WFS_PYRAMID ? std::sqrt((double)env->c.pyr_n_theta) : 1.0;
-    T* amp = host.data() + al(nt * sizeof(T)) / sizeof(T);
     for (size_t q = 0; q < R2; ++q) amp[q] = (T)(env->h_amp[q] * scale);
     AO_HIP(hipStreamSynchronize(st));                              // a window in flight reads the table in place
-    void* p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("aoenv_set_science: no device memory for %zu bytes of table and amplitude", host.size() * sizeof(T));
-    }
-    if (hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
+    Block mem;                                                     // (built whole before the configuration in use is given up)
+    if (mem.alloc(parts, false)) return fail("aoenv_set_science: no device memory for %zu bytes of table and amplitude", dev_layout(parts).total);
+    if (mem.upload(0, table.data(), nt * sizeof(T)) || mem.upload(1, amp.data(), R2 * sizeof(T)))
         return fail("aoenv_set_science: the copy of the table failed");
-    }
-    sci_forget(env);                                               // (a new configuration detaches the accumulators of the previous one)
     AoEnv::Science& sc = env->sci;
-    sc.base = sc.table = p;
-    sc.amp = static_cast<char*>(p) + al(nt * sizeof(T));
+    sc = AoEnv::Science{};                                         // (a new configuration detaches the accumulators of the previous one)
+    sc.mem = std::move(mem);
+    sc.table = sc.mem.part(0);
+    sc.amp = sc.mem.part(1);
     sc.g = g;
     sc.first_frame = cfg->first_frame;
     sc.flags = cfg->flags;
@@ -2791,10 +2719,10 @@ int aoenv_set_science(AoEnv* env, const AoScience* cfg, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!cfg) {
         AO_HIP(hipStreamSynchronize(st));
-        sci_forget(env);
+        env->sci = AoEnv::Science{};
         return 0;
     }
-    return env->c.dtype == AOENV_F32 ? sci_set<float>(env, cfg, st) : sci_set<double>(env, cfg, st);
+    return AO_DISPATCH(env, sci_set, env, cfg, st);
 }
 
 int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream) {
@@ -2967,22 +2895,12 @@ int aoenv_run_rollout(AoEnv* env, const AoRollout* cfg, void* d_obs, void* d_act
 }
 
 // ---- the policy (policy.hpp) ---------------------------------------------------------------------------------------------------
-static void dfree(AoEnv* env, void* p) {
-    if (!p) return;
-    env->allocs.erase(std::remove(env->allocs.begin(), env->allocs.end(), p), env->allocs.end());
-    (void)hipFree(p);                                              // (waits for the device)
-}
-static void policy_release(AoEnv* env, AoEnv::Policy& p) {
-    for (void* q : {p.w1, p.b1, p.w2, p.b2, p.w3, p.wt1, p.wt2, p.proj_fr, p.proj_fl_t, p.hid1, p.hid2}) dfree(env, q);
-    p = AoEnv::Policy{};
-}
-
 int aoenv_set_policy(AoEnv* env, const AoPolicy* cfg, void* stream) {
     AO_CHECK_ENV(env);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!cfg) {
         AO_HIP(hipStreamSynchronize(st));
-        policy_release(env, env->policy);
+        env->policy = AoEnv::Policy{};
         return 0;
     }
     const int H = cfg->n_history, F = cfg->n_filt, Kp = cfg->proj_rank, A = env->A;
@@ -3000,48 +2918,36 @@ int aoenv_set_policy(AoEnv* env, const AoPolicy* cfg, void* stream) {
         {cfg->h_w1, n1, "w1"}, {cfg->h_b1, (size_t)F, "b1"}, {cfg->h_w2, n2, "w2"}, {cfg->h_b2, (size_t)F, "b2"},
         {cfg->h_w3, n3, "w3"}, {cfg->h_b3, 1, "b3"}, {cfg->h_proj, 2 * np, "proj"}};
     for (const auto& a : arrays)
-        for (size_t i = 0; i < a.n; ++i)
-            if (!std::isfinite(a.p[i])) return fail("aoenv_set_policy: %s[%zu] is not finite", a.name, i);
+        if (const size_t i = first_not_finite(a.p, a.n); i < a.n) return fail("aoenv_set_policy: %s[%zu] is not finite", a.name, i);
     AO_HIP(hipStreamSynchronize(st));                              // an evaluation in flight reads the old policy in place
-    AoEnv::Policy p;
+    AoEnv::Policy p;                                               // (a failed build frees it on return: the policy in use stays)
     p.H = H; p.F = F; p.Kp = Kp;
     p.slope = cfg->negative_slope; p.clamp_abs = cfg->clamp_abs; p.b3 = cfg->h_b3[0];
     p.mfma = policy_uses_mfma(env->esz, cfg->path, F, env->nAct, C1);
     const size_t z = env->esz, hid = (size_t)env->E * F * env->nAct * env->nAct * z;
-    auto build = [&]() -> int {
-        AO_TRY(dmalloc(env, &p.w1, n1 * z, false)); AO_TRY(upload_real(env, p.w1, cfg->h_w1, n1));
-        AO_TRY(dmalloc(env, &p.b1, F * z, false));  AO_TRY(upload_real(env, p.b1, cfg->h_b1, F));
-        AO_TRY(dmalloc(env, &p.w2, n2 * z, false)); AO_TRY(upload_real(env, p.w2, cfg->h_w2, n2));
-        AO_TRY(dmalloc(env, &p.b2, F * z, false));  AO_TRY(upload_real(env, p.b2, cfg->h_b2, F));
-        AO_TRY(dmalloc(env, &p.w3, n3 * z, false)); AO_TRY(upload_real(env, p.w3, cfg->h_w3, n3));
-        if (p.mfma) {
-            std::vector<float> t;
-            policy_relayout(cfg->h_w1, F, C1, t);
-            AO_TRY(dmalloc(env, &p.wt1, t.size() * 4, false));
-            AO_HIP(hipMemcpy(p.wt1, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-            policy_relayout(cfg->h_w2, F, F, t);
-            AO_TRY(dmalloc(env, &p.wt2, t.size() * 4, false));
-            AO_HIP(hipMemcpy(p.wt2, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-        }
-        if (Kp > 0) {
-            std::vector<double> t(np);                             // Fl [A][K] -> [K][A], as aoenv_set_noise_filter
-            const double* fl = cfg->h_proj + np;
-            for (int a = 0; a < A; ++a)
-                for (int k = 0; k < Kp; ++k) t[(size_t)k * A + a] = fl[(size_t)a * Kp + k];
-            AO_TRY(dmalloc(env, &p.proj_fr, np * z, false));   AO_TRY(upload_real(env, p.proj_fr, cfg->h_proj, np));
-            AO_TRY(dmalloc(env, &p.proj_fl_t, np * z, false)); AO_TRY(upload_real(env, p.proj_fl_t, t.data(), np));
-        }
-        AO_TRY(dmalloc(env, &p.hid1, hid, false));
-        AO_TRY(dmalloc(env, &p.hid2, hid, false));
-        return 0;
-    };
-    if (int rc = build()) {                                        // (out of memory: the policy in use stays)
-        policy_release(env, p);
-        return rc;
+    std::vector<float> t1, t2;                                     // the wide layers re-laid; absent off the MFMA path
+    if (p.mfma) {
+        policy_relayout(cfg->h_w1, F, C1, t1);
+        policy_relayout(cfg->h_w2, F, F, t2);
+    }
+    AO_TRY(block_alloc(p.mem, {n1 * z, F * z, n2 * z, F * z, n3 * z, t1.size() * 4, t2.size() * 4, np * z, np * z, hid, hid}, false));
+    void** field[] = {&p.w1, &p.b1, &p.w2, &p.b2, &p.w3, &p.wt1, &p.wt2, &p.proj_fr, &p.proj_fl_t, &p.hid1, &p.hid2};
+    for (int k = 0; k < 11; ++k) *field[k] = p.mem.part(k);
+    AO_TRY(upload_real(env, p.w1, cfg->h_w1, n1));
+    AO_TRY(upload_real(env, p.b1, cfg->h_b1, F));
+    AO_TRY(upload_real(env, p.w2, cfg->h_w2, n2));
+    AO_TRY(upload_real(env, p.b2, cfg->h_b2, F));
+    AO_TRY(upload_real(env, p.w3, cfg->h_w3, n3));
+    if (p.mfma) {
+        AO_HIP(hipMemcpy(p.wt1, t1.data(), t1.size() * 4, hipMemcpyHostToDevice));
+        AO_HIP(hipMemcpy(p.wt2, t2.data(), t2.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (Kp > 0) {
+        AO_TRY(upload_real(env, p.proj_fr, cfg->h_proj, np));
+        AO_TRY(upload_transposed(env, p.proj_fl_t, cfg->h_proj + np, A, Kp));   // Fl [A][K] -> [K][A], as aoenv_set_noise_filter
     }
     p.set = true;
-    policy_release(env, env->policy);
-    env->policy = p;
+    env->policy = std::move(p);
     return 0;
 }
 
@@ -3177,9 +3083,9 @@ static int compute_psf_odd_t(AoEnv* env, int zp, void* d_psf, hipStream_t st) {
     sci_fill_table<T>(g, pl, nullptr, host.data());
     const double scale = env->c.wfs_type == AOENV_WFS_PYRAMID ? std::sqrt((double)env->c.pyr_n_theta) : 1.0;
     for (size_t q = 0; q < R2; ++q) host[nt + q] = (T)(env->h_amp[q] * scale);
-    TmpFree tmp;
-    T* d_tab;
-    AO_TRY(tmp.get((void**)&d_tab, host.size() * sizeof(T)));
+    Block tmp;
+    AO_TRY(block_alloc(tmp, {host.size() * sizeof(T)}, false));
+    T* d_tab = static_cast<T*>(tmp.part(0));
     AO_HIP(hipMemcpyAsync(d_tab, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st));
     SciArgs<T> a{};
     a.phase = env->as<T>(env->phase);
@@ -3203,12 +3109,10 @@ static int compute_psf_t(AoEnv* env, int zp, void* d_psf, hipStream_t st) {
     const size_t R2 = (size_t)R * R;
     // scratch of one call: amplitude pupil * sqrt(src.fluxMap) (= the SH field amplitude; the Pyramid's is per modulation
     // point), twiddles, first-pass output
-    TmpFree tmp;
-    T *d_amp, *d_tw;
-    void* d_t1;
-    AO_TRY(tmp.get((void**)&d_amp, R2 * sizeof(T)));
-    AO_TRY(tmp.get((void**)&d_tw, (size_t)2 * N * sizeof(T)));
-    AO_TRY(tmp.get(&d_t1, (size_t)env->E * R * N * 2 * sizeof(T)));
+    Block tmp;
+    AO_TRY(block_alloc(tmp, {R2 * sizeof(T), (size_t)2 * N * sizeof(T), (size_t)env->E * R * N * 2 * sizeof(T)}, false));
+    T *d_amp = static_cast<T*>(tmp.part(0)), *d_tw = static_cast<T*>(tmp.part(1));
+    void* d_t1 = tmp.part(2);
     if (env->h_amp.size() != R2) return fail("the WFS amplitude has not been uploaded");
     const double scale = env->c.wfs_type == AOENV_WFS_PYRAMID ? std::sqrt((double)env->c.pyr_n_theta) : 1.0;
     std::vector<T> amp(R2), tw(2 * (size_t)N);
@@ -3242,8 +3146,7 @@ int aoenv_compute_psf(AoEnv* env, int zero_padding, void* d_psf, void* stream) {
     if ((zero_padding * env->R) % 2) return fail("odd image sizes are not built");
     if (2 * zero_padding * env->R > 8192) return fail("PSF transform length %d too long", 2 * zero_padding * env->R);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return env->c.dtype == AOENV_F32 ? compute_psf_t<float>(env, zero_padding, d_psf, st)
-                                     : compute_psf_t<double>(env, zero_padding, d_psf, st);
+    return AO_DISPATCH(env, compute_psf_t, env, zero_padding, d_psf, st);
 }
 
 int aoenv_set_detector(AoEnv* env, const AoDetector* cfg, void* stream) {
@@ -3499,19 +3402,18 @@ int aoenv_test_normal(int device, uint32_t seed, int n, int n_calls, double* h_o
     if (n < 2 || n % 2 || n_calls < 1 || !h_out) return fail("aoenv_test_normal: bad arguments");
     DeviceGuard ao_device_guard(device);
     if (!ao_device_guard.ok) return fail("hipSetDevice(%d) failed", device);
-    uint32_t* st = nullptr; int* pos = nullptr; double* zx = nullptr;
-    uint32_t* d_seed = nullptr;
-    AO_HIP(hipMalloc((void**)&st, kMtN * 4));
-    AO_HIP(hipMalloc((void**)&pos, 4));
-    AO_HIP(hipMalloc((void**)&zx, (size_t)n * 8));
-    AO_HIP(hipMalloc((void**)&d_seed, 4));
+    Block mem;                                                     // state, position, one call's draws, the seed
+    AO_TRY(block_alloc(mem, {kMtN * 4, 4, (size_t)n * 8, 4}, false));
+    uint32_t* st = static_cast<uint32_t*>(mem.part(0));
+    int* pos = static_cast<int*>(mem.part(1));
+    double* zx = static_cast<double*>(mem.part(2));
+    uint32_t* d_seed = static_cast<uint32_t*>(mem.part(3));
     AO_HIP(hipMemcpy(d_seed, &seed, 4, hipMemcpyHostToDevice));
     int rc = launch_mt_seed(d_seed, 1, nullptr, st, pos, 1, nullptr);                  // RandomState(seed)
     for (int c = 0; c < n_calls && !rc; ++c) {
         rc = launch_mt_normal<double>(st, pos, zx, 1, n, 0, n, nullptr, nullptr);
         if (!rc && hipMemcpy(h_out + (size_t)c * n, zx, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = fail("copy back failed");
     }
-    (void)hipFree(st); (void)hipFree(pos); (void)hipFree(zx); (void)hipFree(d_seed);
     return rc;
 }
 
