@@ -706,6 +706,12 @@ enum AoOption {
                                  whole-pixel ring rounds per layer in front of the sub-pixel one.  Other values are rejected, and so is
                                  lowering n to or below a ratio the shard's clocks hold, with nothing changed.  Raising it costs a shard
                                  whose winds stay below one pixel per frame nothing: the same launches */
+    AOENV_OPT_STEP_PAIRS = 11, /* 1 (default): aoenv_run_integrator without a delay, float32 fused step, shared clock, a specialised
+                                 instantiation of the step kernel whose camera gives whole-number pixels (photon noise alone, or any camera with an ADC; not the
+                                 ideal detector, nor read-out noise, gain or quantum efficiency without an ADC), and no disturbance, wavefront record, long exposure, atmosphere
+                                 store or modal loop: a step takes the step behind it along in its launch where no layer makes a
+                                 whole-pixel round or crosses a pixel in that one (two steps, one workgroup per env, nothing read back
+                                 from global memory in between; bit-identical results).  0: one launch per step */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
                                  other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL and AOENV_PATH_SCI_GENERAL also keeps the shard off the fused step
                                  kernel; other bits are rejected */
@@ -742,7 +748,10 @@ int aoenv_fused_step_active(AoEnv* env);
 /* Per-kernel timing (bench.py roofline leg).  While enabled, every kernel launch of aoenv_step /
  * aoenv_measure is bracketed by a hipEvent pair recorded on the launch stream; aoenv_profile_read
  * synchronises the stream and returns the summed elapsed milliseconds and the launch count of each
- * AoKernel.  aoenv_profile(env, 0|1) also clears the recorded events. */
+ * AoKernel.  aoenv_profile(env, 0|1) also clears the recorded events.
+ * AOENV_K_ENV_STEP counts the steps covered, not the launches: a launch of two steps (AOENV_OPT_STEP_PAIRS) counts two, its
+ * elapsed time once.  aoenv_step_counters: h_out[0] = launches of the fused step kernel, h_out[1] = steps they covered, since the
+ * last aoenv_profile(env, 1) (or the shard's creation); counted whether or not the timing is enabled. */
 enum AoKernel {
     AOENV_K_SHIFT_GATHER = 0, AOENV_K_MT_NORMAL, AOENV_K_GEMM_RING, AOENV_K_SCATTER, AOENV_K_PHASE,
     AOENV_K_SH_SPOTS, AOENV_K_SH_CENTROID, AOENV_K_GEMM_RECON, AOENV_K_RECON_FINISH, AOENV_K_PYRAMID, AOENV_K_SH_TAIL, AOENV_K_ENV_STEP,
@@ -750,6 +759,7 @@ enum AoKernel {
 };
 int aoenv_profile(AoEnv* env, int enable);
 int aoenv_profile_read(AoEnv* env, double* h_ms, int32_t* h_count, void* stream);
+int aoenv_step_counters(AoEnv* env, int64_t* h_out);
 
 /* Test hook: draw `n` (even) values of RandomState(seed).normal(size=n) with the device MT19937 +
  * legacy polar generator into h_out (float64), to pin the stream against NumPy. */

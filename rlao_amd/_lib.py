@@ -21,7 +21,7 @@ WFS_SH, WFS_PYRAMID = 0, 1
 
 
 (OPT_FAST_WFS, OPT_MFMA_GEMM, OPT_FAST_TRIG, OPT_STORE_ATM_OPD, OPT_FUSED_TAIL, OPT_FUSED_STEP, OPT_DEFER_RING, OPT_COEFS_IMAGE,
- OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD, OPT_ENV_WIND_PIXELS) = range(11)
+ OPT_FACTORED_RECON, OPT_RING_LOOKAHEAD, OPT_ENV_WIND_PIXELS, OPT_STEP_PAIRS) = range(12)
 OPT_FORCE_PATH = 99
 MAX_DELAY = 8                                                      # AOENV_MAX_DELAY
 # enum AoPath: bits of OPT_FORCE_PATH
@@ -149,6 +149,7 @@ EXPORTS = {
     "aoenv_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "aoenv_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "aoenv_profile_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_step_counters": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_test_normal": (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "aoenv_test_poisson_table": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aoenv_test_poisson": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p]),
@@ -176,6 +177,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in EXPORTS.items():
+        if name == "aoenv_step_counters" and os.environ.get("AOENV_LIB") and not hasattr(lib, name):
+            continue                       # an A/B run of a library built before the counters (AOENV_LIB): same ABI without them
         fn = getattr(lib, name)            # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

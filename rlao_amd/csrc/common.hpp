@@ -99,6 +99,27 @@ __host__ __device__ inline int clock_rounds(const double ratio[2], int j, int* s
     return mx;
 }
 
+// Whether a launch of the fused step may take the step behind it along (k_env_step_pair_sh6): step k of a call of n_steps, whose
+// layers' clocks stand at (ratio[l], buff[l]) BEFORE step k.  `eligible` is everything that does not depend on the clocks (the
+// caller: aoenv_run_integrator without a delay, the float32 fused path with a shared clock and a specialised instantiation, no
+// disturbance, record, long exposure, atmosphere store or modal loop).  Step k itself may cross a pixel; step k + 1 must lie in the
+// call, and in it no layer may make a whole-pixel round or cross a pixel.  buff2[l] receives the accumulators after step k + 1:
+// what the taps of the second step are made from (taps_from_buff).
+__host__ inline bool plan_step_pair(bool eligible, int k, int n_steps, int n_layer, const double (*ratio)[2], const double (*buff)[2],
+                                    double (*buff2)[2]) {
+    if (!eligible || k < 0 || k + 1 >= n_steps) return false;
+    for (int l = 0; l < n_layer; ++l) {
+        int bx, by;
+        buff2[l][0] = buff[l][0];
+        buff2[l][1] = buff[l][1];
+        if (ratio[l][0] == 0 && ratio[l][1] == 0) continue;      // (a calm layer: advance_atmosphere leaves its clock alone)
+        if (clock_rounds(ratio[l], 0, &bx, &by) > 0) return false;   // a whole-pixel round in every step
+        clock_subpixel(ratio[l], buff2[l], &bx, &by);              // step k: crossing or not
+        if (clock_subpixel(ratio[l], buff2[l], &bx, &by)) return false;
+    }
+    return true;
+}
+
 // the torus origin (oy, ox) after the first j rounds of a step, in closed form: axis d has moved in min(j, floor |r_d|) of them
 __host__ __device__ inline void clock_rounds_origin(const double ratio[2], int j, int S, int org[2]) {
 #pragma clang fp contract(off)
@@ -358,11 +379,18 @@ struct StepArgs {
     const int* inner_idx;        // [n_inner]
     int n_inner, zx_ld;
     int n_modes, n_subap, n_valid, n_env;
+    // a launch of two steps (launch_env_step_pair): the taps of the second one, a step in which no layer crosses a pixel -- made by
+    // the host from a copy of the clocks (clock_subpixel, taps_from_buff), origin and weight as in k.pa.taps.  Last in the block:
+    // the launches of one step never read it.
+    LayerTaps taps2[kMaxLayer];
 };
 int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes);
 int step_alias_capacity(int n_act);
 // star: the per-env amplitude factors and thresholds; with either set the launch runs the STEP_STAR instantiation
 int launch_env_step(const StepArgs& a, const StarEnv<float>& star, hipStream_t st);
+// whether launch_env_step(a, star) would run a specialised instantiation, the ones that exist as a pair; and the pair itself
+bool env_step_pairable(const StepArgs& a, const StarEnv<float>& star);
+int launch_env_step_pair(const StepArgs& a, hipStream_t st);
 
 // exploration action of aoenv_run_rollout (rollout_kernels.hip): action = gain * obs + sigma_e vec_to_img(Fl (Fr z)), z from explore.hpp
 template <typename T>

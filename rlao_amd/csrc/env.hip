@@ -294,8 +294,12 @@ struct AoEnv {
     bool store_opd_atm = false;             // aoenv_set_option(AOENV_OPT_STORE_ATM_OPD): write atm.OPD every step
     bool atm_user_defined = false;          // aoenv_set_atm_opd() until the next step / new screens
     int force_path = 0;                     // aoenv_set_option(AOENV_OPT_FORCE_PATH): AoPath bits
+    bool use_step_pairs = true;             // aoenv_set_option(AOENV_OPT_STEP_PAIRS): aoenv_run_integrator takes a quiet step along in the launch before it
+    // set by aoenv_run_integrator around a step (plan_step_pair): this launch covers the step behind it too, whose clocks stand at buff2
+    struct StepPair { bool on = false; double buff2[kMaxLayer][2] = {}; } pair;
+    int64_t step_launches = 0, step_covered = 0;   // fused-step launches and the steps they covered, since aoenv_profile(env, 1)
     bool prof_on = false;
-    struct ProfEv { int stage; hipEvent_t a, b; };
+    struct ProfEv { int stage; hipEvent_t a, b; int n; };   // n: what the stage counts for the event (env_step: steps covered)
     std::vector<ProfEv> prof_ev;
 
     template <typename T> T* as(void* p_) const { return static_cast<T*>(p_); }
@@ -341,7 +345,7 @@ struct TmpFree {
 // Wraps one kernel launch in a hipEvent pair when profiling is enabled (events are recorded on the same
 // stream as the kernel, so the elapsed time is that kernel's device time plus its launch gap).
 struct ProfScope {
-    AoEnv* env; hipStream_t st; hipEvent_t a = nullptr, b = nullptr; int stage;
+    AoEnv* env; hipStream_t st; hipEvent_t a = nullptr, b = nullptr; int stage; int n = 1;
     ProfScope(AoEnv* e, int stage_, hipStream_t s) : env(e), st(s), stage(stage_) {
         if (!env->prof_on) return;
         if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
@@ -350,10 +354,14 @@ struct ProfScope {
     ~ProfScope() {
         if (!a) return;
         (void)hipEventRecord(b, st);
-        env->prof_ev.push_back({stage, a, b});
+        env->prof_ev.push_back({stage, a, b, n});
     }
 };
 #define AO_PROF(env, stage, st) ProfScope prof_scope_##stage(env, AOENV_K_##stage, st)
+// ... of a launch that counts `count` times in its stage (env_step: the steps it covers)
+#define AO_PROF_N(env, stage, st, count)                      \
+    ProfScope prof_scope_##stage(env, AOENV_K_##stage, st); \
+    prof_scope_##stage.n = (count)
 
 template <typename T>
 int upload_f64(void* dst, const double* src, size_t n) {
@@ -992,12 +1000,42 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.n_subap = env->nSub;
     a.n_valid = env->nVal;
     a.n_env = env->E;
-    {
-        AO_PROF(env, ENV_STEP, st);
-        AO_TRY(launch_env_step(a, env->star_env<float>(), st));
+    const bool pair = env->pair.on;                                // (aoenv_run_integrator: the quiet step behind this one in the same launch)
+    if (pair) {
+        for (int l = 0; l < env->L; ++l) {
+            a.taps2[l] = a.k.pa.taps[l];                           // origin and weight stand: nothing crosses
+            taps_from_buff(env->pair.buff2[l], a.taps2[l]);
+        }
     }
+    {
+        AO_PROF_N(env, ENV_STEP, st, pair ? 2 : 1);
+        AO_TRY(pair ? launch_env_step_pair(a, st) : launch_env_step(a, env->star_env<float>(), st));
+    }
+    env->step_launches += 1;
+    env->step_covered += pair ? 2 : 1;
     rings_written(env);
+    if (pair) {                                                    // the covered step: the host clock and the noise streams follow
+        for (int l = 0; l < env->L; ++l) {
+            LayerClock& c = env->layer[l].clk;
+            if (c.ratio[0] == 0 && c.ratio[1] == 0) continue;
+            int bx, by;
+            if (clock_rounds(c.ratio, 0, &bx, &by) > 0 || clock_subpixel(c.ratio, c.buff, &bx, &by))
+                return fail("internal: a step covered by the launch before it crossed a pixel");
+        }
+        if (env->det.active) env->det.frame_counter += 1;
+    }
     return 0;
+}
+
+// what plan_step_pair calls eligible, as far as it is the same for every step of a call of aoenv_run_integrator (delay.d == 0 and
+// the long exposure's window are the caller's)
+bool step_pair_eligible(AoEnv* env) {
+    if (!env->use_step_pairs || env->esz != 4 || !fused_step_ok<float>(env) || env->per_env_wind) return false;
+    if (env->disturb.set || env->wf.recorded() || env->store_opd_atm) return false;
+    StepArgs a{};                                                  // what the choice of the instantiation reads
+    a.sc = sh_const<float>(env);
+    a.det = env->det;
+    return env_step_pairable(a, env->star_env<float>());
 }
 
 // the measurement of frame i under a disturbance: seen = coefs + B v(t0 + i + 1) in a launch of its own; until the guard goes
@@ -2291,10 +2329,24 @@ int aoenv_run_integrator(AoEnv* env, int i0, int n_steps, double gain, void* d_o
     hipStream_t st = static_cast<hipStream_t>(stream);
     // only the last step's residual phase and camera frame can be read afterwards (aoenv_buffer, aoenv_download, aoenv_compute_psf,
     // d_frame, checkpoints: all of them between calls): the fused step leaves the stores of the other steps out
+    // ... and takes the step behind it along where that one is quiet (plan_step_pair): its arguments are then that step's
     if (env->delay.d == 0) {
-        for (int k = 0; k < n_steps; ++k)
-            AO_TRY(AO_DISPATCH(env, step_t, env, i0 + k, d_obs /*unused*/, d_obs, k == n_steps - 1 ? d_frame : nullptr, d_reward,
-                               d_strehl, gain, k == n_steps - 1, st));
+        const bool eligible = n_steps > 1 && step_pair_eligible(env);   // (nothing a step of this loop does changes it)
+        double ratio[kMaxLayer][2], buff[kMaxLayer][2];
+        for (int l = 0; eligible && l < env->L; ++l)
+            for (int d = 0; d < 2; ++d) ratio[l][d] = env->layer[l].clk.ratio[d];
+        for (int k = 0; k < n_steps;) {
+            for (int l = 0; eligible && l < env->L; ++l)
+                for (int d = 0; d < 2; ++d) buff[l][d] = env->layer[l].clk.buff[d];
+            const bool pair = plan_step_pair(eligible && !env->sci.accumulates(i0 + k + 1), k, n_steps, env->L, ratio, buff, env->pair.buff2);
+            const int last = k + (pair ? 1 : 0);
+            env->pair.on = pair;
+            const int rc = AO_DISPATCH(env, step_t, env, i0 + k, d_obs /*unused*/, d_obs, last == n_steps - 1 ? d_frame : nullptr, d_reward,
+                                       d_strehl, gain, last == n_steps - 1, st);
+            env->pair.on = false;
+            if (rc) return rc;
+            k = last + 1;
+        }
         return 0;
     }
     // under a delay the action formed now is applied d steps later: gain * obs goes into the ring (one small launch per step, one
@@ -3346,6 +3398,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
         case AOENV_OPT_STORE_ATM_OPD: env->store_opd_atm = value != 0; return 0;
         case AOENV_OPT_FUSED_TAIL: env->use_fused_tail = value != 0; return 0;
         case AOENV_OPT_FUSED_STEP: env->use_fused_step = value != 0; return 0;
+        case AOENV_OPT_STEP_PAIRS: env->use_step_pairs = value != 0; return 0;
         case AOENV_OPT_DEFER_RING: env->defer_ring = value != 0; return 0;
         case AOENV_OPT_FACTORED_RECON: env->use_factored_recon = value != 0; return 0;
         case AOENV_OPT_RING_LOOKAHEAD:
@@ -3381,6 +3434,15 @@ int aoenv_profile(AoEnv* env, int enable) {
     for (auto& e : env->prof_ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     env->prof_ev.clear();
     env->prof_on = enable != 0;
+    if (enable) env->step_launches = env->step_covered = 0;
+    return 0;
+}
+
+int aoenv_step_counters(AoEnv* env, int64_t* h_out) {
+    AO_CHECK_ENV(env);
+    if (!h_out) return fail("null argument");
+    h_out[0] = env->step_launches;
+    h_out[1] = env->step_covered;
     return 0;
 }
 
@@ -3393,7 +3455,7 @@ int aoenv_profile_read(AoEnv* env, double* h_ms, int32_t* h_count, void* stream)
         float ms = 0;
         AO_HIP(hipEventElapsedTime(&ms, e.a, e.b));
         h_ms[e.stage] += ms;
-        h_count[e.stage] += 1;
+        h_count[e.stage] += e.n;
     }
     return 0;
 }

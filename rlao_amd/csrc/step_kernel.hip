@@ -1,5 +1,5 @@
 // The fused step kernel's host side: its LDS layout, the envelope it serves and the choice of the instantiation for a launch.
-// The kernel is step_kernel_body.hpp; its instantiations are compiled in step_kernel_general.hip, step_kernel_nocam.hip,
+// The kernels are step_kernel_body.hpp (their body: step_body_text.hpp); its instantiations are compiled in step_kernel_general.hip, step_kernel_nocam.hip,
 // step_kernel_photon.hip, step_kernel_camera.hip and step_kernel_star.hip.
 #include "step_kernel.hpp"
 
@@ -44,20 +44,59 @@ int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes
 // tables that fits there for ALL its camera kernels, so that a pixel is drawn the same way whichever kernel meets it
 int step_alias_capacity(int n_act) { return step_lds_layout(n_act, 1, 1, 1).tab_cap; }
 
-int launch_env_step(const StepArgs& a, const StarEnv<float>& star, hipStream_t st) {
-    const StepLds L = step_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
-    if (a.det.active && a.det.photon_noise && (!a.pa.tab || a.pa.words > L.tab_cap || a.pa.lmax < palias::kCoarseStep))
-        return fail("fused step: the photon-noise tables are missing or do not fit (%d words, room for %d)", a.pa.words, L.tab_cap);
-    // the instantiation: per-env stars have their own; the general one without fast trig or under AOENV_PATH_SH_PLAIN, else by the
-    // camera's kind
-    if (star.amp || star.thr) return launch_env_step_spec<STEP_STAR>(a, L, star, st);
-    if (!a.sc.fast_trig || a.sc.plain) return launch_env_step_spec<STEP_GENERAL>(a, L, star, st);
-    if (!a.det.active) return launch_env_step_spec<STEP_NOCAM>(a, L, star, st);
+// the instantiation of a launch: per-env stars have their own; the general one without fast trig or under AOENV_PATH_SH_PLAIN,
+// else by the camera's kind
+static StepSpec step_spec(const StepArgs& a, const StarEnv<float>& star) {
+    if (star.amp || star.thr) return STEP_STAR;
+    if (!a.sc.fast_trig || a.sc.plain) return STEP_GENERAL;
+    if (!a.det.active) return STEP_NOCAM;
     const DetectorCfg& d = a.det;
     // (the condition under which camera_sh6_lane has nothing to do behind the photon draw)
     const bool after_photons = d.dark_e > 0.f || d.readout_noise != 0.f || d.qe != 1.f || d.gain != 1.f || d.fwc > 0.f || d.bits > 0;
-    if (d.photon_noise && !after_photons) return launch_env_step_spec<STEP_PHOTON>(a, L, star, st);
-    return launch_env_step_spec<STEP_CAMERA>(a, L, star, st);
+    return d.photon_noise && !after_photons ? STEP_PHOTON : STEP_CAMERA;
+}
+
+static int step_tables_fit(const StepArgs& a, const StepLds& L) {
+    if (a.det.active && a.det.photon_noise && (!a.pa.tab || a.pa.words > L.tab_cap || a.pa.lmax < palias::kCoarseStep))
+        return fail("fused step: the photon-noise tables are missing or do not fit (%d words, room for %d)", a.pa.words, L.tab_cap);
+    return 0;
+}
+
+int launch_env_step(const StepArgs& a, const StarEnv<float>& star, hipStream_t st) {
+    const StepLds L = step_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
+    AO_TRY(step_tables_fit(a, L));
+    switch (step_spec(a, star)) {
+        case STEP_STAR: return launch_env_step_spec<STEP_STAR>(a, L, star, st);
+        case STEP_GENERAL: return launch_env_step_spec<STEP_GENERAL>(a, L, star, st);
+        case STEP_NOCAM: return launch_env_step_spec<STEP_NOCAM>(a, L, star, st);
+        case STEP_PHOTON: return launch_env_step_spec<STEP_PHOTON>(a, L, star, st);
+        default: return launch_env_step_spec<STEP_CAMERA>(a, L, star, st);
+    }
+}
+
+bool env_step_pairable(const StepArgs& a, const StarEnv<float>& star) {
+    const StepSpec s = step_spec(a, star);
+    // Only where the camera's pixels are whole numbers -- photon counts, or ADC steps.  The centre of gravity's
+    // `xa * q3 + xb * (q3 + 3)` is a sum of two products; a launch of one step fuses five of its six terms and leaves one as two
+    // rounded products (the vectoriser packs that term's add with the sum of the intensities), the copies of a pair fuse other
+    // ones, and no way of writing the line makes a copy repeat that.  With whole-number pixels below 2^24 / 5 every product is
+    // exact and every form gives the same slopes; with float pixels (the ideal detector, read-out noise or a quantum efficiency
+    // without an ADC) the slopes of a pair differed from one launch per step in the last bit, so those launches do not pair.
+    if (a.k.pa.env_taps != nullptr) return false;
+    return s == STEP_PHOTON || (s == STEP_CAMERA && a.det.bits > 0 && a.det.bits <= 21);   // (5 (2^bits - 1) < 2^24)
+}
+
+int launch_env_step_pair(const StepArgs& a, hipStream_t st) {
+    const StepLds L = step_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
+    const StarEnv<float> star{nullptr, nullptr};
+    if (!env_step_pairable(a, star)) return fail("internal: a step pair on a launch that has no pair kernel");
+    // (the second step takes the integrator's inputs from the first one's registers)
+    if (!a.fa.do_integrate || a.fa.gain_from_obs == 0.f) return fail("internal: a step pair without the on-device integrator");
+    AO_TRY(step_tables_fit(a, L));
+    switch (step_spec(a, star)) {
+        case STEP_PHOTON: return launch_env_step_pair_spec<STEP_PHOTON>(a, L, star, st);
+        default: return launch_env_step_pair_spec<STEP_CAMERA>(a, L, star, st);
+    }
 }
 
 }  // namespace ao

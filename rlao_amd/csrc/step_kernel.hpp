@@ -1,5 +1,5 @@
 // What the translation units of the fused step kernel share: its LDS layout and the instantiations' launchers.
-// (step_kernel.hip: layout, envelope and dispatch; step_kernel_body.hpp: the kernel; step_kernel_<spec>.hip: one SPEC each, so
+// (step_kernel.hip: layout, envelope and dispatch; step_kernel_body.hpp: the kernels, step_body_text.hpp: their body; step_kernel_<spec>.hip: one SPEC each, so
 // that a parallel build compiles them side by side)
 #pragma once
 #include "common.hpp"
@@ -34,5 +34,11 @@ extern template int launch_env_step_spec<STEP_NOCAM>(const StepArgs&, const Step
 extern template int launch_env_step_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 extern template int launch_env_step_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 extern template int launch_env_step_spec<STEP_STAR>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+
+// the step and the quiet step behind it in one launch (k_env_step_pair_sh6): the specialised instantiations with a camera, shared clock
+template <int SPEC>
+int launch_env_step_pair_spec(const StepArgs& a, const StepLds& L, const StarEnv<float>& star, hipStream_t st);
+extern template int launch_env_step_pair_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+extern template int launch_env_step_pair_spec<STEP_CAMERA>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 
 }  // namespace ao

@@ -3,4 +3,5 @@
 
 namespace ao {
 template int launch_env_step_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
+template int launch_env_step_pair_spec<STEP_PHOTON>(const StepArgs&, const StepLds&, const StarEnv<float>&, hipStream_t);
 }  // namespace ao

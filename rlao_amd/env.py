@@ -575,6 +575,14 @@ class Shard:
                                             C.c_void_p(stream)))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(L.KERNEL_NAMES)}
 
+    def step_counters(self) -> tuple:
+        """(launches of the fused step kernel, steps they covered) since profile(True): a launch of two steps counts two."""
+        if not hasattr(self.lib, "aoenv_step_counters"):
+            raise L.AoEnvError("the library loaded through AOENV_LIB was built before aoenv_step_counters")
+        out = np.zeros(2, dtype=np.int64)
+        L.check(self.lib.aoenv_step_counters(self.h, out.ctypes.data_as(C.c_void_p)))
+        return int(out[0]), int(out[1])
+
     def get_buff(self, n_layer: int) -> np.ndarray:
         out = np.zeros((max(n_layer, 1), 2))
         L.check(self.lib.aoenv_get_buff(self.h, out.ctypes.data_as(C.c_void_p)))

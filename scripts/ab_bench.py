@@ -1,17 +1,19 @@
 """A/B timing of kernel builds on one GPU box: the headline bench (no extras) with each library in turn, ROUNDS times interleaved
 (A B A B ...: clocks and neighbours drift between runs), median per library.
-    python scripts/ab_bench.py [--noise off|photon|razor] [--rounds 3] [--config C2] name=path/to/libaoenv.so ...   ("main" = the tree's library)
+    python scripts/ab_bench.py [--noise off|photon|razor] [--rounds 3] [--config C2] [--json OUT.json] name=path/to/libaoenv.so ...   ("main" = the tree's library)
+--json merges every round's figures into OUT.json under the key "<config> <noise>".
 """
 import json, os, statistics, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = sys.argv[1:]
-noise, rounds, config = "photon", 3, "C2"
+noise, rounds, config, json_out = "photon", 3, "C2", None
 while args and args[0].startswith("--"):
     k, v = args[0], args[1]
     args = args[2:]
     if k == "--noise": noise = v
     elif k == "--rounds": rounds = int(v)
     elif k == "--config": config = v
+    elif k == "--json": json_out = v
 libs = [a.split("=", 1) for a in args]
 res = {n: {"step_us": [], "kernel_us": []} for n, _ in libs}
 for r in range(rounds):
@@ -33,3 +35,7 @@ for name, v in res.items():
     if v["step_us"]:
         print(f"{name:24s} step {statistics.median(v['step_us']):8.2f} us  [{min(v['step_us']):.2f} .. {max(v['step_us']):.2f}]   dominant kernel "
               f"{statistics.median(v['kernel_us']):8.2f} us  [{min(v['kernel_us']):.2f} .. {max(v['kernel_us']):.2f}]", flush=True)
+if json_out:
+    doc = json.load(open(json_out)) if os.path.exists(json_out) else {}
+    doc[f"{config} {noise}"] = {n: {"step_us_per_round": [round(x, 3) for x in v["step_us"]]} for n, v in res.items()}
+    json.dump(doc, open(json_out, "w"), indent=1)
