@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AOENV_LIB") or os.path.join(_HERE, "csrc", "libaoenv.so")   # AOENV_LIB: A/B kernel builds
 
@@ -188,6 +190,42 @@ def load():
     return lib
 
 
-def check(rc: int):
+def check(rc: int, lib=None):
     if rc != 0:
-        raise AoEnvError(load().aoenv_last_error().decode("utf-8", "replace"))
+        raise AoEnvError((lib or load()).aoenv_last_error().decode("utf-8", "replace"))
+
+
+def _pointer(a):
+    """One argument of an entry point in the form the library object is handed: a struct by reference, host and device memory
+    as ``c_void_p`` (an empty tensor has no address: None), everything else -- None, numbers, ready-made ctypes objects -- as it
+    is.  Only an object becomes a pointer here; the dtype an entry reads is the caller's business.  An array is never copied (it
+    may be an output), so one that is not C-contiguous is refused."""
+    if a is None or isinstance(a, (int, float)):
+        return a
+    if isinstance(a, np.ndarray):
+        if not a.flags.c_contiguous:
+            raise ValueError("an array handed to libaoenv must be C-contiguous (it is passed by address, never copied)")
+        return a.ctypes.data_as(C.c_void_p)
+    if isinstance(a, C.Structure):
+        return C.byref(a)
+    if hasattr(a, "data_ptr"):                                     # a torch tensor, host or device
+        return C.c_void_p(a.data_ptr()) if a.numel() else None
+    return a
+
+
+def address(a):
+    """The same memory as the integer a struct's pointer field takes (None: a null pointer)."""
+    p = _pointer(a)
+    return None if p is None else p.value
+
+
+def invoke(owner, name: str, *args):
+    """``owner.lib.<name>(owner.h, *args)`` with every argument through ``_pointer``; the entry's own return value.  ``owner``: a
+    ``Shard``, or anything else with ``.lib`` and ``.h``."""
+    return getattr(owner.lib, name)(owner.h, *[_pointer(a) for a in args])
+
+
+def call(owner, name: str, *args):
+    """The one way into the library for an entry point that returns a status: ``invoke``, and ``AoEnvError`` with the library's
+    message unless it is 0."""
+    check(invoke(owner, name, *args), owner.lib)

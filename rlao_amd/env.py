@@ -36,6 +36,11 @@ def _torch():
     return torch
 
 
+def _numpy64(t) -> np.ndarray:
+    """A tensor as the NumPy flavour hands it out: a float64 host array (the caller drops the env dimension)."""
+    return t.detach().to("cpu", dtype=_torch().float64).numpy()
+
+
 # what BatchedAOEnv.rollout returns: obs [K+1, N, a, a], action [K, N, a, a], reward [K, N], strehl [K, N]
 Rollout = namedtuple("Rollout", ["obs", "action", "reward", "strehl"])
 
@@ -47,8 +52,7 @@ def policy_arrays(policy) -> dict:
     0, 2, 4, the slope read from the LeakyReLU at position 1); or a dict, either of arrays ``w1 .. b3`` (optionally
     ``negative_slope``, default torch's 0.01) or a ``state_dict`` with the keys ``[net.]0.weight .. [net.]4.bias``."""
     def arr(t):
-        t = t.detach().cpu().numpy() if hasattr(t, "detach") else t
-        return np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+        return np.ascontiguousarray(np.asarray(_host(t), dtype=np.float64))
 
     slope = 0.01
     if isinstance(policy, dict):
@@ -81,11 +85,7 @@ def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
     that is not 1-D, ids out of range, duplicates, a mask of the wrong length or a non-integer dtype.  ``return_order``: also the
     ids in the caller's order (a mask: ascending), to pair per-env arguments and results with them.  Pure host code."""
     n_envs = int(n_envs)
-    if hasattr(env_ids, "detach"):                                  # a torch tensor, wherever it lives
-        env_ids = env_ids.detach().cpu().numpy()
-    elif isinstance(env_ids, range):
-        env_ids = list(env_ids)
-    a = np.asarray(env_ids)
+    a = np.asarray(list(env_ids) if isinstance(env_ids, range) else _host(env_ids))
     if a.ndim != 1:
         raise ValueError(f"env_ids must be 1-D, got shape {a.shape}")
     if a.dtype == np.bool_:
@@ -107,30 +107,64 @@ def normalize_env_ids(env_ids, n_envs: int, return_order: bool = False):
     return (ids, given) if return_order else ids
 
 
+def _host(x):
+    """A torch tensor, wherever it lives, as a NumPy array; anything else as it is."""
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else x
+
+
+def as_float64(value, name: str) -> np.ndarray:
+    """``value`` (numbers, sequences, arrays, tensors) as a float64 NumPy array; ``ValueError`` naming ``name`` for anything else."""
+    try:
+        return np.asarray(_host(value), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be numeric") from None
+
+
+def assign_per_env(value, env_ids, n_envs: int, current, name: str, tail=(), scalar=True, row=False, finite=True) -> np.ndarray:
+    """The rule of every per-env setter: the quantity ``name`` of all envs after an assignment, float64 ``[n_envs, *tail]``,
+    C-contiguous and the caller's own.  The rows written are those of ``env_ids`` (anything ``normalize_env_ids`` takes) IN THE
+    CALLER'S ORDER (a mask: ascending), every env without them; ``value`` has one row per written env, ``[k, *tail]``, or is a
+    scalar for all of them (``scalar``) or one shared row ``[*tail]`` (``row``).  A None in ``tail`` is a dimension the value is free
+    to choose.  The other envs keep their rows of ``current`` -- anything that broadcasts to the result, None: zeros -- which is
+    itself not written.  Raises ``ValueError`` for a value that is not numeric, has another shape or (``finite``) is not finite,
+    and for a ``current`` of another tail.  Pure host code."""
+    n_envs = int(n_envs)
+    rows = np.arange(n_envs) if env_ids is None else normalize_env_ids(env_ids, n_envs, return_order=True)[1]
+    v = as_float64(value, name)
+
+    def fits(shape):
+        return len(shape) == len(tail) and all(t is None or t == s for s, t in zip(shape, tail))
+
+    if not ((scalar and v.ndim == 0) or (row and tail and fits(v.shape)) or (v.ndim and v.shape[0] == len(rows) and fits(v.shape[1:]))):
+        def text(shape):                                           # (like a tuple's, a free dimension as J)
+            return "(" + ", ".join("J" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+        forms = ["be a scalar"] * bool(scalar) + [f"have shape {text(tail)}"] * bool(row and tail)
+        forms.append(f"have one {'row' if tail else 'value'} per {'env' if env_ids is None else 'listed env'}, "
+                     f"shape {text((len(rows),) + tuple(tail))}")
+        raise ValueError(f"{name} must {' or '.join(forms)}, got {v.shape}")
+    if v.ndim:
+        tail = v.shape[v.ndim - len(tail):]
+    if finite and not np.isfinite(v).all():
+        raise ValueError(f"{name} must be finite")
+    if env_ids is None or current is None:
+        full = np.zeros((n_envs,) + tuple(tail))
+    else:
+        cur = np.asarray(current, dtype=np.float64)
+        if cur.shape[max(cur.ndim - len(tail), 0):] != tuple(tail):
+            raise ValueError(f"env_ids: {name} in force has rows of shape {cur.shape[1:]}, this call {tuple(tail)}")
+        full = np.broadcast_to(cur, (n_envs,) + tuple(tail)).copy()
+    full[rows] = v
+    return full
+
+
 def resolve_r0_per_env(r0, env_ids, n_envs: int, current) -> np.ndarray:
     """The Fried parameter of every env after a per-env assignment, ``[n_envs]`` float64 [m @ 500 nm].  ``current``: the values
     in force, a scalar (one r0 for the shard) or ``[n_envs]``.  Without ``env_ids``, ``r0`` is ``[n_envs]``; with them (anything
     ``normalize_env_ids`` takes) it is one value per listed env, in the order of ``env_ids`` (a mask: ascending), or a scalar for
     all of them, and the other envs keep their value.  Raises ``ValueError`` for a wrong shape and for values that are not
     finite and positive.  Pure host code."""
-    n_envs = int(n_envs)
-    if hasattr(r0, "detach"):
-        r0 = r0.detach().cpu().numpy()
-    try:
-        v = np.asarray(r0, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("r0 must be numeric") from None
-    full = np.broadcast_to(np.asarray(current, dtype=np.float64), (n_envs,)).copy()
-    if env_ids is None:
-        if v.shape != (n_envs,):
-            raise ValueError(f"per-env r0 must have shape (n_envs={n_envs},), got {v.shape}")
-        full[:] = v
-    else:
-        given = normalize_env_ids(env_ids, n_envs, return_order=True)[1]
-        if v.ndim != 0 and v.shape != (given.size,):
-            raise ValueError(f"r0 must be a scalar or have one value per listed env, shape ({given.size},), got {v.shape}")
-        full[given] = v
-        v = full[given]
+    v = as_float64(r0, "r0")
+    full = assign_per_env(v, env_ids, n_envs, current, "r0", scalar=env_ids is not None, finite=False)
     if not (np.isfinite(v).all() and (v > 0).all()):
         raise ValueError("every r0 must be finite and positive")
     return full
@@ -160,48 +194,29 @@ def resolve_disturbance(modes, amp, freq, phase, t0, env_ids, n_envs: int, n_val
             raise ValueError(f"modes={M}: M2C_CL has {0 if m2c is None else np.shape(m2c)[1]} columns")
         B = np.asarray(m2c, dtype=np.float64)[:, :M]
     else:
-        if hasattr(modes, "detach"):
-            modes = modes.detach().cpu().numpy()
-        try:
-            B = np.asarray(modes, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("modes must be numeric") from None
+        B = as_float64(modes, "modes")
     if B.ndim != 2 or B.shape[0] != A:
         raise ValueError(f"modes must have shape (A={A}, M), got {B.shape}")
     M = B.shape[1]
     if not 1 <= M <= DISTURB_MAX_MODES:
         raise ValueError(f"M = {M} modes outside [1, {DISTURB_MAX_MODES}]")
-    given = None if env_ids is None else normalize_env_ids(env_ids, n_envs, return_order=True)[1]
-    k = n_envs if given is None else int(given.size)
 
-    def block(x, name, J):
-        if hasattr(x, "detach"):
-            x = x.detach().cpu().numpy()
-        try:
-            v = np.asarray(x, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be numeric") from None
-        if v.ndim not in (2, 3) or v.shape[-2] != M or (J is not None and v.shape[-1] != J) or (v.ndim == 3 and v.shape[0] != k):
-            raise ValueError(f"{name} must have shape (M={M}, J) or ({k}, M={M}, J), got {v.shape}")
-        return np.broadcast_to(v, (k,) + v.shape[-2:])
+    def block(v, name, J):                                          # [M, J] for every written env or one block each; J: amp chooses it
+        return assign_per_env(v, env_ids, n_envs, None if current is None else current[name], name, tail=(M, J), scalar=False,
+                              row=True, finite=False)
 
-    a = block(amp, "amp", None)
-    J = a.shape[-1]
+    a = as_float64(amp, "amp")
+    out = {"amp": block(a, "amp", None)}
+    J = out["amp"].shape[-1]
     if not 1 <= J <= DISTURB_MAX_LINES:
         raise ValueError(f"J = {J} lines outside [1, {DISTURB_MAX_LINES}]")
-    f = block(freq, "freq", J) * float(sampling_time)
-    ph = np.zeros((k, M, J)) if phase is None else block(phase, "phase", J)
+    f = as_float64(freq, "freq") * float(sampling_time)
+    ph = np.zeros((M, J)) if phase is None else as_float64(phase, "phase")
+    out["freq"], out["phase"] = block(f, "freq", J), block(ph, "phase", J)
     if not (np.isfinite(B).all() and np.isfinite(a).all() and np.isfinite(f).all() and np.isfinite(ph).all()):
         raise ValueError("modes, amp, freq and phase must be finite")
     if (a < 0).any():
         raise ValueError("amp must be >= 0 (a sign belongs into the phase: half a cycle)")
-    out = {"amp": np.zeros((n_envs, M, J)), "freq": np.zeros((n_envs, M, J)), "phase": np.zeros((n_envs, M, J))}
-    if given is not None and current is not None:
-        if current["amp"].shape != (n_envs, M, J):
-            raise ValueError(f"env_ids: the disturbance in force has (M, J) = {current['amp'].shape[1:]}, this call ({M}, {J})")
-        out = {key: current[key].copy() for key in out}
-    rows = slice(None) if given is None else given
-    out["amp"][rows], out["freq"][rows], out["phase"][rows] = a, f, ph
     out["modes"] = np.ascontiguousarray(B, dtype=np.float64).copy()
     out["t0"] = int(t0)
     return out
@@ -215,23 +230,14 @@ def resolve_modal(n_modes, m2c, cm, n_valid_act: int, n_signal: int, m2c_cl=None
     (MAIN/OOPAOEnv/modalAOEnv.py:410, 447-449).  Raises ``ValueError`` for wrong shapes, K outside [1, A] and values that are not
     finite.  Pure host code."""
     A, nS = int(n_valid_act), int(n_signal)
-
-    def arr(x, name):
-        if hasattr(x, "detach"):
-            x = x.detach().cpu().numpy()
-        try:
-            return np.asarray(x, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be numeric") from None
-
     if n_modes is not None and (isinstance(n_modes, bool) or not isinstance(n_modes, (int, np.integer))):
         raise ValueError(f"n_modes must be an int, got {n_modes!r}")
     if m2c is None:
         if m2c_cl is None:
             raise ValueError("m2c=None needs the env's M2C_CL (set_params)")
-        B = arr(m2c_cl, "M2C_CL")
+        B = as_float64(m2c_cl, "M2C_CL")
     else:
-        B = arr(m2c, "m2c")
+        B = as_float64(m2c, "m2c")
     if B.ndim != 2 or B.shape[0] != A:
         raise ValueError(f"m2c must have shape (A={A}, K), got {B.shape}")
     K = B.shape[1] if n_modes is None else int(n_modes)
@@ -244,7 +250,7 @@ def resolve_modal(n_modes, m2c, cm, n_valid_act: int, n_signal: int, m2c_cl=None
         from . import calib
         M = np.asarray(calib.reconstructor_from_imat(np.asarray(imat, dtype=np.float64), B, True)[2], dtype=np.float64)
     else:
-        M = arr(cm, "cm")
+        M = as_float64(cm, "cm")
     if M.shape != (K, nS):
         raise ValueError(f"cm must have shape (K={K}, n_signal={nS}), got {M.shape}")
     if not (np.isfinite(B).all() and np.isfinite(M).all()):
@@ -265,12 +271,7 @@ def resolve_wavefront_basis(m2opd, opd2m, n_modes, n_pix: int) -> np.ndarray:
         raise ValueError("n_modes must be an int")
 
     def table(a, name):
-        if hasattr(a, "detach"):
-            a = a.detach().cpu().numpy()
-        try:
-            a = np.array(a, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be numeric") from None
+        a = as_float64(a, name).copy(order="K")                           # (the result may be a cut of it: never the caller's memory)
         if a.ndim != 2 or not np.isfinite(a).all():
             raise ValueError(f"{name} must be a finite 2-d table")
         return a
@@ -337,33 +338,13 @@ def resolve_modal_gain(g, env_ids, n_envs: int, n_modes: int, current=None):
     (anything ``normalize_env_ids`` takes) a scalar, ``[K]`` or one row per listed env in the order of ``env_ids``, the other envs
     keeping the rows of ``current`` (an earlier result's ``gain``) or, without one, gain 0: open loop.  Raises ``ValueError`` for
     wrong shapes and for entries that are not finite or negative.  Pure host code."""
-    n_envs, K = int(n_envs), int(n_modes)
-    if hasattr(g, "detach"):
-        g = g.detach().cpu().numpy()
-    try:
-        v = np.asarray(g, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("gains must be numeric") from None
-    given = None if env_ids is None else normalize_env_ids(env_ids, n_envs, return_order=True)[1]
-    k = n_envs if given is None else int(given.size)
-    if v.ndim > 2 or (v.ndim >= 1 and v.shape[-1] != K) or (v.ndim == 2 and v.shape[0] != k):
-        raise ValueError(f"gains must be a scalar or have shape (K={K},) or ({k}, K={K}), got {v.shape}")
-    if not np.isfinite(v).all():
-        raise ValueError("gains must be finite")
+    v = as_float64(g, "gains")
+    full = assign_per_env(v, env_ids, n_envs, current, "gains", tail=(int(n_modes),), row=True)
     if (v < 0).any():
         raise ValueError("gains must be >= 0")
-    if given is None and v.ndim < 2:
-        return np.ascontiguousarray(np.broadcast_to(v, (K,))).copy(), False
-    if given is None:
-        return np.ascontiguousarray(v).copy(), True
-    out = np.zeros((n_envs, K))
-    if current is not None:
-        cur = np.asarray(current, dtype=np.float64)
-        if cur.shape[-1] != K:
-            raise ValueError(f"env_ids: the gains in force have K = {cur.shape[-1]}, this call {K}")
-        out[:] = cur
-    out[given] = v
-    return out, True
+    if env_ids is None and v.ndim < 2:                              # one row of gains for every env: the library takes it as [K]
+        return full[0].copy(), False
+    return full, True
 
 
 def disturbance_value(cfg: dict, i: int) -> np.ndarray:
@@ -408,30 +389,15 @@ def resolve_dm_misregistration(values: dict, env_ids, n_envs: int, current) -> d
     ``current``: the dict in force, or None (every env the calibrated mirror: zeros).  Envs not listed keep what they have.  Raises
     ``ValueError`` for unknown keys, wrong shapes, non-numeric or non-finite values and a scaling at or below -1 (a mirror of
     zero or negative size).  Pure host code."""
-    n_envs = int(n_envs)
     unknown = set(values) - set(MISREG_KEYS)
     if unknown:
         raise ValueError(f"unknown mis-registration parameter(s) {sorted(unknown)}")
-    if env_ids is None:
-        rows = np.arange(n_envs)
-    else:
-        _, rows = normalize_env_ids(env_ids, n_envs, return_order=True)
-    out = {k: (np.zeros(n_envs) if current is None else np.array(current[k], dtype=np.float64)) for k in MISREG_KEYS}
+    out = {}
     for k in MISREG_KEYS:
-        v = values.get(k, 0)
-        if hasattr(v, "detach"):
-            v = v.detach().cpu().numpy()
-        try:
-            v = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"{k} must be numeric") from None
-        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != len(rows)):
-            raise ValueError(f"{k} must be a scalar or have shape ({len(rows)},), got {v.shape}")
-        if not np.isfinite(v).all():
-            raise ValueError(f"{k} must be finite")
+        v = as_float64(values.get(k, 0), k)
+        out[k] = assign_per_env(v, env_ids, n_envs, None if current is None else current[k], k)
         if k.endswith("scaling") and (v <= -1).any():
             raise ValueError(f"{k} must be above -1")
-        out[k][rows] = v
     return out
 
 
@@ -447,32 +413,26 @@ def resolve_star_per_env(kind: str, value, env_ids, n_envs: int, current) -> np.
     threshold below 0.  Pure host code."""
     if kind not in STAR_KINDS:
         raise ValueError(f"unknown per-env star parameter {kind!r}")
-    n_envs = int(n_envs)
-    if env_ids is None:
-        rows = np.arange(n_envs)
-    else:
-        _, rows = normalize_env_ids(env_ids, n_envs, return_order=True)
-    v = value
-    if hasattr(v, "detach"):
-        v = v.detach().cpu().numpy()
-    try:
-        v = np.asarray(v, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{kind} must be numeric") from None
-    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != len(rows)):
-        raise ValueError(f"{kind} must be a scalar or have shape ({len(rows)},), got {v.shape}")
-    if not np.isfinite(v).all():
-        raise ValueError(f"{kind} must be finite")
+    v = as_float64(value, kind)
+    out = assign_per_env(v, env_ids, n_envs, current, kind)
     low = STAR_KINDS[kind]
     if low is not None and (v < low).any():
         raise ValueError(f"{kind} must not be below {low:g}")
-    out = np.array(current, dtype=np.float64).reshape(n_envs).copy()
-    out[rows] = v
     return out
 
 
+def _f64(x):
+    """Host memory an entry point reads as float64 (None, an argument left out, stays None)."""
+    return None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+
+
+def _u32(x):
+    return np.ascontiguousarray(x, dtype=np.uint32)
+
+
 class Shard:
-    """One AoEnv handle of libaoenv (a shard of independent loops on one GPU)."""
+    """One AoEnv handle of libaoenv (a shard of independent loops on one GPU).  Every entry point is reached through ``L.call``,
+    which turns arrays, tensors and structs into pointers; the dtype an entry reads is chosen here."""
 
     def __init__(self, cfg: dict, device: int):
         self.lib = L.load()
@@ -498,9 +458,9 @@ class Shard:
                 L.C_SH_SUBAP_IDX: np.int32}.get(kind, np.float64)
         a = np.ascontiguousarray(arr, dtype=want)
         if layer is None:
-            L.check(self.lib.aoenv_upload(self.h, kind, a.ctypes.data_as(C.c_void_p), a.nbytes))
+            L.call(self, "aoenv_upload", kind, a, a.nbytes)
         else:
-            L.check(self.lib.aoenv_upload_layer(self.h, kind, int(layer), a.ctypes.data_as(C.c_void_p), a.nbytes))
+            L.call(self, "aoenv_upload_layer", kind, int(layer), a, a.nbytes)
 
     def upload_ring_tables(self, at, only_ab=False):
         """[A | B] and the ring index tables of every layer (calib.AtmosphereTables): one set when all layers share a grid."""
@@ -517,62 +477,50 @@ class Shard:
                 self.upload(L.C_OUTER_IDX, t.outer_idx, layer=l)
 
     def set_wind(self, ratio: np.ndarray, reset_buff: bool):
-        r = np.ascontiguousarray(ratio, dtype=np.float64)
-        L.check(self.lib.aoenv_set_wind(self.h, r.ctypes.data_as(C.c_void_p), int(reset_buff)))
+        L.call(self, "aoenv_set_wind", _f64(ratio), int(reset_buff))
 
     def new_screens(self, screens, ring_seeds, stream=0):
-        s = None if screens is None else np.ascontiguousarray(screens, dtype=np.float64)
-        k = np.ascontiguousarray(ring_seeds, dtype=np.uint32)
-        L.check(self.lib.aoenv_new_screens(self.h, None if s is None else s.ctypes.data_as(C.c_void_p),
-                                           k.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        L.call(self, "aoenv_new_screens", _f64(screens), _u32(ring_seeds), stream)
 
     def new_screens_device(self, screen_seeds, ring_seeds, r0, L0, pixel_size, stream=0):
-        a = np.ascontiguousarray(screen_seeds, dtype=np.uint32)
-        k = np.ascontiguousarray(ring_seeds, dtype=np.uint32)
-        L.check(self.lib.aoenv_new_screens_device(self.h, a.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p),
-                                                  float(r0), float(L0), float(pixel_size), C.c_void_p(stream)))
+        L.call(self, "aoenv_new_screens_device", _u32(screen_seeds), _u32(ring_seeds), float(r0), float(L0), float(pixel_size), stream)
 
     def reset_envs(self, env_idx, screen_seeds, ring_seeds, r0, L0, pixel_size, stream=0):
         """aoenv_reset_envs: seeds [len(env_idx)][n_layer], row c for env env_idx[c]."""
         i = np.ascontiguousarray(env_idx, dtype=np.int32)
-        a = np.ascontiguousarray(screen_seeds, dtype=np.uint32)
-        k = np.ascontiguousarray(ring_seeds, dtype=np.uint32)
-        L.check(self.lib.aoenv_reset_envs(self.h, i.ctypes.data_as(C.c_void_p), int(i.size), a.ctypes.data_as(C.c_void_p),
-                                          k.ctypes.data_as(C.c_void_p), float(r0), float(L0), float(pixel_size), C.c_void_p(stream)))
+        L.call(self, "aoenv_reset_envs", i, int(i.size), _u32(screen_seeds), _u32(ring_seeds), float(r0), float(L0), float(pixel_size),
+               stream)
 
     def set_atm_opd(self, opd, stream=0):
-        a = None if opd is None else np.ascontiguousarray(opd, dtype=np.float64)
-        L.check(self.lib.aoenv_set_atm_opd(self.h, None if a is None else a.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        L.call(self, "aoenv_set_atm_opd", _f64(opd), stream)
 
     def set_coefs(self, coefs, stream=0):
-        a = None if coefs is None else np.ascontiguousarray(coefs, dtype=np.float64)
-        L.check(self.lib.aoenv_set_coefs(self.h, None if a is None else a.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        L.call(self, "aoenv_set_coefs", _f64(coefs), stream)
 
     def measure(self, stream=0):
-        L.check(self.lib.aoenv_measure(self.h, C.c_void_p(stream)))
+        L.call(self, "aoenv_measure", stream)
 
     def atm_update(self, stream=0):
-        L.check(self.lib.aoenv_atm_update(self.h, C.c_void_p(stream)))
+        L.call(self, "aoenv_atm_update", stream)
 
     def download(self, which: int, shape, stream=0, dtype=None) -> np.ndarray:
         out = np.empty(shape, dtype=self.np_dtype if dtype is None else dtype)
-        L.check(self.lib.aoenv_download(self.h, which, out.ctypes.data_as(C.c_void_p), out.nbytes, C.c_void_p(stream)))
+        L.call(self, "aoenv_download", which, out, out.nbytes, stream)
         return out
 
     def upload_state(self, which: int, arr, stream=0, dtype=None):
         a = np.ascontiguousarray(arr, dtype=self.np_dtype if dtype is None else dtype)
-        L.check(self.lib.aoenv_upload_state(self.h, which, a.ctypes.data_as(C.c_void_p), a.nbytes, C.c_void_p(stream)))
+        L.call(self, "aoenv_upload_state", which, a, a.nbytes, stream)
 
     def profile(self, enable: bool):
-        L.check(self.lib.aoenv_profile(self.h, int(enable)))
+        L.call(self, "aoenv_profile", int(enable))
 
     def profile_read(self, stream=0) -> dict:
         """{kernel name: (total_ms, launches)} recorded since profile(True)."""
         n = len(L.KERNEL_NAMES)
         ms = np.zeros(n)
         cnt = np.zeros(n, dtype=np.int32)
-        L.check(self.lib.aoenv_profile_read(self.h, ms.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p),
-                                            C.c_void_p(stream)))
+        L.call(self, "aoenv_profile_read", ms, cnt, stream)
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(L.KERNEL_NAMES)}
 
     def step_counters(self) -> tuple:
@@ -580,88 +528,79 @@ class Shard:
         if not hasattr(self.lib, "aoenv_step_counters"):
             raise L.AoEnvError("the library loaded through AOENV_LIB was built before aoenv_step_counters")
         out = np.zeros(2, dtype=np.int64)
-        L.check(self.lib.aoenv_step_counters(self.h, out.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_step_counters", out)
         return int(out[0]), int(out[1])
 
     def get_buff(self, n_layer: int) -> np.ndarray:
         out = np.zeros((max(n_layer, 1), 2))
-        L.check(self.lib.aoenv_get_buff(self.h, out.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_get_buff", out)
         return out[:n_layer]
 
     def set_buff(self, buff):
-        b = np.ascontiguousarray(buff, dtype=np.float64)
-        L.check(self.lib.aoenv_set_buff(self.h, b.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_set_buff", _f64(buff))
 
     # per-env clocks: ratio [n_layer][n_env][2] pixels per frame; clock [n_layer][n_env][4] = (ratio x, y, buff x, y)
     def set_wind_env(self, ratio: np.ndarray, reset_buff: bool, stream=0):
-        r = np.ascontiguousarray(ratio, dtype=np.float64)
-        L.check(self.lib.aoenv_set_wind_env(self.h, r.ctypes.data_as(C.c_void_p), int(reset_buff), C.c_void_p(stream)))
+        L.call(self, "aoenv_set_wind_env", _f64(ratio), int(reset_buff), stream)
 
     def get_clock_env(self, n_layer: int, n_env: int) -> np.ndarray:
         out = np.zeros((n_layer, n_env, 4))
-        L.check(self.lib.aoenv_get_clock_env(self.h, out.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_get_clock_env", out)
         return out
 
     def set_clock_env(self, clock):
-        c = np.ascontiguousarray(clock, dtype=np.float64)
-        L.check(self.lib.aoenv_set_clock_env(self.h, c.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_set_clock_env", _f64(clock))
+
+    def _per_env(self, values, what: str, tail=()):
+        """``values`` as the float64 ``[n_env, *tail]`` a per-env entry point reads (None, the shared state again, stays None)."""
+        a = _f64(values)
+        if a is not None and a.shape != (self.cfg.n_env,) + tail:
+            raise ValueError(f"per-env {what} must have shape {(self.cfg.n_env,) + tail}")
+        return a
 
     # per-env Fried parameter: r0 [n_env] metres at 500 nm (None: one r0 for the shard again); r0_tables: the r0 of the uploaded C_AB
     def set_r0_env(self, r0, r0_tables: float, stream=0):
-        a = None if r0 is None else np.ascontiguousarray(r0, dtype=np.float64)
-        if a is not None and a.shape != (self.cfg.n_env,):
-            raise ValueError(f"per-env r0 must have shape ({self.cfg.n_env},)")
-        L.check(self.lib.aoenv_set_r0_env(self.h, None if a is None else a.ctypes.data_as(C.c_void_p), float(r0_tables), C.c_void_p(stream)))
+        L.call(self, "aoenv_set_r0_env", self._per_env(r0, "r0"), float(r0_tables), stream)
 
     def get_r0_env(self) -> np.ndarray:
         out = np.zeros(self.cfg.n_env)
-        L.check(self.lib.aoenv_get_r0_env(self.h, out.ctypes.data_as(C.c_void_p)))
+        L.call(self, "aoenv_get_r0_env", out)
         return out
 
     # per-env mirrors: gx, gy [n_env][R][n_act] float64 (both None: the shared tables again)
     def set_dm_env(self, gx, gy, stream=0):
-        if gx is None and gy is None:
-            L.check(self.lib.aoenv_set_dm_env(self.h, None, None, C.c_void_p(stream)))
-            return
-        shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.n_act)
-        a, b = (np.ascontiguousarray(t, dtype=np.float64) for t in (gx, gy))
-        if a.shape != shape or b.shape != shape:
-            raise ValueError(f"per-env DM tables must have shape {shape}")
-        L.check(self.lib.aoenv_set_dm_env(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        if gx is not None or gy is not None:                        # (one of them None is no table: refused by its shape)
+            tail = (self.cfg.resolution, self.cfg.n_act)
+            gx, gy = (self._per_env(np.asarray(t, dtype=np.float64), "DM tables", tail) for t in (gx, gy))
+        L.call(self, "aoenv_set_dm_env", gx, gy, stream)
 
     def get_dm_env(self, stream=0):
         shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.n_act)
         gx, gy = np.zeros(shape), np.zeros(shape)
-        L.check(self.lib.aoenv_get_dm_env(self.h, gx.ctypes.data_as(C.c_void_p), gy.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        L.call(self, "aoenv_get_dm_env", gx, gy, stream)
         return gx, gy
 
     # per-env guide stars: flux relative to the uploaded C_WFS_AMP / centroid thresholds, [n_env] float64 (None: one for the shard)
-    def _set_star_row(self, fn, values, stream):
-        if values is None:
-            L.check(fn(self.h, None, C.c_void_p(stream)))
-            return
-        a = np.ascontiguousarray(values, dtype=np.float64)
-        if a.shape != (self.cfg.n_env,):
-            raise ValueError(f"per-env star values must have shape ({self.cfg.n_env},)")
-        L.check(fn(self.h, a.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+    def _set_star_row(self, name, values, stream):
+        L.call(self, name, self._per_env(values, "star values"), stream)
 
-    def _get_star_row(self, fn, stream):
+    def _get_star_row(self, name, stream):
         out = np.zeros(self.cfg.n_env)
-        L.check(fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+        L.call(self, name, out, stream)
         return out
 
     def set_flux_env(self, scale, stream=0):
-        self._set_star_row(self.lib.aoenv_set_flux_env, scale, stream)
+        self._set_star_row("aoenv_set_flux_env", scale, stream)
 
     def get_flux_env(self, stream=0):
         """The amplitude factors sqrt(scale) as held (env dtype widened)."""
-        return self._get_star_row(self.lib.aoenv_get_flux_env, stream)
+        return self._get_star_row("aoenv_get_flux_env", stream)
 
     def set_threshold_env(self, thr, stream=0):
-        self._set_star_row(self.lib.aoenv_set_threshold_env, thr, stream)
+        self._set_star_row("aoenv_set_threshold_env", thr, stream)
 
     def get_threshold_env(self, stream=0):
-        return self._get_star_row(self.lib.aoenv_get_threshold_env, stream)
+        return self._get_star_row("aoenv_get_threshold_env", stream)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -772,8 +711,7 @@ class _DmProxy:
     @coefs.setter
     def coefs(self, val):
         e = self._e
-        if hasattr(val, "detach"):                                  # a tensor, wherever it lives (dm.coefs_seen of a twin)
-            val = val.detach().cpu().numpy()
+        val = _host(val)                                            # (a tensor: dm.coefs_seen of a twin)
         if np.isscalar(val):
             if val != 0:
                 print("Error: wrong value for the coefficients")
@@ -869,8 +807,7 @@ class _SourceProxy:
         if name == "magnitude":
             self._e.set_magnitude_per_env(value)
         elif name == "nPhoton":
-            v = value.detach().cpu().numpy() if hasattr(value, "detach") else value
-            v = np.asarray(v, dtype=np.float64)
+            v = np.asarray(_host(value), dtype=np.float64)
             if not (np.isfinite(v).all() and (v > 0).all()):
                 raise ValueError("nPhoton must be finite and above 0")
             self._e.set_magnitude_per_env(-2.5 * np.log10(v / self.zeroPoint))
@@ -955,7 +892,7 @@ class _TelProxy:
         torch = _torch()
         M = int(zeroPaddingFactor) * e.R
         psf = torch.empty((e.n_envs, M, M), device=e.device, dtype=e.tdtype)
-        L.check(e._shard.lib.aoenv_compute_psf(e._shard.h, int(zeroPaddingFactor), C.c_void_p(psf.data_ptr()), C.c_void_p(e._stream())))
+        L.call(e._shard, "aoenv_compute_psf", int(zeroPaddingFactor), psf, e._stream())
         if e.output == "numpy":
             self.PSF = psf[0].double().cpu().numpy()
             self.PSF_norma = self.PSF / self.PSF.max()
@@ -1331,7 +1268,7 @@ class BatchedAOEnv:
                          env_index_offset=int(self.env_index_offset), qe=float(cam.QE),
                          dark_electrons=float(cam.darkCurrent) * float(t_int), fwc=float(cam.FWC or 0), gain=float(cam.gain),
                          readout_noise=float(cam.readoutNoise), seed=int(self.detector_seed) & 0xFFFFFFFFFFFFFFFF)
-        L.check(self._shard.lib.aoenv_set_detector(self._shard.h, C.byref(d), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_detector", d, self._stream())
 
     def _push_wind(self, reset: bool):
         p = self.param
@@ -1350,7 +1287,7 @@ class BatchedAOEnv:
         frame or more needs before ``reset_envs``.  Refused, with nothing changed: n outside 1 .. 8, or at or below a wind the
         per-env clocks hold."""
         n = int(n)
-        L.check(self._shard.lib.aoenv_set_option(self._shard.h, L.OPT_ENV_WIND_PIXELS, n))
+        L.call(self._shard, "aoenv_set_option", L.OPT_ENV_WIND_PIXELS, n)
         self._wind_pixels = n
 
     def set_wind_per_env(self, speed=None, direction=None, reset: bool = False, max_pixels=None):
@@ -1403,15 +1340,14 @@ class BatchedAOEnv:
         of ``get_state``: after ``set_state`` call this again."""
         full = resolve_disturbance(modes, amp, freq, phase, t0, env_ids, self.n_envs, self.nValidAct, self.param.samplingTime,
                                    self.M2C_CL, self._disturb)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        cfg = L.AoDisturbance(n_modes=full["modes"].shape[1], n_lines=full["amp"].shape[2], t0=full["t0"], h_modes=ptr(full["modes"]),
-                              h_amp=ptr(full["amp"]), h_freq=ptr(full["freq"]), h_phase=ptr(full["phase"]))
-        L.check(self._shard.lib.aoenv_set_disturbance(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        cfg = L.AoDisturbance(n_modes=full["modes"].shape[1], n_lines=full["amp"].shape[2], t0=full["t0"],
+                              **{f"h_{key}": L.address(full[key]) for key in ("modes", "amp", "freq", "phase")})
+        L.call(self._shard, "aoenv_set_disturbance", cfg, self._stream())
         self._disturb = full
 
     def clear_disturbance(self):
         """No disturbance: every call does exactly what it did before ``set_disturbance``."""
-        L.check(self._shard.lib.aoenv_set_disturbance(self._shard.h, None, C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_disturbance", None, self._stream())
         self._disturb = None
 
     def disturbance(self, i: int) -> np.ndarray:
@@ -1468,32 +1404,14 @@ class BatchedAOEnv:
         the meaning of ``calib.DMTables.gx`` / ``gy`` (a two-DM env: the composite ``[gx1 | gx2]``).  A dead actuator is a zero
         column, an actuator gain a scaled one.  ``dm_misregistration`` is None from then on.  Bad arguments raise before anything is
         touched.  Not part of ``get_state``."""
-        R, nA = self.R, self.nActuator
         if env_ids is None:
-            rows = np.arange(self.n_envs)
-        else:
-            _, rows = normalize_env_ids(env_ids, self.n_envs, return_order=True)
-        tabs = []
-        for name, t in (("gx", gx), ("gy", gy)):
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            try:
-                t = np.asarray(t, dtype=np.float64)
-            except (TypeError, ValueError):
-                raise ValueError(f"{name} must be numeric") from None
-            if t.shape != (len(rows), R, nA):
-                raise ValueError(f"{name} must have shape ({len(rows)}, {R}, {nA}), got {t.shape}")
-            if not np.isfinite(t).all():
-                raise ValueError(f"{name} must be finite")
-            tabs.append(t)
-        if len(rows) == self.n_envs:
-            full = [np.empty((self.n_envs, R, nA)) for _ in tabs]
+            cur = (None, None)
         elif self._dm_per_env:
-            full = list(self._shard.get_dm_env(self._stream()))     # (values as held: a second rounding to the env dtype changes nothing)
+            cur = self._shard.get_dm_env(self._stream())            # (values as held: a second rounding to the env dtype changes nothing)
         else:
-            full = [np.tile(np.asarray(t, dtype=np.float64), (self.n_envs, 1, 1)) for t in (self._dm_tables.gx, self._dm_tables.gy)]
-        for f, t in zip(full, tabs):
-            f[rows] = t
+            cur = (self._dm_tables.gx, self._dm_tables.gy)
+        full = [assign_per_env(t, env_ids, self.n_envs, c, name, tail=(self.R, self.nActuator), scalar=False)
+                for name, t, c in (("gx", gx, cur[0]), ("gy", gy, cur[1]))]
         self._shard.set_dm_env(full[0], full[1], self._stream())
         self._dm_per_env, self._dm_misreg = True, None
 
@@ -1565,18 +1483,18 @@ class BatchedAOEnv:
         zeroes the delay line; with the current ``d`` it is the clear of a new episode, which ``reset_soft()`` does by itself.
         ``set_delay(0)``: no delay, every call does exactly what it did before.  Use this INSTEAD of wrapping the env: a
         ``TimeDelayEnv`` around an env with a library delay adds the two."""
-        L.check(self._shard.lib.aoenv_set_delay(self._shard.h, int(d), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_delay", int(d), self._stream())
 
     @property
     def delay(self) -> int:
         """The control delay in force, in frames (``set_delay``)."""
         d = C.c_int(0)
-        L.check(self._shard.lib.aoenv_get_delay(self._shard.h, C.byref(d)))
+        L.call(self._shard, "aoenv_get_delay", C.byref(d))
         return int(d.value)
 
     def _delay_line_host(self, d: int) -> np.ndarray:
-        line = np.empty((d, self.n_envs, self.nActuator, self.nActuator), dtype=np.float32 if self.dtype == "f32" else np.float64)
-        L.check(self._shard.lib.aoenv_get_delay_line(self._shard.h, line.ctypes.data_as(C.c_void_p), line.nbytes, C.c_void_p(self._stream())))
+        line = np.empty((d, self.n_envs, self.nActuator, self.nActuator), dtype=_NP_DT[self.dtype])
+        L.call(self._shard, "aoenv_get_delay_line", line, line.nbytes, self._stream())
         return line
 
     def delay_line(self):
@@ -1588,9 +1506,7 @@ class BatchedAOEnv:
             line = torch.empty((0, self.n_envs, self.nActuator, self.nActuator), device=self.device, dtype=self.tdtype)
         else:
             line = torch.as_tensor(self._delay_line_host(d)).to(self.device)
-        if self.output == "numpy":
-            return line.detach().to("cpu", dtype=torch.float64).numpy()[:, 0]
-        return line
+        return _numpy64(line)[:, 0] if self.output == "numpy" else line
 
     # -- the modal control surface (MAIN/OOPAOEnv/modalAOEnv.py; aoenv_set_modal) ------------------------------------------------
     def set_modal(self, n_modes=None, m2c=None, cm=None):
@@ -1603,14 +1519,13 @@ class BatchedAOEnv:
         and unchanged; delays, disturbances, per-env winds, r0 and mirrors act on a modal step as on a zonal one.  A new basis
         forgets the gains of ``set_modal_gain``.  Not part of ``get_state``: after ``set_state`` on a new env call this again."""
         full = resolve_modal(n_modes, m2c, cm, self.nValidAct, self.nSignal, self.M2C_CL, self.imat)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        cfg = L.AoModal(n_modes=full["m2c"].shape[1], h_m2c=ptr(full["m2c"]), h_cm=ptr(full["cm"]))
-        L.check(self._shard.lib.aoenv_set_modal(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        cfg = L.AoModal(n_modes=full["m2c"].shape[1], h_m2c=L.address(full["m2c"]), h_cm=L.address(full["cm"]))
+        L.call(self._shard, "aoenv_set_modal", cfg, self._stream())
         self._modal, self._modal_gain, self._mobs = full, None, None
 
     def clear_modal(self):
         """No modal surface: the basis, the gains and the device memory of both are gone."""
-        L.check(self._shard.lib.aoenv_set_modal(self._shard.h, None, C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_modal", None, self._stream())
         self._modal = self._modal_gain = self._mobs = None
 
     @property
@@ -1634,23 +1549,17 @@ class BatchedAOEnv:
         shard.  With ``env_ids`` (a list or a mask) the rows belong to the listed envs, in that order, and the other envs keep
         theirs (none yet: 0, open loop).  Gains are finite and >= 0."""
         self._require_modal()
-        cur = self._modal_gain
-        if cur is not None and cur.ndim == 1:
-            cur = np.broadcast_to(cur, (self.n_envs, cur.shape[0]))
-        gain, per_env = resolve_modal_gain(g, env_ids, self.n_envs, self.n_modal, cur)
-        L.check(self._shard.lib.aoenv_set_modal_gain(self._shard.h, gain.ctypes.data_as(C.c_void_p), int(per_env), C.c_void_p(self._stream())))
+        gain, per_env = resolve_modal_gain(g, env_ids, self.n_envs, self.n_modal, self._modal_gain)   # (gains [K] in force: every env's row)
+        L.call(self._shard, "aoenv_set_modal_gain", gain, int(per_env), self._stream())
         self._modal_gain = gain
 
     def reset_soft_modal(self):
         """``reset_soft`` in mode space: the modal reconstruction ``[n_envs, K]`` of the measurement as it stands (no disturbance;
         a library delay line is cleared, as ``reset_soft`` does)."""
         self._require_modal()
-        self.action_buffer = []
-        d = self.delay
-        if d > 0:
-            self.set_delay(d)
+        self._new_episode()
         obs = _torch().empty((self.n_envs, self.n_modal), device=self.device, dtype=self.tdtype)
-        L.check(self._shard.lib.aoenv_reset_soft_modal(self._shard.h, C.c_void_p(obs.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_reset_soft_modal", obs, self._stream())
         self._mobs, self._surface = obs, "modal"
         return self._out(obs)
 
@@ -1670,29 +1579,7 @@ class BatchedAOEnv:
         then the command is updated -- the reference's modal env with ``delay = d`` is this with ``set_delay(d - 1)``
         (INTEGRATION.md)."""
         self._require_modal()
-        torch = _torch()
-        a = self._modal_tensor(action)
-        N = self.n_envs
-        obs = torch.empty((N, self.n_modal), device=self.device, dtype=self.tdtype)
-        reward = torch.empty((N,), device=self.device, dtype=self.tdtype)
-        strehl = torch.empty((N,), device=self.device, dtype=self.tdtype)
-        view = self.return_frame == "view"
-        fr = torch.empty((N, self.cam_res, self.cam_res), device=self.device, dtype=self.tdtype) if (self.return_frame and not view) else None
-        L.check(self._shard.lib.aoenv_step_modal(
-            self._shard.h, int(i), C.c_void_p(a.data_ptr()), C.c_void_p(obs.data_ptr()),
-            C.c_void_p(fr.data_ptr()) if fr is not None else None, C.c_void_p(reward.data_ptr()),
-            C.c_void_p(strehl.data_ptr()), C.c_void_p(self._stream())))
-        if view:
-            fr = self._frame_alias()
-        self._mobs, self._reward, self._strehl, self._frame = obs, reward, strehl, fr
-        self._surface = "modal"
-        self.SR.append(strehl)
-        if self.output == "numpy":
-            s = float(strehl[0])
-            return (self._out(obs), None if fr is None else self._out(fr), float(reward[0]), s, False, {"strehl": s})
-        if self._done is None:
-            self._done = torch.zeros(N, dtype=torch.bool, device=self.device)
-        return obs, fr, reward, strehl, self._done, {"strehl": strehl}
+        return self._step("aoenv_step_modal", i, self._modal_tensor(action), (self.n_modal,), "_mobs", "modal")
 
     def run_integrator_modal(self, i0: int, n_steps: int):
         """The modal integrator on the device, one gain per mode (and per env): ``n_steps`` iterations of ``a = g * obs;
@@ -1705,13 +1592,7 @@ class BatchedAOEnv:
             raise L.AoEnvError("no modal gains are set: call set_modal_gain() first")
         if self._mobs is None:
             raise L.AoEnvError("no modal observation yet: call reset_soft_modal() first")
-        self._require_surface("modal", "run_integrator_modal")
-        self._mobs = self._mobs.clone()                             # in place on a private copy, as run_integrator
-        self._reward, self._strehl = _torch().empty_like(self._reward), _torch().empty_like(self._strehl)
-        L.check(self._shard.lib.aoenv_run_integrator_modal(
-            self._shard.h, int(i0), int(n_steps), C.c_void_p(self._mobs.data_ptr()), None,
-            C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._strehl.data_ptr()), C.c_void_p(self._stream())))
-        return self._mobs, self._reward, self._strehl
+        return self._run_in_place("aoenv_run_integrator_modal", "run_integrator_modal", "_mobs", "modal", i0, n_steps)
 
     # -- wavefront modes (aoenv_set_wavefront_basis; the reference's opd2m @ tel.OPD[pupil]) ---------------------------------------
     def set_wavefront_basis(self, m2opd=None, opd2m=None, n_modes=None):
@@ -1723,13 +1604,13 @@ class BatchedAOEnv:
         p-th of ``np.where(tel.pupil == 1)``.  A new basis detaches a record.  Not part of ``get_state``: after ``set_state`` on a
         new env call this again."""
         table = resolve_wavefront_basis(m2opd, opd2m, n_modes, int(np.count_nonzero(self.pupil)))
-        cfg = L.AoWavefrontBasis(n_modes=table.shape[0], n_pix=table.shape[1], h_opd2m=table.ctypes.data_as(C.c_void_p))
-        L.check(self._shard.lib.aoenv_set_wavefront_basis(self._shard.h, C.byref(cfg), C.c_void_p(self._stream())))
+        cfg = L.AoWavefrontBasis(n_modes=table.shape[0], n_pix=table.shape[1], h_opd2m=L.address(table))
+        L.call(self._shard, "aoenv_set_wavefront_basis", cfg, self._stream())
         self._wf, self._wf_rec = table, None
 
     def clear_wavefront_basis(self):
         """No wavefront basis: the projector and its device memory are gone, a record is detached."""
-        L.check(self._shard.lib.aoenv_set_wavefront_basis(self._shard.h, None, C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_wavefront_basis", None, self._stream())
         self._wf = self._wf_rec = None
 
     @property
@@ -1750,7 +1631,7 @@ class BatchedAOEnv:
         if bits not in (L.WF_RESIDUAL, L.WF_ATMOSPHERE):
             raise ValueError("project_wavefront takes one of 'residual' and 'atmosphere'; record_wavefront takes both")
         out = _torch().empty((self.n_envs, self.n_wavefront_modes), device=self.device, dtype=self.tdtype)
-        L.check(self._shard.lib.aoenv_project_wavefront(self._shard.h, bits, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_project_wavefront", bits, out, self._stream())
         return self._out(out)
 
     def record_wavefront(self, i0: int, n_steps: int, what=("residual",)):
@@ -1765,14 +1646,14 @@ class BatchedAOEnv:
         if int(n_steps) < 1 or int(i0) < 0:
             raise ValueError("record_wavefront: i0 >= 0 and n_steps >= 1")
         rec = _torch().zeros((int(n_steps), W, self.n_envs, self.n_wavefront_modes), device=self.device, dtype=self.tdtype)
-        L.check(self._shard.lib.aoenv_set_wavefront_record(self._shard.h, bits, C.c_void_p(rec.data_ptr()), int(i0), int(n_steps)))
+        L.call(self._shard, "aoenv_set_wavefront_record", bits, rec, int(i0), int(n_steps))
         self._wf_rec = rec
         return rec
 
     def stop_wavefront_record(self):
         """Detaches the record; the loops run as without one.  Work already enqueued still writes the tensor: it stays alive with
         the caller's reference."""
-        L.check(self._shard.lib.aoenv_set_wavefront_record(self._shard.h, 0, None, 0, 0))
+        L.call(self._shard, "aoenv_set_wavefront_record", 0, None, 0, 0)
         self._wf_rec = None
 
     # -- science camera (aoenv_set_science; the reference's windowed tel.computePSF and its long exposure) ---------------------------
@@ -1788,13 +1669,13 @@ class BatchedAOEnv:
         does not restore it."""
         cfg = resolve_science(self.R, zero_padding, window, first_frame, log10, dft)
         c = L.AoScience(zero_padding=cfg["zero_padding"], window=cfg["window"], first_frame=cfg["first_frame"], flags=cfg["flags"],
-                        h_dft=None if cfg["dft"] is None else cfg["dft"].ctypes.data_as(C.c_void_p))
-        L.check(self._shard.lib.aoenv_set_science(self._shard.h, C.byref(c), C.c_void_p(self._stream())))
+                        h_dft=L.address(cfg["dft"]))
+        L.call(self._shard, "aoenv_set_science", c, self._stream())
         self._sci, self._le = cfg, None
 
     def clear_science(self):
         """No science camera: the table and its device memory are gone, a long exposure is detached."""
-        L.check(self._shard.lib.aoenv_set_science(self._shard.h, None, C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_set_science", None, self._stream())
         self._sci = self._le = None
 
     @property
@@ -1813,7 +1694,7 @@ class BatchedAOEnv:
     def _science_window(self, flat):
         W = self._sci["window"]
         out = _torch().empty((self.n_envs, W, W), device=self.device, dtype=self.tdtype)
-        L.check(self._shard.lib.aoenv_science_psf(self._shard.h, 1 if flat else 0, C.c_void_p(out.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_science_psf", 1 if flat else 0, out, self._stream())
         return out
 
     def science_psf(self, flat=False):
@@ -1834,9 +1715,7 @@ class BatchedAOEnv:
         acc = torch.zeros((self.n_envs, W, W), device=self.device, dtype=self.tdtype)
         acc_log = torch.zeros_like(acc) if self._sci["flags"] & L.SCI_LOG10 else None
         count = torch.zeros((self.n_envs,), device=self.device, dtype=torch.int32)
-        L.check(self._shard.lib.aoenv_set_science_accumulator(
-            self._shard.h, C.c_void_p(acc.data_ptr()), None if acc_log is None else C.c_void_p(acc_log.data_ptr()),
-            C.c_void_p(count.data_ptr())))
+        L.call(self._shard, "aoenv_set_science_accumulator", acc, acc_log, count)
         self._le = (acc, acc_log, count)
 
     def zero_long_exposure(self, env_ids=None):
@@ -1856,7 +1735,7 @@ class BatchedAOEnv:
     def stop_long_exposure(self):
         """Detaches the accumulators; the loops run as without them.  The read-outs keep answering from what was accumulated until
         the next ``start_long_exposure`` / ``set_science``."""
-        L.check(self._shard.lib.aoenv_set_science_accumulator(self._shard.h, None, None, None))
+        L.call(self._shard, "aoenv_set_science_accumulator", None, None, None)
 
     def _le_mean(self, acc, count):
         torch = _torch()
@@ -1970,7 +1849,7 @@ class BatchedAOEnv:
         self._per_env_clock = True
         self.measure()
         scratch = torch.empty_like(self._obs)
-        L.check(self._shard.lib.aoenv_reset_soft(self._shard.h, C.c_void_p(scratch.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_reset_soft", scratch, self._stream())
         sel = torch.as_tensor(given.astype(np.int64), device=self.device)
         rows = scratch.index_select(0, sel)
         self._obs = self._obs.index_copy(0, sel, rows)              # (out of place: the old tensor may be in a caller's hands)
@@ -1978,20 +1857,23 @@ class BatchedAOEnv:
 
     # -- the reference surface ------------------------------------------------------------------------------
     def _out(self, t):
-        if self.output == "numpy":
-            return t.detach().to("cpu", dtype=_torch().float64).numpy()[0]
-        return t
+        return _numpy64(t)[0] if self.output == "numpy" else t
 
-    def reset_soft(self):
-        """MAIN/OOPAOEnv/OOPAOEnv.py:82-86.  Under a library delay (``set_delay``) the delay line is cleared too, as
-        ``TimeDelayEnv.reset_soft`` refills its buffer (MAIN/PO4AO/util_simple.py:41-44)."""
+    def _new_episode(self):
+        """What both ``reset_soft`` do first: the reference's action buffer is emptied and a library delay re-armed, which
+        zeroes its line."""
         self.action_buffer = []
         d = self.delay
         if d > 0:
             self.set_delay(d)
+
+    def reset_soft(self):
+        """MAIN/OOPAOEnv/OOPAOEnv.py:82-86.  Under a library delay (``set_delay``) the delay line is cleared too, as
+        ``TimeDelayEnv.reset_soft`` refills its buffer (MAIN/PO4AO/util_simple.py:41-44)."""
+        self._new_episode()
         # a NEW tensor, like step(): the observation handed out by the previous step (a trainer may have kept it) is not written to
         obs = _torch().empty_like(self._obs)
-        L.check(self._shard.lib.aoenv_reset_soft(self._shard.h, C.c_void_p(obs.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_reset_soft", obs, self._stream())
         self._obs, self._surface = obs, "zonal"
         return self._out(obs)
 
@@ -2012,22 +1894,24 @@ class BatchedAOEnv:
         """MAIN/OOPAOEnv/OOPAOEnv.py:485-536.  Returns (obs, wfs_frame, reward, strehl, done, info).  Every call hands out NEW
         tensors, as the reference hands out new arrays (a replay buffer may keep them): the library writes straight into them, so
         there is no copy kernel behind the call -- only the allocator."""
+        return self._step("aoenv_step", i, self._action_tensor(action), (self.nActuator, self.nActuator), "_obs", "zonal")
+
+    def _step(self, entry: str, i, a, obs_shape: tuple, holder: str, surface: str):
+        """One frame of either surface: ``entry`` is the library's step, ``a`` the validated action, ``obs_shape`` one env's
+        observation, ``holder`` the attribute the env keeps it in and ``surface`` what ``_surface`` becomes.  New tensors for
+        every output (the library writes straight into them), the frame as ``return_frame`` says, then the bookkeeping."""
         torch = _torch()
-        a = self._action_tensor(action)
-        N, A_ = self.n_envs, self.nActuator
-        obs = torch.empty((N, A_, A_), device=self.device, dtype=self.tdtype)
+        N = self.n_envs
+        obs = torch.empty((N,) + obs_shape, device=self.device, dtype=self.tdtype)
         reward = torch.empty((N,), device=self.device, dtype=self.tdtype)
         strehl = torch.empty((N,), device=self.device, dtype=self.tdtype)
         view = self.return_frame == "view"
         fr = torch.empty((N, self.cam_res, self.cam_res), device=self.device, dtype=self.tdtype) if (self.return_frame and not view) else None
-        L.check(self._shard.lib.aoenv_step(
-            self._shard.h, int(i), C.c_void_p(a.data_ptr()), C.c_void_p(obs.data_ptr()),
-            C.c_void_p(fr.data_ptr()) if fr is not None else None, C.c_void_p(reward.data_ptr()),
-            C.c_void_p(strehl.data_ptr()), C.c_void_p(self._stream())))
+        L.call(self._shard, entry, int(i), a, obs, fr, reward, strehl, self._stream())
         if view:
             fr = self._frame_alias()
-        self._obs, self._reward, self._strehl, self._frame = obs, reward, strehl, fr
-        self._surface = "zonal"
+        setattr(self, holder, obs)
+        self._reward, self._strehl, self._frame, self._surface = reward, strehl, fr, surface
         self.SR.append(strehl)
         if self.output == "numpy":
             s = float(strehl[0])
@@ -2040,14 +1924,14 @@ class BatchedAOEnv:
     def fused_step(self) -> bool:
         """True when ``step`` runs as ONE kernel per step (float32 Shack-Hartmann inside the fused kernel's envelope, see
         aoenv_fused_step_active in include/aoenv.h); False: the batched kernels (every geometry, float64, the Pyramid)."""
-        return bool(self._shard.lib.aoenv_fused_step_active(self._shard.h))
+        return bool(L.invoke(self._shard, "aoenv_fused_step_active"))      # (an answer, not a status: no check)
 
     def _frame_alias(self):
         """wfs.cam.frame of every env as a tensor that ALIASES the library's buffer (no copy: 14.7 MB per step at 256 envs of the
         8 m geometry); the next measurement overwrites it.  ``return_frame="view"``."""
         if getattr(self, "_frame_view", None) is None:
             ptr, nbytes = C.c_void_p(), C.c_size_t()
-            L.check(self._shard.lib.aoenv_buffer(self._shard.h, L.B_FRAME, C.byref(ptr), C.byref(nbytes)))
+            L.call(self._shard, "aoenv_buffer", L.B_FRAME, C.byref(ptr), C.byref(nbytes))
 
             class _Iface:
                 pass
@@ -2063,28 +1947,32 @@ class BatchedAOEnv:
         have produced the current observation.  Under a library delay (``set_delay``) ``gainCL * obs`` goes into the delay line
         instead (one small launch per step) and the step applies the action formed ``delay`` steps earlier."""
         g = float(self.gainCL if gain is None else gain)
-        self._require_surface("zonal", "run_integrator")
-        # the loop runs in place on the observation: on private copies, never on tensors step() / reset_soft() have handed out
-        self._obs = self._obs.clone()
+        return self._run_in_place("aoenv_run_integrator", "run_integrator", "_obs", "zonal", i0, n_steps, g)
+
+    def _run_in_place(self, entry: str, who: str, holder: str, surface: str, i0, n_steps, *gain):
+        """An integrator loop of the library on either surface (``gain``: what ``entry`` takes between the step count and the
+        observation).  It runs in place on the observation: on private copies, never on tensors a step or a reset has handed
+        out."""
+        self._require_surface(surface, who)
+        obs = getattr(self, holder).clone()
+        setattr(self, holder, obs)
         self._reward, self._strehl = _torch().empty_like(self._reward), _torch().empty_like(self._strehl)
-        L.check(self._shard.lib.aoenv_run_integrator(
-            self._shard.h, int(i0), int(n_steps), g, C.c_void_p(self._obs.data_ptr()), None,
-            C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._strehl.data_ptr()), C.c_void_p(self._stream())))
-        return self._obs, self._reward, self._strehl
+        L.call(self._shard, entry, int(i0), int(n_steps), *gain, obs, None, self._reward, self._strehl, self._stream())
+        return obs, self._reward, self._strehl
+
+    def _filter_factors(self, Fr, Fl):
+        """``(Fr [K, A] then Fl [A, K] in one contiguous float64 vector, K)``: the factored filter as the library is handed it."""
+        Fr, Fl = np.asarray(Fr, dtype=np.float64), np.asarray(Fl, dtype=np.float64)
+        if Fr.ndim != 2 or Fr.shape[1] != self.nValidAct or Fl.shape != Fr.shape[::-1]:
+            raise ValueError(f"Fr must be [K, {self.nValidAct}] and Fl [{self.nValidAct}, K], got {Fr.shape} and {Fl.shape}")
+        return np.ascontiguousarray(np.concatenate([Fr.reshape(-1), Fl.reshape(-1)])), int(Fr.shape[0])
 
     def set_noise_filter(self, Fr=None, Fl=None):
         """The filter of ``rollout``'s exploration noise in factored form, ``F = Fl @ Fr`` with ``Fr`` [K, A] and ``Fl`` [A, K]
         (``set_params`` uploads ``pinv(M2C_CL)`` and ``M2C_CL``, the factors of ``self.F``); no arguments: no filter, ``n = z``,
         the reference's ``F = 1`` before ``set_params``.  ``self.F`` and ``sample_noise`` are not touched."""
-        sh = self._shard
-        if Fr is None or Fl is None:
-            L.check(sh.lib.aoenv_set_noise_filter(sh.h, None, 0, C.c_void_p(self._stream())))
-            return
-        Fr, Fl = np.asarray(Fr, dtype=np.float64), np.asarray(Fl, dtype=np.float64)
-        if Fr.ndim != 2 or Fr.shape[1] != self.nValidAct or Fl.shape != Fr.shape[::-1]:
-            raise ValueError(f"Fr must be [K, {self.nValidAct}] and Fl [{self.nValidAct}, K], got {Fr.shape} and {Fl.shape}")
-        fac = np.ascontiguousarray(np.concatenate([Fr.reshape(-1), Fl.reshape(-1)]))
-        L.check(sh.lib.aoenv_set_noise_filter(sh.h, fac.ctypes.data_as(C.c_void_p), int(Fr.shape[0]), C.c_void_p(self._stream())))
+        fac, rank = (None, 0) if Fr is None or Fl is None else self._filter_factors(Fr, Fl)
+        L.call(self._shard, "aoenv_set_noise_filter", fac, rank, self._stream())
 
     def rollout(self, i0: int, n_steps: int, sigma, gain=None, seed=None, sigma_env=None):
         """An exploration episode as a replay-ready trajectory, on the device (the warm-up loop of MAIN/PO4AO/mbrl.py:64-89):
@@ -2098,11 +1986,11 @@ class BatchedAOEnv:
         ``gainCL`` and may be 0.  The env is left as ``n_steps`` calls of ``step`` leave it (last obs / reward / strehl, ``SR``,
         the frame)."""
         g = float(self.gainCL if gain is None else gain)
-        return self._recorded_rollout(self._shard.lib.aoenv_run_rollout, i0, n_steps, sigma, g, seed, sigma_env, ())
+        return self._recorded_rollout("aoenv_run_rollout", i0, n_steps, sigma, g, seed, sigma_env, ())
 
     def _recorded_rollout(self, entry, i0, n_steps, sigma, g, seed, sigma_env, extra):
         """The buffers, the call and the env-state bookkeeping ``rollout`` and ``policy_rollout`` share.  ``entry``: the library's
-        loop; ``extra``: the device pointers it takes between the frame and the stream."""
+        loop; ``extra``: the device tensors it takes between the frame and the stream."""
         torch = _torch()
         K, N, A_ = int(n_steps), self.n_envs, self.nActuator
         if K < 0:
@@ -2127,12 +2015,9 @@ class BatchedAOEnv:
         fr = torch.empty((N, self.cam_res, self.cam_res), device=self.device, dtype=self.tdtype) \
             if (K > 0 and self.return_frame and not view) else None
         cfg = L.AoRollout(i0=int(i0), n_steps=K, env_index_offset=int(self.env_index_offset), reserved=0, gain=g,
-                          sigma=0.0 if sig is not None else float(sigma), d_sigma_env=None if sig is None else sig.data_ptr(),
-                          seed=sd & 0xFFFFFFFFFFFFFFFF)
+                          sigma=0.0 if sig is not None else float(sigma), d_sigma_env=L.address(sig), seed=sd & 0xFFFFFFFFFFFFFFFF)
         if K > 0:                                                  # (no steps: nothing to launch, and empty tensors have no address)
-            L.check(entry(
-                self._shard.h, C.byref(cfg), C.c_void_p(obs.data_ptr()), C.c_void_p(action.data_ptr()), C.c_void_p(reward.data_ptr()),
-                C.c_void_p(strehl.data_ptr()), C.c_void_p(fr.data_ptr()) if fr is not None else None, *extra, C.c_void_p(self._stream())))
+            L.call(self._shard, entry, cfg, obs, action, reward, strehl, fr, *extra, self._stream())
         self.explore_seed = sd                                     # (after the call: a refused rollout changes nothing)
         if K > 0:
             if view:
@@ -2141,7 +2026,7 @@ class BatchedAOEnv:
             self._obs, self._reward, self._strehl, self._frame = obs[K].clone(), reward[K - 1].clone(), strehl[K - 1].clone(), fr
             self.SR.extend(strehl.clone().unbind(0))
         if self.output == "numpy":
-            return Rollout(*(t.detach().to("cpu", dtype=torch.float64).numpy()[:, 0] for t in (obs, action, reward, strehl)))
+            return Rollout(*(_numpy64(t)[:, 0] for t in (obs, action, reward, strehl)))
         return Rollout(obs, action, reward, strehl)
 
     # -- the trainer's policy inside the library (MAIN/PO4AO/conv_models_simple.py:56-111, mbrl.py:72-74) ----------------------
@@ -2151,9 +2036,8 @@ class BatchedAOEnv:
         projection on the controlled modes: ``True`` the factors ``pinv(M2C_CL), M2C_CL`` of ``self.F`` (after ``set_params``),
         ``None`` no projection, a pair ``(Fr [K, A], Fl [A, K])`` custom factors.  ``clamp``: the reference clamps to [-1, 1].
         ``path=1`` forces the general kernel (parity tests)."""
-        sh = self._shard
         if policy is None:
-            L.check(sh.lib.aoenv_set_policy(sh.h, None, C.c_void_p(self._stream())))
+            L.call(self._shard, "aoenv_set_policy", None, self._stream())
             self.policy_n_history = None
             return
         w = policy_arrays(policy)
@@ -2161,16 +2045,12 @@ class BatchedAOEnv:
             F = (np.linalg.pinv(self.M2C_CL), self.M2C_CL)
         proj, rank = None, 0
         if F is not None and F is not False:
-            Fr, Fl = (np.asarray(x, dtype=np.float64) for x in F)
-            if Fr.ndim != 2 or Fr.shape[1] != self.nValidAct or Fl.shape != Fr.shape[::-1]:
-                raise ValueError(f"Fr must be [K, {self.nValidAct}] and Fl [{self.nValidAct}, K], got {Fr.shape} and {Fl.shape}")
-            proj, rank = np.ascontiguousarray(np.concatenate([Fr.reshape(-1), Fl.reshape(-1)])), int(Fr.shape[0])
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+            Fr, Fl = F
+            proj, rank = self._filter_factors(Fr, Fl)
         cfg = L.AoPolicy(n_history=w["n_history"], n_filt=w["n_filt"], proj_rank=rank, path=int(path),
-                         negative_slope=w["negative_slope"], clamp_abs=float(clamp), h_w1=ptr(w["w1"]), h_b1=ptr(w["b1"]),
-                         h_w2=ptr(w["w2"]), h_b2=ptr(w["b2"]), h_w3=ptr(w["w3"]), h_b3=ptr(w["b3"]),
-                         h_proj=None if proj is None else ptr(proj))
-        L.check(sh.lib.aoenv_set_policy(sh.h, C.byref(cfg), C.c_void_p(self._stream())))
+                         negative_slope=w["negative_slope"], clamp_abs=float(clamp), h_proj=L.address(proj),
+                         **{f"h_{key}": L.address(w[key]) for key in ("w1", "b1", "w2", "b2", "w3", "b3")})
+        L.call(self._shard, "aoenv_set_policy", cfg, self._stream())
         self.policy_n_history = int(w["n_history"])
 
     def _history_tensor(self, t, name, copy):
@@ -2187,7 +2067,7 @@ class BatchedAOEnv:
 
     def _require_policy(self):
         if self.policy_n_history is None:
-            L.check(self._shard.lib.aoenv_policy_forward(self._shard.h, None, None, None, None, None))   # the library's own refusal
+            L.call(self._shard, "aoenv_policy_forward", None, None, None, None, None)   # the library's own refusal
 
     def policy_action(self, obs, past_obs=None, past_act=None):
         """``policy(obs, cat([past_obs, past_act], dim=1))`` (mbrl.py:73) by the library's kernels: ``obs`` [N, a, a], ``past_obs`` and
@@ -2198,8 +2078,7 @@ class BatchedAOEnv:
         o = self._action_tensor(obs)
         po, pa = self._history_tensor(past_obs, "past_obs", False), self._history_tensor(past_act, "past_act", False)
         act = torch.empty_like(o)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        L.check(self._shard.lib.aoenv_policy_forward(self._shard.h, p(o), p(po), p(pa), p(act), C.c_void_p(self._stream())))
+        L.call(self._shard, "aoenv_policy_forward", o, po, pa, act, self._stream())    # (H = 1: the empty windows go as null)
         return self._out(act)
 
     def policy_rollout(self, i0: int, n_steps: int, sigma=0.0, past=None, seed=None, sigma_env=None):
@@ -2211,10 +2090,9 @@ class BatchedAOEnv:
         at ``sigma == 0`` (the reference's behaviour) every action is bit for bit ``policy_action`` of its windows."""
         self._require_policy()
         po, pa = (self._history_tensor(None if past is None else past[j], name, True) for j, name in ((0, "past[0]"), (1, "past[1]")))
-        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
-        tr = self._recorded_rollout(self._shard.lib.aoenv_run_policy_rollout, i0, n_steps, sigma, 0.0, seed, sigma_env, (p(po), p(pa)))
+        tr = self._recorded_rollout("aoenv_run_policy_rollout", i0, n_steps, sigma, 0.0, seed, sigma_env, (po, pa))
         if self.output == "numpy":
-            po, pa = (t.detach().to("cpu", dtype=_torch().float64).numpy()[0] for t in (po, pa))
+            po, pa = (_numpy64(t)[0] for t in (po, pa))
         return tr, (po, pa)
 
     # -- checkpoint / resume (SURVEY.md section 5: env state = screens, sub-pixel accumulators, ring RNG, dm coefs) --------
@@ -2284,10 +2162,10 @@ class BatchedAOEnv:
         d = int(state.get("delay", 0))                               # (a state without the keys: no delay)
         self.set_delay(d)
         if d > 0:
-            line = np.ascontiguousarray(state["delay_line"], dtype=np.float32 if self.dtype == "f32" else np.float64)
+            line = np.ascontiguousarray(state["delay_line"], dtype=_NP_DT[self.dtype])
             if line.shape != (d, self.n_envs, self.nActuator, self.nActuator):
                 raise ValueError(f"delay_line must have shape ({d}, {self.n_envs}, {self.nActuator}, {self.nActuator}), got {line.shape}")
-            L.check(sh.lib.aoenv_set_delay_line(sh.h, line.ctypes.data_as(C.c_void_p), line.nbytes, C.c_void_p(st)))
+            L.call(sh, "aoenv_set_delay_line", line, line.nbytes, st)
         self._obs = _torch().as_tensor(state["obs"]).to(device=self.device, dtype=self.tdtype).clone()   # (never into a handed-out tensor)
         self._surface, self._mobs = "zonal", None                    # (the state carries the zonal observation alone)
 
@@ -2315,8 +2193,7 @@ class BatchedAOEnv:
             if tuple(tensor.shape) != (self.n_envs,) or tensor.dtype != self.tdtype or not tensor.is_cuda or not tensor.is_contiguous():
                 raise ValueError(f"the return accumulator must be a contiguous cuda {self.tdtype} tensor of shape ({self.n_envs},)")
         self._returns = tensor
-        L.check(self._shard.lib.aoenv_set_return_accumulator(
-            self._shard.h, None if tensor is None else C.c_void_p(tensor.data_ptr())))
+        L.call(self._shard, "aoenv_set_return_accumulator", tensor)
 
     def calculate_strehl_AVG(self):
         """MAIN/OOPAOEnv/OOPAOEnv.py:538-546: (mean, std) over the episode, then clears the list."""
