@@ -338,6 +338,34 @@ int aoenv_set_disturbance(AoEnv* env, const AoDisturbance* cfg, void* stream);  
 int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* stream);
 int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream);
 
+/* Replaces: a MisRegistration with rotationAngle != 0 on the mirror of one env (OOPAO/DeformableMirror.py:326-351 moves the actuator
+ * positions, :494-510 evaluates the Gaussians).  A rotated grid is not Gy C Gx^T, but at anamorphosis angle 0 every actuator's
+ * Gaussian is still a product of a y factor and an x factor, so env e's surface is
+ *     S_e[y][x] = sum_k c_e[k] py_e[y][k] px_e[x][k],   k over the n_valid_act valid actuators.
+ * h_py, h_px: [n_env][R][n_valid_act] float64 (rlao_amd.calib.dm_actuator_pairs computes them; a dead actuator is a zero column).
+ * While pairs are in force the shard forms the surface ahead of the phase kernel, as a dense mirror's shard does, in one launch
+ * wherever the command changes: on the fp32 matrix cores for float32 shards (k_dm_pairs_mfma), as one fma chain per pixel for
+ * float64 shards and under AOENV_PATH_DM_PAIRS_GENERAL (k_dm_pairs).  Both add c[k] py[y][k] * px[x][k] in ascending k: the order
+ * depends on (R, n_valid_act) alone, there are no atomics, and an env has the same bits in any shard and at any place in it.  The
+ * shard then runs the batched kernels (k_phase<T> reads the surface); aoenv_fused_step_active is 0 until the pairs are cleared.
+ * Device memory of a set (rlao_amd/csrc/dm_pairs.hpp): n_env times
+ *     2 R A sizeof(dtype) + 2 (R pad 128) 4 ga_stride sizeof(float) + R^2 sizeof(dtype),   ga_stride = max(8, A / 4 pad 4)
+ * (the tables in the env dtype, the two float32 operand tables, the surface).  Both pointers NULL: the pairs are cleared and the
+ * memory freed; the shard launches what it launched before.
+ * Configuration like the per-env factor tables: copied before the call returns (the stream is waited for once), not loop state,
+ * not in the checkpoint buffers; aoenv_reset_envs and aoenv_new_screens* leave them alone.
+ * Refused, with nothing changed: exactly one pointer null, a non-finite entry (the index is reported), a shard with
+ * dm_separable == 0, per-env factor tables in force (aoenv_set_dm_env: clear them first; aoenv_set_dm_env with tables is likewise
+ * refused while pairs are in force), an allocation that fails.
+ * aoenv_get_dm_pairs fills h_py, h_px with the values as held: rounded to the env dtype, widened to float64. */
+int aoenv_set_dm_pairs(AoEnv* env, const double* h_py, const double* h_px, void* stream);
+int aoenv_get_dm_pairs(AoEnv* env, double* h_py, double* h_px, void* stream);
+
+/* Replaces: reading dm.OPD.  h_surface [n_env][R*R]: the mirror surface, in metres, of the command currently held
+ * (AOENV_B_COEFS, without a disturbance), formed first on the stream.  For shards that keep a surface buffer: a dense mirror
+ * (dm_separable == 0) and actuator factor pairs.  Refused on a shard that forms its surface inside the phase kernel. */
+int aoenv_get_dm_surface(AoEnv* env, double* h_surface, void* stream);
+
 /* Replaces: OOPAOEnvRazor.change_mag (MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647: source.nPhoton = zeroPoint 10^(-0.4 mag), then
  * source * tel * wfs) and the assignment env.wfs.threshold_cog = t, as the noise study makes them between its serial runs
  * (MAIN/OOPAOEnvRazor/integrator_threshold.py:34-106: six thresholds for each of six magnitudes) -- for the envs of ONE shard: every
@@ -713,7 +741,7 @@ enum AoOption {
                                  whole-pixel round or crosses a pixel in that one (two steps, one workgroup per env, nothing read back
                                  from global memory in between; bit-identical results).  0: one launch per step */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL and AOENV_PATH_SCI_GENERAL also keeps the shard off the fused step
+                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL, AOENV_PATH_SCI_GENERAL and AOENV_PATH_DM_PAIRS_GENERAL also keeps the shard off the fused step
                                  kernel; other bits are rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
@@ -732,6 +760,9 @@ enum AoPath {
     AOENV_PATH_SCI_GENERAL = 16384,    /* the science window (aoenv_science_psf, the long exposure) as fma chains on float32 shards
                                           too, instead of the matrix-core kernel.  Like AOENV_PATH_WF_GENERAL it touches nothing
                                           inside the step and leaves the shard on the fused step kernel */
+    AOENV_PATH_DM_PAIRS_GENERAL = 32768, /* the surface of actuator factor pairs (aoenv_set_dm_pairs) as one fma chain per pixel on float32
+                                          shards too, instead of the matrix-core kernel.  It touches nothing of a shard without pairs,
+                                          which stays on the fused step kernel */
     AOENV_PATH_SH_PLAIN = 4096         /* the general instantiation of the fused step kernel (run-time camera and trig tests, the
                                           pixel-by-pixel stage A epilogue) and the plain C++ lenslet transform, there and in the
                                           batched spots kernel, instead of the forms specialised for the launch and the register-pair

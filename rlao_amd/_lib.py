@@ -29,6 +29,7 @@ MAX_DELAY = 8                                                      # AOENV_MAX_D
 # enum AoPath: bits of OPT_FORCE_PATH
 PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN, PATH_WF_GENERAL = 256, 512, 1024, 2048, 4096, 8192
 PATH_SCI_GENERAL = 16384
+PATH_DM_PAIRS_GENERAL = 32768
 SCI_LOG10 = 1                                                      # enum AoScienceFlag
 WF_RESIDUAL, WF_ATMOSPHERE = 1, 2                                  # enum AoWavefront
 MAX_WF_MODES = 1024                                                # AOENV_MAX_WF_MODES
@@ -118,6 +119,9 @@ EXPORTS = {
     "aoenv_set_wavefront_record": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "aoenv_set_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_dm_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_dm_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_dm_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_dm_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_flux_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_flux_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_threshold_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

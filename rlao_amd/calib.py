@@ -250,7 +250,8 @@ class AtmosphereTables:
 # Deformable mirror
 # ------------------------------------------------------------------------------------------------------
 ROTATION_REFUSAL = ("a rotated actuator grid is not a product of two factors gy (x) gx: the separable-DM kernels cannot show it "
-                    "(MisReg_rotationAngle / rotation_angle must be 0)")
+                    "(MisReg_rotationAngle / rotation_angle must be 0); a mirror rotated AFTER calibration is "
+                    "BatchedAOEnv.set_dm_rotation (actuator factor pairs, calib.dm_actuator_pairs)")
 
 
 def _dm_axes(p: AOParams, ns: int, shift_x=0, shift_y=0, radial_scaling=0, tangential_scaling=0):
@@ -283,6 +284,35 @@ def dm_factors(p: AOParams, shift_x=0, shift_y=0, radial_scaling=0, tangential_s
     gx = np.exp(-((pix[:, None] - cx[None, :]) ** 2) / (2 * wx ** 2))     # [R, nAct]
     gy = np.exp(-((pix[:, None] - cy[None, :]) ** 2) / (2 * wy ** 2))
     return gx, gy
+
+
+def dm_actuator_pairs(p: AOParams, shift_x=0, shift_y=0, rotation_angle=0, radial_scaling=0, tangential_scaling=0,
+                      n_subap: int | None = None, pitch: float | None = None):
+    """The actuator factor pairs ``(py, px)``, float64 ``[R, nValidAct]`` each, of a Cartesian DM mis-registered by a rotation
+    [degrees], a shift [m] and the two scalings: the influence function of valid actuator k is ``py[:, k] (x) px[:, k]``, i.e.
+    ``modes[y R + x, k] = py[y, k] px[x, k]``.  A rotated grid is no longer ``gy (x) gx`` with one column per grid line, but at
+    ``anamorphosisAngle = 0`` the cross term ``b`` of OOPAO/DeformableMirror.py:507 vanishes and every actuator's Gaussian stays a
+    product of an x and a y factor around its own rotated centre.  Restated from :326-346 and :494-510 with every quirk
+    ``dm_factors`` documents (scalings swapped between positions and widths, the shift subtracted, ``u0 = R / 2 + xIF R / D`` on
+    the grid ``linspace(0, 1, R) R``); the rotation (:480-483) comes after the anamorphosis and before the shift (:331-338).  The
+    valid actuators are those of the NOMINAL grid (:327-328 selects with ``validAct`` before anything moves): ``nValidAct``,
+    ``act_idx`` and a reconstructor do not change.  At ``rotation_angle = 0`` column k equals column ``iy_k`` / ``ix_k`` of
+    ``dm_factors``' ``gy`` / ``gx`` bit for bit."""
+    ns = p.nSubaperture if n_subap is None else int(n_subap)
+    R, D = p.resolution, p.diameter
+    act_idx = DMTables(p, pitch=pitch, n_subap=ns).act_idx
+    x = np.linspace(-D / 2, D / 2, ns + 1)
+    pix, _, _, wx, wy = _dm_axes(p, ns, 0, 0, radial_scaling, tangential_scaling)
+    xa = x[act_idx % (ns + 1)] * (1 + tangential_scaling)              # anamorphosis at angle 0 (:487-490, slots as called at :331)
+    ya = x[act_idx // (ns + 1)] * (1 + radial_scaling)
+    t = float(rotation_angle) * np.pi / 180
+    xr = xa * np.cos(t) - ya * np.sin(t)                               # :480-483
+    yr = ya * np.cos(t) + xa * np.sin(t)
+    centre_x = R / 2 + (xr - shift_x) * R / D
+    centre_y = R / 2 + (yr - shift_y) * R / D
+    px = np.exp(-((pix[:, None] - centre_x[None, :]) ** 2) / (2 * wx ** 2))     # [R, nValidAct]
+    py = np.exp(-((pix[:, None] - centre_y[None, :]) ** 2) / (2 * wy ** 2))
+    return py, px
 
 
 class DMTables:

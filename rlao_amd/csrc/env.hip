@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "delay.hpp"
 #include "dev_block.hpp"
+#include "dm_pairs.hpp"
 #include "dm_tables.hpp"
 #include "detector.hpp"
 #include "disturb.hpp"
@@ -219,6 +220,19 @@ struct AoEnv {
         void *gx = nullptr, *gy = nullptr, *gxt = nullptr;
         float *gxa = nullptr, *gya = nullptr;
     } dm_env;
+    // per-env actuator factor pairs (aoenv_set_dm_pairs, dm_pairs.hpp): E blocks of both layouts of py / px and the surface buffer
+    // [E][R*R] they are multiplied into, in ONE block of its own (clearing frees it).  While `on` the surface is formed ahead of the
+    // phase kernel, like a dense mirror's.
+    struct DmPairs {
+        bool on = false;
+        Block mem;
+        void *pyt = nullptr, *pxt = nullptr, *opd = nullptr;
+        float *pya = nullptr, *pxa = nullptr;
+    } dm_pairs;
+    PairsLayout pairs_layout() const { PairsLayout l; l.R = R; l.A = A; return l; }
+    // this shard forms its DM surface ahead of the phase kernel (refresh_dense_dm), which reads it from surface()
+    bool dm_surface_ahead() const { return !c.dm_separable || dm_pairs.on; }
+    void* surface() const { return dm_pairs.on ? dm_pairs.opd : dm_opd; }
     // per-env guide stars (aoenv_set_flux_env / aoenv_set_threshold_env, star_env.hpp): [E] each in the env dtype, a block of its
     // own each (NULL frees it); absent = null, and the kernels are then handed null pointers
     struct StarDev {
@@ -701,7 +715,7 @@ void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_
 template <typename T>
 int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int store_phase = 1) {
     AO_TRY(refresh_minmax<T>(env, st));
-    if (env->use_coefs_img && env->c.dm_separable) {               // ELT-size DMs: once per env instead of once per tile
+    if (env->use_coefs_img && !env->dm_surface_ahead()) {          // ELT-size DMs: once per env instead of once per tile
         if constexpr (std::is_same<T, float>::value) {
             if (env->dm_rows)                                       // Gy C on the matrix cores, in operand layout
                 AO_TRY(launch_dm_rows(env->as<float>(env->cmd()), env->act_idx, env->dm_env.on ? env->dm_env.gya : env->gya,
@@ -795,10 +809,29 @@ int run_wfs(AoEnv* env, hipStream_t st) {
     return 0;
 }
 
+// The one place that forms the DM surface of a shard that forms it ahead of the phase kernel (AoEnv::dm_surface_ahead).
+// Actuator factor pairs: S_e = (Py_e diag(c_e)) Px_e^T per env (dm_pairs_kernels.hip).
 // dm.OPD = modes @ coefs for a dense (non-separable, e.g. two chained mirrors) DM: [E][R^2] = coefs [E][A] . modes [R^2][A]^T
 template <typename T>
 int refresh_dense_dm(AoEnv* env, hipStream_t st) {
-    if (env->c.dm_separable) return 0;
+    if (!env->dm_surface_ahead()) return 0;
+    if (env->dm_pairs.on) {
+        const AoEnv::DmPairs& dp = env->dm_pairs;
+        const PairsLayout pl = env->pairs_layout();
+        PairsArgs<T> a{};
+        a.coefs = env->as<T>(env->cmd());
+        a.pyt = env->as<T>(dp.pyt);
+        a.pxt = env->as<T>(dp.pxt);
+        a.pya = dp.pya;
+        a.pxa = dp.pxa;
+        a.out = env->as<T>(dp.opd);
+        a.R = env->R;
+        a.A = env->A;
+        a.ga_stride = pl.ga_stride();
+        a.t_env = pl.t_elems();
+        a.ga_env = pl.ga_elems();
+        return launch_dm_pairs<T>(a, env->E, (env->force_path & AOENV_PATH_DM_PAIRS_GENERAL) != 0, st);
+    }
     if (sizeof(T) == 4 && env->use_mfma)                           // one K slice: the product lands in dm_opd directly
         return launch_gemm_nt_mfma(reinterpret_cast<const float*>(env->cmd()), reinterpret_cast<const float*>(env->modes),
                                    reinterpret_cast<float*>(env->dm_opd), env->E, env->R * env->R, env->A, env->A, env->A, 1, st);
@@ -893,8 +926,8 @@ template <typename T>
 bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
-    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && env->c.dm_separable && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL)) == 0 &&
+    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && env->n_modes > 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -926,8 +959,8 @@ void fill_phase_args(AoEnv* env, PhaseArgs& pa, PhaseBuffers<T>& pb, int update_
     pb.opd_atm = env->as<T>(env->opd_atm);
     pb.coefs = env->as<T>(env->cmd());
     pb.coefs_img = env->use_coefs_img && env->coefs_img ? env->as<T>(env->coefs_img) : nullptr;
-    pb.s1a = env->use_coefs_img && env->c.dm_separable ? env->dm_rows : nullptr;
-    pb.dm_opd = env->c.dm_separable ? nullptr : env->as<T>(env->dm_opd);
+    pb.s1a = env->use_coefs_img && !env->dm_surface_ahead() ? env->dm_rows : nullptr;
+    pb.dm_opd = env->dm_surface_ahead() ? env->as<T>(env->surface()) : nullptr;
     const AoEnv::DmEnv& de = env->dm_env;                          // every env its own mirror: its tables, a block apart
     const DmLayout dl = env->dm_layout();
     pb.gx = env->as<T>(de.on ? de.gx : env->gx);
@@ -2459,6 +2492,8 @@ int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* s
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!h_gx != !h_gy) return fail("aoenv_set_dm_env: one of gx / gy is null (both, or neither for the shared tables)");
     if (h_gx && !env->c.dm_separable) return fail("aoenv_set_dm_env: this shard's DM is dense (dm_separable == 0): it has no factors");
+    if (h_gx && env->dm_pairs.on)
+        return fail("aoenv_set_dm_env: actuator factor pairs are in force (aoenv_set_dm_pairs): clear them first (two NULLs)");
     if (!h_gx) {
         if (env->dm_env.mem) AO_HIP(hipStreamSynchronize(st));
         env->dm_env = AoEnv::DmEnv{};
@@ -2479,6 +2514,91 @@ int aoenv_get_dm_env(AoEnv* env, double* h_gx, double* h_gy, void* stream) {
     const size_t n = (size_t)env->E * env->dm_layout().g_elems();
     AO_TRY(download_real(env, h_gx, env->dm_env.gx, n));
     return download_real(env, h_gy, env->dm_env.gy, n);
+}
+
+// ---- per-env actuator factor pairs (dm_pairs.hpp) ----------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+template <typename T>
+int set_dm_pairs_t(AoEnv* env, const double* h_py, const double* h_px, hipStream_t st) {
+    const PairsLayout pl = env->pairs_layout();
+    const size_t E = (size_t)env->E;
+    const size_t bt = E * pl.t_elems() * sizeof(T), ba = E * pl.ga_elems() * sizeof(float), bo = E * env->R * env->R * sizeof(T);
+    const std::initializer_list<size_t> parts = {bt, bt, ba, ba, bo};
+    PairsHostTables<T> h;
+    pairs_relayout<T>(pl, env->E, h_py, h_px, h);
+    AO_HIP(hipStreamSynchronize(st));                              // a step in flight reads the tables in place
+    AoEnv::DmPairs& dp = env->dm_pairs;
+    if (!dp.mem) {
+        if (dp.mem.alloc(parts, false))
+            return fail("aoenv_set_dm_pairs: no device memory for %zu bytes of actuator factor pairs (%d envs x %zu, and the surfaces)", dev_layout(parts).total, env->E, pl.bytes(sizeof(T)));
+        dp.pyt = dp.mem.part(0);
+        dp.pxt = dp.mem.part(1);
+        dp.pya = static_cast<float*>(dp.mem.part(2));
+        dp.pxa = static_cast<float*>(dp.mem.part(3));
+        dp.opd = dp.mem.part(4);
+    }
+    dp.on = false;                                                 // (a failed copy leaves no half-written mirror in use)
+    AO_HIP(hipMemcpy(dp.pyt, h.pyt.data(), h.pyt.size() * sizeof(T), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(dp.pxt, h.pxt.data(), h.pxt.size() * sizeof(T), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(dp.pya, h.pya.data(), h.pya.size() * sizeof(float), hipMemcpyHostToDevice));
+    AO_HIP(hipMemcpy(dp.pxa, h.pxa.data(), h.pxa.size() * sizeof(float), hipMemcpyHostToDevice));
+    dp.on = true;
+    return refresh_dense_dm<T>(env, st);                           // the surface of the command held, on the new mirror
+}
+template <typename T>
+int get_dm_pairs_t(AoEnv* env, double* h_py, double* h_px) {
+    const PairsLayout pl = env->pairs_layout();
+    const size_t n = (size_t)env->E * pl.t_elems();
+    std::vector<T> ty(n), tx(n);
+    AO_HIP(hipMemcpy(ty.data(), env->dm_pairs.pyt, n * sizeof(T), hipMemcpyDeviceToHost));
+    AO_HIP(hipMemcpy(tx.data(), env->dm_pairs.pxt, n * sizeof(T), hipMemcpyDeviceToHost));
+    for (int e = 0; e < env->E; ++e) {
+        pairs_read_t<T>(pl, ty.data() + (size_t)e * pl.t_elems(), h_py + (size_t)e * pl.t_elems());
+        pairs_read_t<T>(pl, tx.data() + (size_t)e * pl.t_elems(), h_px + (size_t)e * pl.t_elems());
+    }
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int aoenv_set_dm_pairs(AoEnv* env, const double* h_py, const double* h_px, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_py != !h_px) return fail("aoenv_set_dm_pairs: one of py / px is null (both, or neither to clear the pairs)");
+    if (!h_py) {
+        if (env->dm_pairs.mem) AO_HIP(hipStreamSynchronize(st));
+        env->dm_pairs = AoEnv::DmPairs{};
+        return 0;
+    }
+    if (!env->c.dm_separable) return fail("aoenv_set_dm_pairs: this shard's DM is dense (dm_separable == 0): upload its modes instead");
+    if (env->dm_env.on)
+        return fail("aoenv_set_dm_pairs: per-env factor tables are in force (aoenv_set_dm_env): clear them first (two NULLs)");
+    const size_t n = (size_t)env->E * env->R * env->A;
+    const size_t iy = first_not_finite(h_py, n), ix = first_not_finite(h_px, n);   // (the lower index is reported, py first)
+    if (iy < n && iy <= ix) return fail("aoenv_set_dm_pairs: py[%zu] is not finite", iy);
+    if (ix < n) return fail("aoenv_set_dm_pairs: px[%zu] is not finite", ix);
+    return AO_DISPATCH(env, set_dm_pairs_t, env, h_py, h_px, st);
+}
+
+int aoenv_get_dm_pairs(AoEnv* env, double* h_py, double* h_px, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_py || !h_px) return fail("aoenv_get_dm_pairs: null destination");
+    if (!env->dm_pairs.on) return fail("aoenv_get_dm_pairs: no actuator factor pairs are in force (aoenv_set_dm_pairs has not been called)");
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return AO_DISPATCH(env, get_dm_pairs_t, env, h_py, h_px);
+}
+
+int aoenv_get_dm_surface(AoEnv* env, double* h_surface, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_surface) return fail("aoenv_get_dm_surface: null destination");
+    if (!env->dm_surface_ahead())
+        return fail("aoenv_get_dm_surface: this shard forms its mirror surface inside the phase kernel and has no surface buffer "
+                    "(a dense DM or aoenv_set_dm_pairs has one)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AO_TRY(AO_DISPATCH(env, refresh_dense_dm, env, st));            // (outside a step: the pure command)
+    AO_HIP(hipStreamSynchronize(st));
+    return download_real(env, h_surface, env->surface(), (size_t)env->E * env->R * env->R);
 }
 
 // ---- per-env guide stars (star_env.hpp) ------------------------------------------------------------------------------------------
@@ -3421,7 +3541,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             return 0;
         case AOENV_OPT_FORCE_PATH:
             if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN |
-                          AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL))
+                          AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

@@ -380,6 +380,7 @@ def _layer_seeds(env_seeds, n_layer: int):
 
 
 MISREG_KEYS = ("shift_x", "shift_y", "radial_scaling", "tangential_scaling")
+ROTATION_KEYS = ("rotation_angle",) + MISREG_KEYS
 
 
 def resolve_dm_misregistration(values: dict, env_ids, n_envs: int, current) -> dict:
@@ -394,6 +395,24 @@ def resolve_dm_misregistration(values: dict, env_ids, n_envs: int, current) -> d
         raise ValueError(f"unknown mis-registration parameter(s) {sorted(unknown)}")
     out = {}
     for k in MISREG_KEYS:
+        v = as_float64(values.get(k, 0), k)
+        out[k] = assign_per_env(v, env_ids, n_envs, None if current is None else current[k], k)
+        if k.endswith("scaling") and (v <= -1).any():
+            raise ValueError(f"{k} must be above -1")
+    return out
+
+
+def resolve_dm_rotation(values: dict, env_ids, n_envs: int, current) -> dict:
+    """The rotated mirror of every env after a ``set_dm_rotation`` call: a dict of five ``[n_envs]`` float64 arrays
+    (``ROTATION_KEYS``; the angle in degrees), by the rules of ``resolve_dm_misregistration``: scalars or ``[n_envs]`` arrays (with
+    ``env_ids``: ``[len(env_ids)]`` in that order, a mask ascending), absolute per listed env, the others keep what ``current``
+    holds (None: zeros).  Raises ``ValueError`` for unknown keys, wrong shapes, non-numeric or non-finite values and a scaling at or
+    below -1.  Pure host code."""
+    unknown = set(values) - set(ROTATION_KEYS)
+    if unknown:
+        raise ValueError(f"unknown rotation parameter(s) {sorted(unknown)}")
+    out = {}
+    for k in ROTATION_KEYS:
         v = as_float64(values.get(k, 0), k)
         out[k] = assign_per_env(v, env_ids, n_envs, None if current is None else current[k], k)
         if k.endswith("scaling") and (v <= -1).any():
@@ -580,6 +599,25 @@ class Shard:
         L.call(self, "aoenv_get_dm_env", gx, gy, stream)
         return gx, gy
 
+    # per-env actuator factor pairs: py, px [n_env][R][n_valid_act] float64 (both None: cleared)
+    def set_dm_pairs(self, py, px, stream=0):
+        if py is not None or px is not None:
+            tail = (self.cfg.resolution, self.cfg.n_valid_act)
+            py, px = (self._per_env(np.asarray(t, dtype=np.float64), "DM actuator pairs", tail) for t in (py, px))
+        L.call(self, "aoenv_set_dm_pairs", py, px, stream)
+
+    def get_dm_pairs(self, stream=0):
+        shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.n_valid_act)
+        py, px = np.zeros(shape), np.zeros(shape)
+        L.call(self, "aoenv_get_dm_pairs", py, px, stream)
+        return py, px
+
+    # dm.OPD [n_env][R*R] of the command held (dense-DM shards and shards with actuator pairs)
+    def get_dm_surface(self, stream=0):
+        out = np.zeros((self.cfg.n_env, self.cfg.resolution * self.cfg.resolution))
+        L.call(self, "aoenv_get_dm_surface", out, stream)
+        return out
+
     # per-env guide stars: flux relative to the uploaded C_WFS_AMP / centroid thresholds, [n_env] float64 (None: one for the shard)
     def _set_star_row(self, name, values, stream):
         L.call(self, name, self._per_env(values, "star values"), stream)
@@ -736,6 +774,21 @@ class _DmProxy:
         if not e._dm_per_env:
             return None
         return e._shard.get_dm_env(e._stream())
+
+    def pairs_per_env(self):
+        """``(py, px)`` of every env as the library holds them (``aoenv_get_dm_pairs``): float64 ``[n_envs, R, nValidAct]``, the
+        uploaded values rounded to the env dtype; None while no actuator pairs are in force."""
+        e = self._e
+        if not getattr(e, "_dm_pairs_on", False):
+            return None
+        return e._shard.get_dm_pairs(e._stream())
+
+    def surface(self):
+        """``dm.OPD`` [m] of the command currently held, float64 ``[n_envs, R, R]`` (``aoenv_get_dm_surface``): for envs whose
+        shard keeps a surface buffer -- actuator pairs in force (``set_dm_rotation`` / ``set_dm_pairs_per_env``) or a dense mirror;
+        the library refuses otherwise."""
+        e = self._e
+        return e._shard.get_dm_surface(e._stream()).reshape(e.n_envs, e.R, e.R)
 
 
 class _Cam:
@@ -1091,6 +1144,7 @@ class BatchedAOEnv:
         self._per_env_clock = False
         self._wind_pixels = 1
         self._dm_per_env, self._dm_misreg = False, None              # ... and one mirror, the calibrated one
+        self._dm_pairs_on, self._dm_rot = False, None               # ... given by its factor tables, not by actuator pairs
         self._mag_env = self._thr_env = None                         # ... and one star, the calibrated one
         self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
         self._wf = self._wf_rec = None                               # ... and no wavefront basis (it is indexed by the pupil's pixels)
@@ -1384,6 +1438,7 @@ class BatchedAOEnv:
         is touched.  Not part of ``get_state``: after ``set_state`` call this again."""
         if np.any(np.asarray(rotation_angle, dtype=np.float64) != 0):
             raise NotImplementedError(calib.ROTATION_REFUSAL)
+        self._refuse_while_pairs("set_dm_misregistration")
         if self._dm_per_env and self._dm_misreg is None and env_ids is not None:
             raise ValueError("arbitrary per-env tables are in force (set_dm_tables_per_env): pass every env, or clear_dm_per_env() first")
         full = resolve_dm_misregistration(dict(shift_x=shift_x, shift_y=shift_y, radial_scaling=radial_scaling,
@@ -1404,6 +1459,7 @@ class BatchedAOEnv:
         the meaning of ``calib.DMTables.gx`` / ``gy`` (a two-DM env: the composite ``[gx1 | gx2]``).  A dead actuator is a zero
         column, an actuator gain a scaled one.  ``dm_misregistration`` is None from then on.  Bad arguments raise before anything is
         touched.  Not part of ``get_state``."""
+        self._refuse_while_pairs("set_dm_tables_per_env")
         if env_ids is None:
             cur = (None, None)
         elif self._dm_per_env:
@@ -1416,9 +1472,89 @@ class BatchedAOEnv:
         self._dm_per_env, self._dm_misreg = True, None
 
     def clear_dm_per_env(self):
-        """Every env the calibrated mirror again: every call does exactly what it did before the per-env tables were set."""
+        """Every env the calibrated mirror again: every call does exactly what it did before the per-env tables, or the actuator
+        pairs, were set."""
+        if getattr(self, "_dm_pairs_on", False):
+            self._shard.set_dm_pairs(None, None, self._stream())
+            self._dm_pairs_on, self._dm_rot = False, None
         self._shard.set_dm_env(None, None, self._stream())
         self._dm_per_env, self._dm_misreg = False, None
+
+    # -- every env its own rotated mirror (aoenv_set_dm_pairs) -----------------------------------------------------------------
+    def _refuse_while_pairs(self, who: str):
+        if getattr(self, "_dm_pairs_on", False):
+            raise ValueError(f"{who}: actuator factor pairs are in force (set_dm_rotation / set_dm_pairs_per_env): "
+                             "clear_dm_per_env() first")
+
+    def _refuse_while_tables(self, who: str):
+        if self._dm_per_env:
+            raise ValueError(f"{who}: per-env factor tables are in force (set_dm_misregistration / set_dm_tables_per_env): "
+                             "clear_dm_per_env() first")
+
+    def _calibrated_pairs(self):
+        """(py, px) [R, A] of the calibrated mirror: the columns of its factor tables, actuator by actuator (a two-DM env: of the
+        composite tables)."""
+        dmt = self._dm_tables
+        n = dmt.nAct
+        return dmt.gy[:, dmt.act_idx // n], dmt.gx[:, dmt.act_idx % n]
+
+    def set_dm_rotation(self, rotation_angle, shift_x=0, shift_y=0, radial_scaling=0, tangential_scaling=0, env_ids=None):
+        """Every env its own ROTATED mirror: ``rotation_angle`` [degrees] with ``shift_x`` / ``shift_y`` [m] and the two scalings,
+        scalars or ``[n_envs]`` arrays (with ``env_ids``: ``[len(env_ids)]`` in that order), relative to the calibrated mirror
+        (the shifts are added to its ``MisReg_shift*``) and absolute per listed env, as in ``set_dm_misregistration``.  The mirror
+        is OOPAO/DeformableMirror.py:326-351 with ``rotationAngle != 0``: the actuator grid turns about the optical axis after the
+        scalings and before the shift; each actuator's Gaussian stays a product of a y and an x factor
+        (``calib.dm_actuator_pairs``), and the library sums ``c[k] py[:, k] (x) px[:, k]`` per env on the matrix cores
+        (``aoenv_set_dm_pairs``).  The reconstructor and the calibration stay those of the calibrated mirror.  The shard leaves
+        the fused step kernel while pairs are in force (``fused_step`` is False); every loop, the disturbance, the delay, the modal
+        surface, the wavefront record and the long exposure see the env's own mirror.  Refused while per-env factor tables are in
+        force (``clear_dm_per_env()`` first) and on a two-DM env (use ``set_dm_pairs_per_env``).  Bad arguments raise before
+        anything is touched.  Not part of ``get_state``."""
+        self._refuse_while_tables("set_dm_rotation")
+        dmt = self._dm_tables
+        if hasattr(dmt, "dm2"):
+            raise ValueError("set_dm_rotation: a two-DM env has no single actuator grid to rotate; build the pairs of the composite "
+                             "mirror and use set_dm_pairs_per_env")
+        if getattr(self, "_dm_pairs_on", False) and getattr(self, "_dm_rot", None) is None and env_ids is not None:
+            raise ValueError("arbitrary actuator pairs are in force (set_dm_pairs_per_env): pass every env, or clear_dm_per_env() first")
+        full = resolve_dm_rotation(dict(rotation_angle=rotation_angle, shift_x=shift_x, shift_y=shift_y, radial_scaling=radial_scaling,
+                                        tangential_scaling=tangential_scaling), env_ids, self.n_envs, getattr(self, "_dm_rot", None))
+        cache, pairs = {}, []
+        for e in range(self.n_envs):
+            key = tuple(float(full[k][e]) for k in ROTATION_KEYS)
+            if key not in cache:
+                kw = dict(zip(ROTATION_KEYS, key))
+                for k_ in MISREG_KEYS:
+                    kw[k_] = dmt.misreg[k_] + kw[k_]
+                cache[key] = calib.dm_actuator_pairs(self.param, n_subap=dmt.nAct - 1, **kw)
+            pairs.append(cache[key])
+        self._shard.set_dm_pairs(np.stack([g[0] for g in pairs]), np.stack([g[1] for g in pairs]), self._stream())
+        self._dm_pairs_on, self._dm_rot = True, full
+
+    def set_dm_pairs_per_env(self, py, px, env_ids=None):
+        """The general form: any mirror whose actuators are products of a y and an x factor, per env.  ``py``, ``px``: float64
+        ``[n_envs, R, nValidAct]`` (with ``env_ids``: ``[len(env_ids), R, nValidAct]`` in that order, the other envs keeping what
+        they have -- the calibrated mirror if none yet).  A dead actuator is a zero column, a weak one a scaled column; a two-DM
+        env passes the pairs of its composite mirror.  ``dm_rotation`` is None from then on.  Refused while per-env factor tables
+        are in force.  Bad arguments raise before anything is touched.  Not part of ``get_state``."""
+        self._refuse_while_tables("set_dm_pairs_per_env")
+        if env_ids is None:
+            cur = (None, None)
+        elif getattr(self, "_dm_pairs_on", False):
+            cur = self._shard.get_dm_pairs(self._stream())          # (values as held: a second rounding to the env dtype changes nothing)
+        else:
+            cur = self._calibrated_pairs()
+        full = [assign_per_env(t, env_ids, self.n_envs, c, name, tail=(self.R, self._dm_tables.nValidAct), scalar=False)
+                for name, t, c in (("py", py, cur[0]), ("px", px, cur[1]))]
+        self._shard.set_dm_pairs(full[0], full[1], self._stream())
+        self._dm_pairs_on, self._dm_rot = True, None
+
+    @property
+    def dm_rotation(self):
+        """``dict(rotation_angle, shift_x, shift_y, radial_scaling, tangential_scaling)`` of ``[n_envs]`` float64 copies, relative
+        to the calibrated mirror, while ``set_dm_rotation`` is in force; None otherwise (no pairs, or arbitrary ones)."""
+        rot = getattr(self, "_dm_rot", None)
+        return None if rot is None else {k: v.copy() for k, v in rot.items()}
 
     @property
     def dm_misregistration(self):

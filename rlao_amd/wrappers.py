@@ -74,6 +74,16 @@ class TorchWrapper:
     def clear_dm_per_env(self):
         return self._env.clear_dm_per_env()
 
+    def set_dm_rotation(self, *args, **kw):
+        return self._env.set_dm_rotation(*args, **kw)
+
+    def set_dm_pairs_per_env(self, py, px, env_ids=None):
+        return self._env.set_dm_pairs_per_env(py, px, env_ids)
+
+    @property
+    def dm_rotation(self):
+        return self._env.dm_rotation
+
     @property
     def dm_misregistration(self):
         return self._env.dm_misregistration
@@ -239,6 +249,16 @@ class TimeDelayEnv:
 
     def clear_dm_per_env(self):
         return self._env.clear_dm_per_env()
+
+    def set_dm_rotation(self, *args, **kw):
+        return self._env.set_dm_rotation(*args, **kw)
+
+    def set_dm_pairs_per_env(self, py, px, env_ids=None):
+        return self._env.set_dm_pairs_per_env(py, px, env_ids)
+
+    @property
+    def dm_rotation(self):
+        return self._env.dm_rotation
 
     @property
     def dm_misregistration(self):
@@ -471,6 +491,16 @@ class HistoryEnv:
 
     def clear_dm_per_env(self):
         return self._env.clear_dm_per_env()
+
+    def set_dm_rotation(self, *args, **kw):
+        return self._env.set_dm_rotation(*args, **kw)
+
+    def set_dm_pairs_per_env(self, py, px, env_ids=None):
+        return self._env.set_dm_pairs_per_env(py, px, env_ids)
+
+    @property
+    def dm_rotation(self):
+        return self._env.dm_rotation
 
     @property
     def dm_misregistration(self):
