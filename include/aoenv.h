@@ -513,7 +513,9 @@ int aoenv_run_integrator_modal(AoEnv* env, int i0, int n_steps, void* d_obs, voi
  * wavefront_kernels.hip up to 64 modes and the split-K GEMM of the reconstruction above (measured: profiles/wavefront_timing.json);
  * the split count of that route is a function of (R^2, K) too. */
 #define AOENV_MAX_WF_MODES 1024
-enum AoWavefront { AOENV_WF_RESIDUAL = 1, AOENV_WF_ATMOSPHERE = 2 };
+enum AoWavefront { AOENV_WF_RESIDUAL = 1, AOENV_WF_ATMOSPHERE = 2,
+                   AOENV_WF_SCIENCE = 4 /* the residual toward the science target (aoenv_set_science_direction): X = phase_sci, s as the
+                                           residual's; aoenv_project_wavefront alone takes it, one more launch in front; the record refuses it */ };
 typedef struct AoWavefrontBasis {
     int32_t n_modes;               /* K in [1, min(n_pix, AOENV_MAX_WF_MODES)] */
     int32_t n_pix;                 /* must equal the number of pupil pixels of the uploaded pupil */
@@ -662,6 +664,46 @@ int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream);
  * camera frame; the loop's state and every output are bit for bit what they are without it, and a fused shard stays fused.
  * d_sum_log10 must be non-null exactly when AOENV_SCI_LOG10 is set.  NULL d_sum detaches; no stream is waited for. */
 int aoenv_set_science_accumulator(AoEnv* env, void* d_sum, void* d_sum_log10, int32_t* d_count);
+
+/* Replaces: the reference env's second source, put off axis "to simulate anisoplanetism" (MAIN_CODE/OOPAOEnv/OOPAOEnv.py:140-146,
+ * 303-304, 335-336: self.src.coordinates = [0.4, 0]; atm * src, OOPAO/Atmosphere.py:313-334, 439-450, 643-647): per env, a science
+ * target at [zenith arcsec, azimuth deg] seen through the same layers and the same mirror as the guide star.  The model is
+ * rlao_amd/csrc/offaxis.hpp.  For a layer at altitude h on its N x N grid
+ *     [x_z, y_z] = pol2cart(h tan(zenith / 206265) R / D, deg2rad(azimuth))    pixels; y_z moves rows, x_z columns
+ * and the target's R x R footprint reads layer.phase (the wind's clipped bicubic warp) at (row + N//2 - R//2 + y_z, column + N//2 -
+ * R//2 + x_z), bilinearly, exactly where the reference translates: unless both offsets are whole pixels.  The host computes floor
+ * and fraction of every (layer, env) in float64; the blend runs in the env dtype.  The mirror is conjugated to the pupil:
+ *     OPD_sci = (OPD_no_pupil_sci + dm.OPD) * pupil,  phase_sci = OPD_sci 2 pi / lambda_src,
+ *     rms_sci = std(OPD_sci[pupil]) 1e9,  strehl_sci = exp(-var(phase_sci[pupil]))
+ * with the surface the sensor saw in that step (delay, disturbance, per-env mirrors included); the library forms it as
+ * AOENV_B_PHASE + (OPD_no_pupil_sci - OPD_no_pupil) 2 pi / lambda_src.  The pupil sums are float64 in a fixed order, no atomics: an
+ * env has the same bits in any shard and at any place in it; at zenith 0 OPD_no_pupil_sci and phase_sci are bit for bit
+ * AOENV_B_OPD_ATM and AOENV_B_PHASE.
+ * aoenv_set_field tells the library what it is otherwise never told: the telescope's diameter [m], its field of view [arcsec] and
+ * the n_layer altitudes [m].  Refused: values that are negative or not finite, and any call while a direction is set.
+ * aoenv_set_science_direction takes [n_env] arrays; it copies the footprints (and allocates phase_sci scratch) before it returns and
+ * waits for the stream once.  Configuration: in no checkpoint buffer.  Both arrays NULL forget the direction and detach its record.
+ * Refused, with nothing changed: no field set, a shard without layers, a zenith that is negative, not finite or above fov / 2, an
+ * azimuth that is not finite, and a footprint whose interpolation taps would leave the layer's screen (with the reference's grid
+ * rule N = ceil(R / D (D + 2 tan(fov / 2) h)) + 4 no zenith <= fov / 2 does).  Every zenith 0 is legal.
+ * No buffer id, no profiled kernel and no ABI version go with it. */
+int aoenv_set_field(AoEnv* env, double diameter, double fov_arcsec, const double* h_altitude);
+int aoenv_set_science_direction(AoEnv* env, const double* h_zenith_arcsec, const double* h_azimuth_deg, void* stream);
+int aoenv_get_science_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azimuth_deg);
+/* The residual toward the target of the buffers as they are now -- after aoenv_reset_soft, aoenv_measure or a step of the per-call
+ * API: d_phase_sci [n_env][R*R] (rad at the source wavelength), d_opd_atm_sci [n_env][R*R] (OPD_no_pupil toward the target, m),
+ * d_rms_nm and d_strehl [n_env], all in the env dtype, any of them NULL.  One launch, after the re-derivation of the on-axis
+ * atmosphere OPD where aoenv_download(AOENV_B_OPD_ATM) would re-derive it.  Refused: no direction set, a user-defined atmosphere OPD
+ * (aoenv_set_atm_opd: there are no layers to look through until the atmosphere advances again). */
+int aoenv_science_residual(AoEnv* env, void* d_phase_sci, void* d_opd_atm_sci, void* d_rms_nm, void* d_strehl, void* stream);
+/* A per-step record by the rules of aoenv_set_wavefront_record: while attached, stepped frame i of every stepped call writes slot
+ * i - i_base of the caller-owned d_rec [n_slots][2][n_env] (env dtype): rms nm, then Strehl, toward the target.  One extra launch
+ * per recorded step; such a step stores the phase and the on-axis atmosphere OPD it otherwise skips; the loop's state and outputs
+ * are bit for bit what they are without it; a fused shard stays fused; AOENV_OPT_STEP_PAIRS stands down.  A call whose frames do
+ * not all lie in the window is refused before anything is launched.  NULL detaches.  Refused: no direction, i_base < 0, n_slots < 1.
+ * While a direction is set, aoenv_science_psf(flat = 0) and the long exposure form their window from phase_sci (one more launch in
+ * front of the window's); aoenv_compute_psf keeps the guide star's direction. */
+int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int n_slots);
 
 /* Replaces: the WFS camera settings wfs.cam.{photonNoise, readoutNoise, QE, darkCurrent, integrationTime, FWC, bits, gain,
  * sensor} (OOPAO/Detector.py:19-60; Papyrus: photonNoise = True, MAIN/OOPAOEnv/OOPAOEnv.py:379; Razor:

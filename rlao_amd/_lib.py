@@ -31,7 +31,7 @@ PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_P
 PATH_SCI_GENERAL = 16384
 PATH_DM_PAIRS_GENERAL = 32768
 SCI_LOG10 = 1                                                      # enum AoScienceFlag
-WF_RESIDUAL, WF_ATMOSPHERE = 1, 2                                  # enum AoWavefront
+WF_RESIDUAL, WF_ATMOSPHERE, WF_SCIENCE = 1, 2, 4                   # enum AoWavefront
 MAX_WF_MODES = 1024                                                # AOENV_MAX_WF_MODES
 KERNEL_NAMES = ("ring_prepare", "mt_normal", "gemm_ring", "ring_scatter", "phase", "sh_spots", "sh_centroid",
                 "gemm_recon", "recon_finish", "pyramid", "sh_tail", "env_step", "detector")
@@ -140,6 +140,11 @@ EXPORTS = {
     "aoenv_set_science": (C.c_int, [C.c_void_p, C.POINTER(AoScience), C.c_void_p]),
     "aoenv_science_psf": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "aoenv_set_science_accumulator": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_field": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    "aoenv_set_science_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_science_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_science_residual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_science_direction_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -160,6 +165,10 @@ EXPORTS = {
     "aoenv_test_poisson_table": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aoenv_test_poisson": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p]),
 }
+
+
+_LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
+                  "aoenv_science_residual", "aoenv_set_science_direction_record")
 
 
 class AoEnvError(RuntimeError):
@@ -183,8 +192,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in EXPORTS.items():
-        if name == "aoenv_step_counters" and os.environ.get("AOENV_LIB") and not hasattr(lib, name):
-            continue                       # an A/B run of a library built before the counters (AOENV_LIB): same ABI without them
+        if name in _LATER_ENTRIES and os.environ.get("AOENV_LIB") and not hasattr(lib, name):
+            continue                       # an A/B run of a library built before these entries (AOENV_LIB): same ABI without them
         fn = getattr(lib, name)            # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

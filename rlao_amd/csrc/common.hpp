@@ -510,6 +510,27 @@ struct SciArgs {
 template <typename T>
 int launch_science_window(const SciArgs<T>& a, bool general, hipStream_t st);
 
+// the residual toward the science target (offaxis_kernels.hip; the model and the plan are offaxis.hpp): one launch, one workgroup
+// per env.  `pa` as the phase kernels take it (screens, taps, grids); every output may be null
+struct OaShift;
+template <typename T>
+struct OaArgs {
+    PhaseArgs pa;
+    const OaShift* dir;    // [n_layer][E] the footprints toward the target
+    const uint8_t* pupil;  // [R*R]
+    const T* phase;        // [E][R*R] AOENV_B_PHASE of this step
+    const T* opd_atm;      // [E][R*R] the on-axis atmosphere OPD of this step
+    T* phase_sci;          // [E][R*R] rad at the source wavelength
+    T* opd_atm_sci;        // [E][R*R] m
+    T* rms_nm;             // [E]
+    T* strehl;             // [E]
+    int R, n_pupil;
+    T atm_scale, src_scale;
+    double src_scale_d;    // 2 pi / lambda_src
+};
+template <typename T>
+int launch_science_residual(const OaArgs<T>& a, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

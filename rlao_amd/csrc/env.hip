@@ -21,6 +21,7 @@
 #include "science.hpp"
 #include "star_env.hpp"
 #include "wavefront.hpp"
+#include "offaxis.hpp"
 
 namespace ao {
 
@@ -194,6 +195,21 @@ struct AoEnv {
         int32_t* count = nullptr;           // caller-owned [E]
         bool accumulates(int i) const { return sum && i >= first_frame; }
     } sci;
+    // off-axis science target (aoenv_set_science_direction, offaxis.hpp): configuration like the science camera, in ONE block of its
+    // own (NULL arrays free it); the record is the caller's memory.  The field (aoenv_set_field) is what the library is otherwise
+    // never told: the telescope's diameter and field of view and the layers' altitudes
+    struct OffAxis {
+        bool set = false, have_field = false;
+        double D = 0, fov = 0, altitude[kMaxLayer] = {};
+        std::vector<double> zenith, azimuth;   // [E] arcsec, deg
+        Block mem;
+        OaShift* dir = nullptr;             // [L][E] the footprints toward the target
+        void* phase_sci = nullptr;          // [E][R*R] what the science camera and the projection look at
+        void* rec = nullptr;                // caller-owned [n_slots][2][E] (rms nm, Strehl), or null: nothing is recorded
+        int i_base = 0, n_slots = 0;
+        // stepped frame i needs the step's phase and on-axis atmosphere OPD in HBM
+        bool reads_step(bool accumulates) const { return rec || (set && accumulates); }
+    } oa;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -1000,7 +1016,8 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     // (a wavefront record reads the phase -- and the atmosphere, if it records it -- of EVERY step: both stores, not the frame's;
     // the long exposure reads the phase of every frame it accumulates)
     const int rec = env->wf.recorded();
-    fill_phase_args<float>(env, pa, pb, 1, (env->store_opd_atm || (rec & AOENV_WF_ATMOSPHERE)) ? 1 : 0, 1);
+    const bool oa = env->oa.reads_step(env->sci.accumulates(i));   // (the science direction reads both of every step it serves)
+    fill_phase_args<float>(env, pa, pb, 1, (env->store_opd_atm || (rec & AOENV_WF_ATMOSPHERE) || oa) ? 1 : 0, 1);
     a.k = make_phase_kargs<float>(pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
     a.sc = sh_const<float>(env);
     a.fa = finish_args<float>(env, static_cast<const float*>(d_action), static_cast<float*>(d_obs),
@@ -1009,7 +1026,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     a.frame = env->as<float>(env->frame);
     // (atm.OPD written every step is the state-inspection mode: every step is then observable, there is no fast path to keep)
     a.store_frame = (observable || env->store_opd_atm) ? 1 : 0;
-    a.store_phase = (a.store_frame || rec || env->sci.accumulates(i)) ? 1 : 0;
+    a.store_phase = (a.store_frame || rec || oa || env->sci.accumulates(i)) ? 1 : 0;
     a.signal = env->as<float>(env->signal);
     a.wfs_max = env->as<float>(env->wfs_max);
     a.fac_m = env->as<float>(env->fac_m);
@@ -1064,7 +1081,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
 // the long exposure's window are the caller's)
 bool step_pair_eligible(AoEnv* env) {
     if (!env->use_step_pairs || env->esz != 4 || !fused_step_ok<float>(env) || env->per_env_wind) return false;
-    if (env->disturb.set || env->wf.recorded() || env->store_opd_atm) return false;
+    if (env->disturb.set || env->wf.recorded() || env->oa.rec || env->store_opd_atm) return false;
     StepArgs a{};                                                  // what the choice of the instantiation reads
     a.sc = sh_const<float>(env);
     a.det = env->det;
@@ -1150,8 +1167,8 @@ int wf_project(AoEnv* env, int what, void* out, hipStream_t st) {
     const AoEnv::Wavefront& wf = env->wf;
     WfArgs<T> a{};
     int w = 0;
-    if (what & AOENV_WF_RESIDUAL) {
-        a.x[w] = env->as<T>(env->phase);
+    if (what & (AOENV_WF_RESIDUAL | AOENV_WF_SCIENCE)) {            // (the residual toward the target: the caller has formed it)
+        a.x[w] = env->as<T>((what & AOENV_WF_SCIENCE) ? env->oa.phase_sci : env->phase);
         a.scale[w] = (T)(env->c.src_wavelength / (2.0 * M_PI));
         a.use_scale[w] = 1;
         ++w;
@@ -1206,11 +1223,62 @@ int wf_record_step(AoEnv* env, int i, hipStream_t st) {
 // what every stepped call checks before its first launch: frames [i0, i0 + n) inside the window of an attached record
 static int wf_window_check(const AoEnv* env, int i0, int n) {
     const AoEnv::Wavefront& wf = env->wf;
+    const AoEnv::OffAxis& oa = env->oa;
+    if (oa.rec && n > 0 && (i0 < oa.i_base || (int64_t)i0 + n > (int64_t)oa.i_base + oa.n_slots))
+        return fail("frames [%d, %lld) leave the window [%d, %d) of the attached science-direction record", i0, (long long)i0 + n, oa.i_base,
+                    oa.i_base + oa.n_slots);
     if (!wf.rec || n <= 0) return 0;
     if (i0 < wf.i_base || (int64_t)i0 + n > (int64_t)wf.i_base + wf.n_slots)
         return fail("frames [%d, %lld) leave the window [%d, %d) of the attached wavefront record", i0, (long long)i0 + n, wf.i_base,
                     wf.i_base + wf.n_slots);
     return 0;
+}
+
+// ---- off-axis science target (offaxis.hpp, offaxis_kernels.hip) -------------------------------------------------------------------
+// The residual toward the target from the screens, AOENV_B_PHASE and the on-axis atmosphere OPD as they stand.  One launch, not
+// attributed by aoenv_profile.
+template <typename T>
+int oa_residual(AoEnv* env, void* phase_sci, void* opd_atm_sci, void* rms_nm, void* strehl, hipStream_t st) {
+    OaArgs<T> a{};
+    PhaseBuffers<T> pb;
+    fill_phase_args<T>(env, a.pa, pb, 1, 0, 0);
+    const KArgs<T> k = make_phase_kargs<T>(a.pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
+    a.dir = env->oa.dir;
+    a.pupil = env->pupil;
+    a.phase = env->as<T>(env->phase);
+    a.opd_atm = env->as<T>(env->opd_atm);
+    a.phase_sci = static_cast<T*>(phase_sci);
+    a.opd_atm_sci = static_cast<T*>(opd_atm_sci);
+    a.rms_nm = static_cast<T*>(rms_nm);
+    a.strehl = static_cast<T*>(strehl);
+    a.R = env->R;
+    a.n_pupil = env->n_pupil;
+    a.atm_scale = k.atm_scale;
+    a.src_scale = k.src_scale;
+    a.src_scale_d = 6.283185307179586476925286766559 / env->c.src_wavelength;
+    return launch_science_residual<T>(a, st);
+}
+
+// frame i of a stepped loop into its slot of the record, if one is attached (the window was checked before the first launch)
+template <typename T>
+int oa_record_step(AoEnv* env, int i, hipStream_t st) {
+    const AoEnv::OffAxis& oa = env->oa;
+    if (!oa.rec) return 0;
+    if (i < oa.i_base || i - oa.i_base >= oa.n_slots) return fail("frame %d outside the science-direction record's window [%d, %d)", i, oa.i_base, oa.i_base + oa.n_slots);
+    T* slot = static_cast<T*>(oa.rec) + (size_t)(i - oa.i_base) * 2 * env->E;
+    return oa_residual<T>(env, nullptr, nullptr, slot, slot + env->E, st);
+}
+
+// on demand: the on-axis atmosphere OPD is not written by the step kernels unless asked to, and is re-derived from the screens
+// first, as aoenv_download(AOENV_B_OPD_ATM) does
+template <typename T>
+int oa_residual_now(AoEnv* env, const char* who, void* phase_sci, void* opd_atm_sci, void* rms_nm, void* strehl, hipStream_t st) {
+    if (!env->oa.set) return fail("%s: no science direction is set (aoenv_set_science_direction)", who);
+    if (env->atm_user_defined)
+        return fail("%s: the atmosphere OPD is user-defined (aoenv_set_atm_opd): there are no layers to look through until the atmosphere advances", who);
+    if (env->L < 1) return fail("%s: the shard has no layers", who);
+    if (!env->store_opd_atm) AO_TRY(run_phase<T>(env, 1, 1, st, 0));
+    return oa_residual<T>(env, phase_sci, opd_atm_sci, rms_nm, strehl, st);
 }
 
 // ---- science camera (science.hpp, science_kernels.hip) -----------------------------------------------------------------------------
@@ -1220,7 +1288,8 @@ template <typename T>
 int sci_window(AoEnv* env, int flat, void* out, hipStream_t st) {
     const AoEnv::Science& sc = env->sci;
     SciArgs<T> a{};
-    a.phase = env->as<T>(env->phase);
+    // (under a science direction the camera looks at the target: the caller has formed phase_sci in the launch before this one)
+    a.phase = env->as<T>(env->oa.set && !flat ? env->oa.phase_sci : env->phase);
     a.amp = env->as<T>(sc.amp);
     a.table = env->as<T>(sc.table);
     a.out = static_cast<T*>(out);
@@ -1241,6 +1310,7 @@ int sci_window(AoEnv* env, int flat, void* out, hipStream_t st) {
 template <typename T>
 int sci_accumulate_step(AoEnv* env, int i, hipStream_t st) {
     if (!env->sci.accumulates(i)) return 0;
+    if (env->oa.set) AO_TRY(oa_residual<T>(env, env->oa.phase_sci, nullptr, nullptr, nullptr, st));   // (the step stored what it reads)
     return sci_window<T>(env, 0, nullptr, st);
 }
 
@@ -1256,14 +1326,16 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
         AO_TRY(run_fused_step<T>(env, i, d_action, d_obs, d_reward, d_strehl, gain, observable, st));
         env->step_cmd = nullptr;
         AO_TRY(wf_record_step<T>(env, i, st));
+        AO_TRY(oa_record_step<T>(env, i, st));
         AO_TRY(sci_accumulate_step<T>(env, i, st));
         if (d_frame)
             AO_HIP(hipMemcpyAsync(d_frame, env->frame, (size_t)env->E * env->c.cam_res * env->c.cam_res * sizeof(T),
                                   hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE)) ? 1 : 0, st));
+    AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE) || env->oa.reads_step(env->sci.accumulates(i))) ? 1 : 0, st));
     AO_TRY(wf_record_step<T>(env, i, st));                         // (the phase kernel has written what the sensor is about to see)
+    AO_TRY(oa_record_step<T>(env, i, st));
     AO_TRY(sci_accumulate_step<T>(env, i, st));
     env->step_cmd = nullptr;                                       // the integration below, and a dense DM's next surface: the pure command
     // one workgroup per env re-reads the factors from L2: wins while launch latency dominates (measured: 19.5 us vs
@@ -2809,10 +2881,16 @@ static int wf_one_or_two_bits(int what) { return what != 0 && (what & ~(AOENV_WF
 int aoenv_project_wavefront(AoEnv* env, int what, void* d_out, void* stream) {
     AO_CHECK_ENV(env);
     if (!env->wf.set) return fail("aoenv_project_wavefront: no wavefront basis is set (aoenv_set_wavefront_basis)");
-    if (what != AOENV_WF_RESIDUAL && what != AOENV_WF_ATMOSPHERE)
-        return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE", what);
+    if (what != AOENV_WF_RESIDUAL && what != AOENV_WF_ATMOSPHERE && what != AOENV_WF_SCIENCE)
+        return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE, AOENV_WF_SCIENCE", what);
     if (!d_out) return fail("aoenv_project_wavefront: null output");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (what == AOENV_WF_SCIENCE) {                                // the residual toward the target, formed now
+        if (!env->oa.set)
+            return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE (AOENV_WF_SCIENCE: no science direction is set, aoenv_set_science_direction)", what);
+        AO_TRY(require_step_constants(env, false));
+        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_project_wavefront", env->oa.phase_sci, nullptr, nullptr, nullptr, st));
+    }
     if (what == AOENV_WF_ATMOSPHERE && env->L > 0 && !env->atm_user_defined && !env->store_opd_atm) {
         // not written by the step kernels unless asked to: re-derived from the screens now, as aoenv_download(AOENV_B_OPD_ATM) does
         AO_TRY(require_step_constants(env, false));
@@ -2830,6 +2908,8 @@ int aoenv_set_wavefront_record(AoEnv* env, int what, void* d_rec, int i_base, in
         return 0;
     }
     if (!wf.set) return fail("aoenv_set_wavefront_record: no wavefront basis is set (aoenv_set_wavefront_basis)");
+    if (what & AOENV_WF_SCIENCE)
+        return fail("aoenv_set_wavefront_record: what = %d is no combination of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE: AOENV_WF_SCIENCE is projected on demand only (aoenv_project_wavefront), the record does not take it", what);
     if (!wf_one_or_two_bits(what)) return fail("aoenv_set_wavefront_record: what = %d is no combination of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE", what);
     if (i_base < 0 || n_slots < 1) return fail("aoenv_set_wavefront_record: window [%d, %d + %d) is empty or negative", i_base, i_base, n_slots);
     wf.rec = d_rec;
@@ -2901,7 +2981,12 @@ int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream) {
     AO_CHECK_ENV(env);
     if (!env->sci.set) return fail("aoenv_science_psf: no science camera is set (aoenv_set_science)");
     if (!d_out) return fail("aoenv_science_psf: null output");
-    return AO_DISPATCH(env, sci_window, env, flat, d_out, static_cast<hipStream_t>(stream));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (env->oa.set && !flat) {                                    // the camera looks at the target
+        AO_TRY(require_step_constants(env, false));
+        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_science_psf", env->oa.phase_sci, nullptr, nullptr, nullptr, st));
+    }
+    return AO_DISPATCH(env, sci_window, env, flat, d_out, st);
 }
 
 int aoenv_set_science_accumulator(AoEnv* env, void* d_sum, void* d_sum_log10, int32_t* d_count) {
@@ -2919,6 +3004,103 @@ int aoenv_set_science_accumulator(AoEnv* env, void* d_sum, void* d_sum_log10, in
     sc.sum = d_sum;
     sc.sum_log10 = d_sum_log10;
     sc.count = d_count;
+    return 0;
+}
+
+// ---- off-axis science target (offaxis.hpp) -----------------------------------------------------------------------------------------
+int aoenv_set_field(AoEnv* env, double diameter, double fov_arcsec, const double* h_altitude) {
+    AO_CHECK_ENV(env);
+    if (!(std::isfinite(diameter) && diameter > 0)) return fail("aoenv_set_field: diameter %g is not positive", diameter);
+    if (!(std::isfinite(fov_arcsec) && fov_arcsec >= 0)) return fail("aoenv_set_field: field of view %g arcsec is negative or not finite", fov_arcsec);
+    if (env->L > 0 && !h_altitude) return fail("aoenv_set_field: null altitudes");
+    for (int l = 0; l < env->L; ++l)
+        if (!(std::isfinite(h_altitude[l]) && h_altitude[l] >= 0)) return fail("aoenv_set_field: altitude %g of layer %d is negative or not finite", h_altitude[l], l);
+    if (env->oa.set) return fail("aoenv_set_field: a science direction is set; forget it first (aoenv_set_science_direction with NULL)");
+    AoEnv::OffAxis& oa = env->oa;
+    oa.D = diameter;
+    oa.fov = fov_arcsec;
+    for (int l = 0; l < env->L; ++l) oa.altitude[l] = h_altitude[l];
+    oa.have_field = true;
+    return 0;
+}
+
+int aoenv_set_science_direction(AoEnv* env, const double* h_zenith_arcsec, const double* h_azimuth_deg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AoEnv::OffAxis& oa = env->oa;
+    if (!h_zenith_arcsec && !h_azimuth_deg) {                      // forget the direction; the record goes with it, the field stays
+        AO_HIP(hipStreamSynchronize(st));
+        oa.mem = Block{};
+        oa.dir = nullptr;
+        oa.phase_sci = nullptr;
+        oa.rec = nullptr;
+        oa.i_base = oa.n_slots = 0;
+        oa.zenith.clear();
+        oa.azimuth.clear();
+        oa.set = false;
+        return 0;
+    }
+    if (!h_zenith_arcsec || !h_azimuth_deg) return fail("aoenv_set_science_direction: one of the two arrays is null");
+    if (env->L < 1) return fail("aoenv_set_science_direction: the shard has no layers to look through");
+    if (!oa.have_field) return fail("aoenv_set_science_direction: the field is not set (aoenv_set_field)");
+    const int E = env->E, L = env->L;
+    int N_l[kMaxLayer], we = 0, wl = 0;
+    for (int l = 0; l < L; ++l) N_l[l] = env->layer[l].N;
+    std::vector<OaShift> dir((size_t)L * E);
+    switch (oa_make(L, E, env->R, oa.D, oa.fov, oa.altitude, N_l, h_zenith_arcsec, h_azimuth_deg, dir.data(), &we, &wl)) {
+        case kOaOk: break;
+        case kOaNoLayers: return fail("aoenv_set_science_direction: the shard has no layers to look through");
+        case kOaNull: return fail("aoenv_set_science_direction: null argument");
+        case kOaGeometry: return fail("aoenv_set_science_direction: the field is not valid (aoenv_set_field)");
+        case kOaZenith:
+            return fail("aoenv_set_science_direction: zenith %g arcsec of env %d is negative, not finite or above fov / 2 = %g", h_zenith_arcsec[we], we, oa.fov / 2);
+        case kOaAzimuth: return fail("aoenv_set_science_direction: azimuth of env %d is not finite", we);
+        case kOaPlan:
+            return fail("aoenv_set_science_direction: the footprint of env %d in layer %d (grid %d) would read beyond the layer's screen", we, wl, N_l[wl]);
+    }
+    const size_t R2 = (size_t)env->R * env->R;
+    const std::initializer_list<size_t> parts = {dir.size() * sizeof(OaShift), (size_t)E * R2 * env->esz};
+    AO_HIP(hipStreamSynchronize(st));                              // a launch in flight reads the table in place
+    Block mem;                                                     // (built whole before the direction in use is given up)
+    if (mem.alloc(parts, true)) return fail("aoenv_set_science_direction: no device memory for %zu bytes", dev_layout(parts).total);
+    if (mem.upload(0, dir.data(), dir.size() * sizeof(OaShift))) return fail("aoenv_set_science_direction: the copy of the footprints failed");
+    oa.mem = std::move(mem);
+    oa.dir = static_cast<OaShift*>(oa.mem.part(0));
+    oa.phase_sci = oa.mem.part(1);
+    oa.zenith.assign(h_zenith_arcsec, h_zenith_arcsec + E);
+    oa.azimuth.assign(h_azimuth_deg, h_azimuth_deg + E);
+    oa.set = true;                                                 // (an attached record stays: it is [n_slots][2][E] whatever the direction)
+    return 0;
+}
+
+int aoenv_get_science_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azimuth_deg) {
+    if (!env || !h_zenith_arcsec || !h_azimuth_deg) return fail("aoenv_get_science_direction: null argument");
+    if (!env->oa.set) return fail("aoenv_get_science_direction: no science direction is set (aoenv_set_science_direction)");
+    std::copy(env->oa.zenith.begin(), env->oa.zenith.end(), h_zenith_arcsec);
+    std::copy(env->oa.azimuth.begin(), env->oa.azimuth.end(), h_azimuth_deg);
+    return 0;
+}
+
+int aoenv_science_residual(AoEnv* env, void* d_phase_sci, void* d_opd_atm_sci, void* d_rms_nm, void* d_strehl, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!env->oa.set) return fail("aoenv_science_residual: no science direction is set (aoenv_set_science_direction)");
+    AO_TRY(require_step_constants(env, false));
+    return AO_DISPATCH(env, oa_residual_now, env, "aoenv_science_residual", d_phase_sci, d_opd_atm_sci, d_rms_nm, d_strehl, static_cast<hipStream_t>(stream));
+}
+
+int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int n_slots) {
+    AO_CHECK_ENV(env);
+    AoEnv::OffAxis& oa = env->oa;
+    if (!d_rec) {
+        oa.rec = nullptr;
+        oa.i_base = oa.n_slots = 0;
+        return 0;
+    }
+    if (!oa.set) return fail("aoenv_set_science_direction_record: no science direction is set (aoenv_set_science_direction)");
+    if (i_base < 0 || n_slots < 1) return fail("aoenv_set_science_direction_record: window [%d, %d + %d) is empty or negative", i_base, i_base, n_slots);
+    oa.rec = d_rec;
+    oa.i_base = i_base;
+    oa.n_slots = n_slots;
     return 0;
 }
 

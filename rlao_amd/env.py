@@ -317,7 +317,8 @@ def resolve_science(R: int, zero_padding=4, window=None, first_frame=16, log10=F
     return dict(zero_padding=zp, window=W, first_frame=int(first_frame), flags=L.SCI_LOG10 if log10 else 0, dft=dft)
 
 
-_WF_BITS = {"residual": L.WF_RESIDUAL, "atmosphere": L.WF_ATMOSPHERE}
+_WF_BITS = {"residual": L.WF_RESIDUAL, "atmosphere": L.WF_ATMOSPHERE,
+            "science": L.WF_SCIENCE}                               # (toward the science target: project_wavefront alone, on its own)
 
 
 def wavefront_bits(what) -> int:
@@ -868,6 +869,37 @@ class _SourceProxy:
             raise AttributeError(f"cannot set source.{name}")
 
 
+class _ScienceSourceProxy:
+    """``env.src`` (MAIN_CODE/OOPAOEnv/OOPAOEnv.py:140-146, 303-304: ``self.src.coordinates = [0.4, 0]``): the science target of
+    every env.  ``coordinates`` is ``[n_envs, 2]`` (zenith arcsec, azimuth deg; zeros while no direction is set); assigning one
+    pair for every env or an ``[n_envs, 2]`` array is ``set_science_direction``."""
+    tag = "source"
+    type = "NGS"
+
+    def __init__(self, env):
+        object.__setattr__(self, "_e", env)
+
+    @property
+    def wavelength(self):
+        return self._e.src_wavelength
+
+    @property
+    def coordinates(self):
+        d = self._e.science_direction
+        return np.zeros((self._e.n_envs, 2)) if d is None else d
+
+    def __setattr__(self, name, value):
+        if name != "coordinates":
+            raise AttributeError(f"cannot set src.{name}")
+        v = as_float64(value, "coordinates")
+        if v.shape == (2,):
+            self._e.set_science_direction(v[0], v[1])
+        elif v.shape == (self._e.n_envs, 2):
+            self._e.set_science_direction(np.ascontiguousarray(v[:, 0]), np.ascontiguousarray(v[:, 1]))
+        else:
+            raise ValueError(f"coordinates must be [zenith, azimuth] or have shape ({self._e.n_envs}, 2), got {v.shape}")
+
+
 class _WfsProxy:
     def __init__(self, env):
         self._e = env
@@ -1033,6 +1065,8 @@ class BatchedAOEnv:
         self._wf_rec = None                                        # the tensor of an attached wavefront record (kept alive here)
         self._sci = None                                           # resolve_science()'s dict while a science camera is set
         self._le = None                                            # (sum, sum_log10 or None, count) of an attached long exposure
+        self._oa = None                                            # [n_envs, 2] (zenith arcsec, azimuth deg) while a science direction is set
+        self._oa_rec = None                                        # the tensor of an attached science-direction record (kept alive here)
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
         self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
         self.source = self.ngs = None
@@ -1149,8 +1183,11 @@ class BatchedAOEnv:
         self._modal = self._modal_gain = self._mobs = None           # ... and no modal basis
         self._wf = self._wf_rec = None                               # ... and no wavefront basis (it is indexed by the pupil's pixels)
         self._sci = self._le = None                                  # ... and no science camera (it holds the pupil's amplitude)
+        self._oa = self._oa_rec = None                               # ... and no science direction
         self._surface = "zonal"
         sh = self._shard
+        if p.nLayer > 0 and hasattr(sh.lib, "aoenv_set_field"):     # what a science direction is computed from (absent: an A/B library of AOENV_LIB)
+            L.call(sh, "aoenv_set_field", float(p.diameter), float(p.fov), np.ascontiguousarray(p.altitude, dtype=np.float64))
         at = self._atm_tables
         sh.upload_ring_tables(at)
         sh.upload(L.C_LAYER_WEIGHT, at.weights)
@@ -1169,6 +1206,7 @@ class BatchedAOEnv:
         self.SR = []
         self.atm, self.dm, self.tel, self.wfs = _AtmProxy(self), _DmProxy(self), _TelProxy(self), _WfsProxy(self)
         self.source = self.ngs = _SourceProxy(self)
+        self.src = _ScienceSourceProxy(self)
         self.wfs.tag = "shackHartmann" if self.wfs_type == "sh" else "pyramid"
         pre, post = CAMERAS[camera]
         self.wfs.cam.configure(**{k: (p.samplingTime if v == "samplingTime" else v) for k, v in pre.items()})
@@ -1764,7 +1802,7 @@ class BatchedAOEnv:
         ``tel.OPD``, ``what="atmosphere"`` those of the pupil-masked ``atm.OPD``.  A new tensor every call."""
         self._require_wavefront()
         bits = wavefront_bits(what)
-        if bits not in (L.WF_RESIDUAL, L.WF_ATMOSPHERE):
+        if bits not in (L.WF_RESIDUAL, L.WF_ATMOSPHERE, L.WF_SCIENCE):
             raise ValueError("project_wavefront takes one of 'residual' and 'atmosphere'; record_wavefront takes both")
         out = _torch().empty((self.n_envs, self.n_wavefront_modes), device=self.device, dtype=self.tdtype)
         L.call(self._shard, "aoenv_project_wavefront", bits, out, self._stream())
@@ -1898,6 +1936,76 @@ class BatchedAOEnv:
         self._require_long_exposure()
         le, _ = self.long_exposure()
         return le.amax(dim=(1, 2)) / self._science_window(True).amax(dim=(1, 2))
+
+    # -- off-axis science target (aoenv_set_science_direction; the reference's `src.coordinates = [zenith, azimuth]`, atm * src) ----
+    def set_science_direction(self, zenith, azimuth=0.0, env_ids=None):
+        """The science target of every env: ``zenith`` [arcsec, ``0 .. fov / 2``] and ``azimuth`` [deg], scalars or one value per
+        (listed) env; the other envs keep their direction, or sit on axis if none was set.  From here on ``science_residual()``,
+        ``science_atmosphere()``, ``project_wavefront("science")``, ``science_psf()`` and the long exposure look through the layers
+        toward the target, behind the mirror surface the guide star's sensor saw (MAIN_CODE/OOPAOEnv/OOPAOEnv.py:140-146, 303-304;
+        OOPAO/Atmosphere.py:313-334, 439-450).  Bad arguments raise before anything is touched.  Not part of ``get_state``."""
+        cur = self._oa if self._oa is not None else np.zeros((self.n_envs, 2))
+        zen = assign_per_env(zenith, env_ids, self.n_envs, cur[:, 0], "zenith")
+        az = assign_per_env(azimuth, env_ids, self.n_envs, cur[:, 1], "azimuth")
+        fov = float(self.param.fov)
+        if (zen < 0).any() or (zen > fov / 2).any():
+            raise ValueError(f"zenith must lie in [0, fov / 2 = {fov / 2}] arcsec")
+        L.call(self._shard, "aoenv_set_science_direction", zen, az, self._stream())
+        self._oa = np.stack([zen, az], axis=1)
+
+    def clear_science_direction(self):
+        """No science direction: the science camera looks at the guide star again, a record is detached, nothing is left behind."""
+        L.call(self._shard, "aoenv_set_science_direction", None, None, self._stream())
+        self._oa = self._oa_rec = None
+
+    @property
+    def science_direction(self):
+        """``[n_envs, 2]`` (zenith arcsec, azimuth deg) as the library holds it, None while no direction is set."""
+        if self._oa is None:
+            return None
+        zen, az = np.zeros(self.n_envs), np.zeros(self.n_envs)
+        L.call(self._shard, "aoenv_get_science_direction", zen, az)
+        return np.stack([zen, az], axis=1)
+
+    def _require_science_direction(self):
+        if self._oa is None:
+            raise L.AoEnvError("no science direction is set: call set_science_direction() first")
+
+    def science_residual(self):
+        """``(phase, rms_nm, strehl)`` toward the science target of the buffers as they stand: the residual phase ``[n_envs, R, R]``
+        [rad at the source wavelength], ``std(OPD[pupil]) * 1e9`` and ``exp(-var(phase[pupil]))`` per env.  New tensors every call."""
+        self._require_science_direction()
+        torch = _torch()
+        phase = torch.empty((self.n_envs, self.R, self.R), device=self.device, dtype=self.tdtype)
+        rms = torch.empty((self.n_envs,), device=self.device, dtype=self.tdtype)
+        sr = torch.empty_like(rms)
+        L.call(self._shard, "aoenv_science_residual", phase, None, rms, sr, self._stream())
+        return self._out(phase), self._out(rms), self._out(sr)
+
+    def science_atmosphere(self):
+        """``atm.OPD_no_pupil`` toward the science target, ``[n_envs, R, R]`` metres."""
+        self._require_science_direction()
+        opd = _torch().empty((self.n_envs, self.R, self.R), device=self.device, dtype=self.tdtype)
+        L.call(self._shard, "aoenv_science_residual", None, opd, None, None, self._stream())
+        return self._out(opd)
+
+    def record_science_direction(self, i0: int, n_steps: int):
+        """Attaches a record ``[n_steps, 2, n_envs]`` (a new device tensor, returned: rms nm, then Strehl, toward the target) that
+        every stepped frame ``i0 <= i < i0 + n_steps`` of every loop fills: slot ``i - i0`` is what ``science_residual()`` gives
+        after that step.  The loops' results do not change by a bit.  A call whose frames leave the window is refused;
+        ``stop_science_direction_record()`` detaches."""
+        self._require_science_direction()
+        if int(n_steps) < 1 or int(i0) < 0:
+            raise ValueError("record_science_direction: i0 >= 0 and n_steps >= 1")
+        rec = _torch().zeros((int(n_steps), 2, self.n_envs), device=self.device, dtype=self.tdtype)
+        L.call(self._shard, "aoenv_set_science_direction_record", rec, int(i0), int(n_steps))
+        self._oa_rec = rec
+        return rec
+
+    def stop_science_direction_record(self):
+        """Detaches the record; the loops run as without one."""
+        L.call(self._shard, "aoenv_set_science_direction_record", None, 0, 0)
+        self._oa_rec = None
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

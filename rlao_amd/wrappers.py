@@ -162,6 +162,33 @@ class TorchWrapper:
     def science_psf(self, flat=False):
         return self._env.science_psf(flat)
 
+    def set_science_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_science_direction(zenith, azimuth, env_ids)
+
+    def clear_science_direction(self):
+        return self._env.clear_science_direction()
+
+    @property
+    def science_direction(self):
+        return self._env.science_direction
+
+    @property
+    def src(self):
+        return self._env.src
+
+    def science_residual(self):
+        return self._env.science_residual()
+
+    def science_atmosphere(self):
+        return self._env.science_atmosphere()
+
+    def record_science_direction(self, i0, n_steps):
+        """``BatchedAOEnv.record_science_direction``: the record itself, in the env dtype (the library writes into this very tensor)."""
+        return self._env.record_science_direction(i0, n_steps)
+
+    def stop_science_direction_record(self):
+        return self._env.stop_science_direction_record()
+
     def long_exposure(self):
         return self._env.long_exposure()
 
@@ -313,6 +340,26 @@ class TimeDelayEnv:
     def science_psf(self, flat=False):
         return self._env.science_psf(flat)
 
+    def set_science_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_science_direction(zenith, azimuth, env_ids)
+
+    def clear_science_direction(self):
+        return self._env.clear_science_direction()
+
+    @property
+    def science_direction(self):
+        return self._env.science_direction
+
+    @property
+    def src(self):
+        return self._env.src
+
+    def science_residual(self):
+        return self._env.science_residual()
+
+    def science_atmosphere(self):
+        return self._env.science_atmosphere()
+
     def long_exposure(self):
         return self._env.long_exposure()
 
@@ -441,6 +488,26 @@ class HistoryEnv:
 
     def science_psf(self, flat=False):
         return self._env.science_psf(flat)
+
+    def set_science_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_science_direction(zenith, azimuth, env_ids)
+
+    def clear_science_direction(self):
+        return self._env.clear_science_direction()
+
+    @property
+    def science_direction(self):
+        return self._env.science_direction
+
+    @property
+    def src(self):
+        return self._env.src
+
+    def science_residual(self):
+        return self._env.science_residual()
+
+    def science_atmosphere(self):
+        return self._env.science_atmosphere()
 
     def long_exposure(self):
         return self._env.long_exposure()
