@@ -848,6 +848,13 @@ int aoenv_test_normal(int device, uint32_t seed, int n, int n_calls, double* h_o
 int aoenv_test_poisson_table(uint32_t* h_out, size_t cap_words, size_t* h_words);
 int aoenv_test_poisson(int device, const float* h_lambda, int n, uint64_t seed, uint32_t frame, float lmax, float* h_out);
 
+/* Test hook of the fused step kernel's LDS layouts (rlao_amd/csrc/step_kernel.hip; host only, no GPU needed), for a geometry of
+ * n_act actuators across, n_subap lenslets across, n_valid valid lenslets and n_modes modes:
+ *   h_out[0] = words (4 bytes) of a launch of one step, h_out[1] = of a launch of two steps (AOENV_OPT_STEP_PAIRS), which has words
+ *   of its own for the first step's slopes, from h_out[2], and modal coefficients, from h_out[3]; h_out[4] = the bytes a workgroup
+ *   has for either; h_out[5] = 1 if a photon-noise launch of this geometry may cover two steps, 0 if it runs one launch per step. */
+int aoenv_test_step_lds(int n_act, int n_subap, int n_valid, int n_modes, int32_t* h_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,11 +164,12 @@ EXPORTS = {
     "aoenv_test_normal": (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "aoenv_test_poisson_table": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "aoenv_test_poisson": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p]),
+    "aoenv_test_step_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 
 _LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
-                  "aoenv_science_residual", "aoenv_set_science_direction_record")
+                  "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds")
 
 
 class AoEnvError(RuntimeError):

@@ -1085,6 +1085,10 @@ bool step_pair_eligible(AoEnv* env) {
     StepArgs a{};                                                  // what the choice of the instantiation reads
     a.sc = sh_const<float>(env);
     a.det = env->det;
+    a.k.n_act = env->nAct;                                         // ... and the pair's LDS layout
+    a.n_subap = env->nSub;
+    a.n_valid = env->nVal;
+    a.n_modes = env->n_modes;
     return env_step_pairable(a, env->star_env<float>());
 }
 

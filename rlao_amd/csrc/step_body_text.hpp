@@ -1,11 +1,14 @@
 // The body of the fused step kernel as TEXT (step_kernel_body.hpp includes it: once in k_env_step_sh6, twice in k_env_step_pair_sh6).
 // No include guard.  The including kernel has the by-value arguments `a`, `L`, `star` in scope and defines STEP_BODY_SUB:
 //   0  a launch of one step: the text below is then, token for token, the kernel it always was
-//   1  the first step of a pair: it is never a call's last, so it stores neither phase nor frame nor atmosphere, and leaves the
-//      lane's command and observation and lane 0's return in carry_cn / carry_o / carry_ret
-//   2  the second step of a pair, in a scope of its own behind a workgroup barrier: a step in which no layer crosses a pixel -- no
-//      ring, no gather, no range scan (lohi[] of the first stands in LDS), taps from StepArgs::taps2, telemetry index and frame
-//      counter plus one, and the command, the observation, the integrator's state and the return from the carry_* registers:
+//   1  the first step of a pair: it is never a call's last, so it stores neither phase nor frame nor atmosphere.  It ends behind
+//      its centre of gravity: the slopes go to the pair's own LDS (StepLds::pair), the lane's next command to carry_cn -- it
+//      depends on the observation of the step BEFORE this one, not on this step's -- and its reconstruction is left to the second
+//      copy.  On its last barriers it builds the second step's Gy C in s1, which is that step's prologue.
+//   2  the second step of a pair, in a scope of its own behind a workgroup barrier (which also means "s1 complete"): a step in
+//      which no layer crosses a pixel -- no ring, no gather, no range scan (lohi[] of the first stands in LDS), no prologue barrier,
+//      taps from StepArgs::taps2, telemetry index and frame counter plus one, the command from carry_cn.  Its stage C reconstructs
+//      both steps with one fetch of the rows of M and M2C^T, and stores coefs, dm_prev, obs, reward and the return once:
 //      nothing the launch wrote to global memory is read back.  `a`, `L`, `star`, tid2, e2 are the scope's opaque copies.
 // A function would have to be handed the kernel's by-value arguments by reference; the instantiations at the 128-register ceiling
 // then spill, and the compiler's contraction choices move.
@@ -19,7 +22,9 @@
     const KArgs<float>& k = a.k;
     const int R = k.R, nA = k.n_act, S = k.pa.S;
     const int nAp = (nA + 3) & ~3, SS = nAp + 1;
+#if STEP_BODY_SUB != 2
     float* cimg = lds + L.cimg;                                  // [nA][nA] command image
+#endif
     float* s1 = lds + L.s1;                                      // [2 PR][SS]  Gy C, every row
 #if STEP_BODY_SUB != 2
     const int w_ = threadIdx.x >> 6;
@@ -29,8 +34,12 @@
     float* mapt = lds + L.mapt + w_ * (WR * WC);                   // [WR][WC] this wave's private layer tile
     short* slot_s = reinterpret_cast<short*>(lds + L.slot);      // [nSub^2] lenslet -> compact valid index or -1
     cplx<float>* E0 = reinterpret_cast<cplx<float>*>(lds + L.e0);    // [nValid][EST]
+#if STEP_BODY_SUB != 1
     float* sl = lds + L.sl;                                      // [2 nValid] slopes            (aliases E0: behind the threshold barrier)
     float* img_s = lds + L.img;                                  // [nA^2 + n_modes]             (aliases E0: stage C)
+#else
+    float* sl = lds + L.pair;                                    // [2 nValid] (the pair's own words: E0 is the second step's before they are read)
+#endif
     const uint32_t* tab_s = reinterpret_cast<const uint32_t*>(lds + L.tab);   // camera: alias tables (alias cimg, s1, the layer tiles: stage B)
 #if STEP_BODY_SUB != 2
     __shared__ double red[4][16];
@@ -58,32 +67,33 @@
 #else
     const float ctab = (float)fast6::kCos[lane % 24];            // (cos_table_lane() of the scope's own lane index)
 #endif
+#if STEP_BODY_SUB != 2
     f32x4s gx_raw[2][2], gy_raw[2];
+#else
+    f32x4s gx_raw[2][2];                                         // (Gy C of this step stands in s1: the tail of the first copy)
+#endif
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
         const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gxa + e * a.ga_env) + (2 * cg + tt) * 2 * 64 + (tid & 63);   // ga_index(), stride 8
         gx_raw[tt][0] = src[0];
         gx_raw[tt][1] = src[64];
     }
+#if STEP_BODY_SUB != 2
     const int rt = w >> 1, ct = w & 1;                           // s1 tile of this wave: rows 16 rt.., command columns 16 ct..
     {
         const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gya + e * a.ga_env) + rt * 2 * 64 + (tid & 63);   // gy[16 rt + lc][lq + 4 step]
         gy_raw[0] = src[0];
         gy_raw[1] = src[64];
     }
-#if STEP_BODY_SUB != 2
     float mm_pre[kMaxLayer];                                     // stored range of every layer's screen (lane & 1: min / max)
 #pragma unroll
     for (int l = 0; l < kMaxLayer; ++l)
         mm_pre[l] = l < k.pa.n_layer ? static_cast<const float*>(k.pa.minmax[l])[2 * e + (tid & 1)] : 0.f;
 #endif
     const bool has_act = tid < k.n_valid_act;                    // n_valid_act <= 1024 (n_act <= 32)
-    const int act_px = k.pb.act_idx[has_act ? tid : 0];
 #if STEP_BODY_SUB != 2
+    const int act_px = k.pb.act_idx[has_act ? tid : 0];
     const float act_c = k.pb.coefs[(size_t)e * k.n_valid_act + (has_act ? tid : 0)];
-#else
-    const float act_c = carry_cn;                                // the command this lane formed a step ago
-#endif
     const short slot_v = a.slot_of[tid < n_sub * n_sub ? tid : 0];
     for (int i = tid; i < nA * nA; i += 1024) cimg[i] = 0.f;
     for (int i = tid; i < 2 * PR * SS; i += 1024) s1[i] = 0.f;
@@ -91,6 +101,7 @@
     for (int i = tid + 1024; i < n_sub * n_sub; i += 1024) slot_s[i] = a.slot_of[i];
     lds_barrier();
     if (has_act) cimg[act_px] = act_c;
+#endif   // (second step of a pair: cimg and s1 were made in the first copy's tail, slot_s stands)
     float breg[2][KS];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
@@ -100,6 +111,7 @@
         for (int ks = 0; ks < KS; ++ks) breg[tt][ks] = t[ks];
     }
 
+#if STEP_BODY_SUB != 2
     // ---- s1[y][ix] = sum_iy gy[y][iy] C[iy][ix] for every row, on the matrix cores: 8 x 2 tiles of 16 x 16, one per wave ---
     lds_barrier();                                             // cimg complete
     {
@@ -124,7 +136,6 @@
         }
     }
 
-#if STEP_BODY_SUB != 2
     // ---- deferred ring scatter: map_full[outerMask] = X of a layer that crossed a pixel this step ----------------------------
     // The ring values are the fixed-order sum of the GEMM's split-K slabs, written through the torus origin.  This
     // workgroup is the only reader of this env's map in this launch, and its vector L1 holds no line of it yet (no load of
@@ -210,7 +221,7 @@
             mm[0] = lo; mm[1] = hi;
         }
     }
-#endif   // (second step of a pair: no ring, no gather, lohi[] of the first stands)
+#endif   // (second step of a pair: s1 = Gy C from the first copy's tail, no ring, no gather, lohi[] of the first stands)
 
     // Lane -> pixel map of a pass (64 rows): wave = (band = w >> 2: 16 rows, cg = w & 3: 32 columns = 2 tiles of 16);
     // in a tile the lane owns ONE row y = 16 band + (lane & 15) and FOUR CONSECUTIVE columns x = 16 tile + 4 (lane >> 4) + r.
@@ -223,7 +234,9 @@
         const int tye = min(PR, R - y0);
         const int yl = 16 * band + lc, y = y0 + yl;              // the lane's row
         const bool row_ok = yl < tye;
+#if STEP_BODY_SUB != 2
         if (pass == 0) lds_barrier();                            // s1 and the screen ranges complete
+#endif   // (second step of a pair: that is the barrier between the copies)
         // pupil + WFS amplitude of the lane's 2 x 4 pixels (one table: amplitude, or -1 outside the pupil), long before use
         f32x4s apv[2];
 #pragma unroll
@@ -446,6 +459,16 @@
     //  hoisted to the top of the kernel, where 40 more live registers spill)
     int late0;
     asm volatile("v_mov_b32 %0, 0" : "=v"(late0) : "v"(mx));
+#if STEP_BODY_SUB == 1
+    // (the first step of a pair requests no row of M or M2C^T: the second copy's stage C reconstructs both steps with one fetch.
+    //  In their place: the Gy operand of the second step's command product, which this copy forms on its last barriers)
+    f32x4s gy_nx[2];
+    {
+        const f32x4s* src = reinterpret_cast<const f32x4s*>(a.gya + e * a.ga_env) + rt * 2 * 64 + (tid & 63) + late0;
+        gy_nx[0] = src[0];
+        gy_nx[1] = src[64];
+    }
+#else
     const int n_sig = 2 * n_valid, n4 = n_sig / 4, A = k.n_valid_act;
     const int km = tid >> 4, l16 = tid & 15;                     // (host: n_modes <= 52, nSig % 4 == 0, nSig <= 640)
     f32x4s mv[10];
@@ -459,20 +482,24 @@
 #pragma unroll
         for (int j = 0; j < 10; ++j) mv[j] = f32x4s{0.f, 0.f, 0.f, 0.f};
     }
+#endif
     const float ref0 = a.sc.ref[ok ? s : 0], ref1 = a.sc.ref[ok ? n_valid + s : 0];
     // the integrator's inputs of this lane's actuator -- the previous observation (or the caller's action) and env.dm_prev
     // (OOPAOEnv.py:508) -- are requested here too: held from the prologue on they were two more live registers across stages A and B
 #if STEP_BODY_SUB == 2
-    float act_prev = carry_o, dm_prev_c = carry_cn;              // (a pair: do_integrate and gain_from_obs != 0, launch_env_step_pair)
-    if (false) {
+    // (a pair: do_integrate and gain_from_obs != 0, launch_env_step_pair.  The state is the command the first copy formed; the
+    //  input is that copy's observation, which the joint pass of stage C below reconstructs.  The lane's image index, which the
+    //  other copies hold from the prologue on, is requested here)
+    const float dm_prev_c = carry_cn;
+    const int act_px = k.pb.act_idx[(has_act ? tid : 0) + late0];
 #else
     float act_prev = 0.f, dm_prev_c = 0.f;
     if (a.fa.do_integrate) {
-#endif
         const size_t io = (size_t)e * (nA * nA) + (has_act ? act_px : 0) + late0;
         act_prev = (a.fa.gain_from_obs != 0.f) ? a.fa.obs[io] : a.fa.action[io];
         dm_prev_c = a.fa.dm_prev[(size_t)e * k.n_valid_act + (has_act ? tid : 0) + late0];
     }
+#endif
     for (int off = 32; off > 0; off >>= 1) {
         const float o = __shfl_down(mx, off);
         mx = o > mx ? o : mx;
@@ -485,7 +512,15 @@
     if (tid == 0) a.wfs_max[e] = mx;
     // (aliases E0: every wave has its spots by now) zero at non-actuators: vec_to_img.  Stage C writes the actuators' values two
     // barriers from here.
+#if STEP_BODY_SUB != 1
     for (int i = tid; i < nA * nA; i += 1024) img_s[i] = 0.f;
+#else
+    // (the first step of a pair has no image.  Every wave has left the camera: the tables' region is dead, and the second step's
+    //  command image and Gy C are zeroed there instead -- that step's prologue, on this copy's barriers.  The slopes go to the
+    //  pair's own words: `sl` lies in E0, which stage A of the second step overwrites.)
+    for (int i = tid; i < nA * nA; i += 1024) cimg[i] = 0.f;
+    for (int i = tid; i < 2 * PR * SS; i += 1024) s1[i] = 0.f;
+#endif
     float cut;
     if constexpr (STAR) cut = (star.thr ? star.thr[e] : a.sc.threshold) * mx;
     else cut = a.sc.threshold * mx;
@@ -517,6 +552,7 @@
     }
     lds_barrier();
 
+#if STEP_BODY_SUB == 0
     // ---- stage C ------------------------------------------------------------------------------------------------------------
     // Same arithmetic as tail_from_slopes (sh_device.hpp), with every operand that does not depend on the slopes already
     // in registers: t = M s ; o = -M2C t 1e6 ; integrator ; obs image ; reward          (MAIN/OOPAOEnv/OOPAOEnv.py:491-536)
@@ -529,12 +565,7 @@
         for (int j = 0; j < 10; ++j) {
             const bool okj = l16 + 16 * j < n4;
             const f32x4s sv = s4[okj ? l16 + 16 * j : 0];
-#if STEP_BODY_SUB == 0
             const float d = ((mv[j][0] * sv[0] + mv[j][1] * sv[1]) + mv[j][2] * sv[2]) + mv[j][3] * sv[3];
-#else
-            // (likewise: a launch of one step rounds mv1 sv1 and chains three fmas onto it)
-            const float d = __builtin_fmaf(mv[j][3], sv[3], __builtin_fmaf(mv[j][2], sv[2], __builtin_fmaf(mv[j][0], sv[0], mv[j][1] * sv[1])));
-#endif
             acc += okj ? d : 0.f;
         }
 #pragma unroll
@@ -577,21 +608,11 @@
             const float mine = part == 0 ? acc[0] : (part == 1 ? acc[1] : (part == 2 ? acc[2] : acc[3]));
             if (a.fa.do_integrate) {
                 const float act = (a.fa.gain_from_obs != 0.f) ? a.fa.gain_from_obs * act_prev : act_prev;
-#if STEP_BODY_SUB == 0
                 const float cn = dm_prev_c * a.fa.leak + act * 1e-6f;                    // float32 increment (k_recon_finish)
-#else
-                // the contraction written out -- the rounded increment, then one fma, which is what the compiler makes of the line
-                // above in every launch of one step: left to it, the first step of a pair rounds both products (a packed multiply)
-                const float cn = __builtin_fmaf(dm_prev_c, a.fa.leak, act * 1e-6f);
-                carry_cn = cn;
-#endif
                 a.fa.coefs[(size_t)e * A + tid] = cn;
                 a.fa.dm_prev[(size_t)e * A + tid] = cn;
             }
             const float o = -mine * 1e6f;
-#if STEP_BODY_SUB == 1
-            carry_o = o;
-#endif
             img_s[act_px] = o;
             ss += (double)o * (double)o;
         }
@@ -608,18 +629,152 @@
         double tot = 0;
         for (int q = 0; q < 16; ++q) tot += red_tail[q];
         if (a.fa.reward) a.fa.reward[e] = (float)(-sqrt(tot));
-#if STEP_BODY_SUB == 0
         if (a.fa.ret && a.fa.do_integrate) a.fa.ret[e] += (float)(-sqrt(tot));
-#else
-        if (a.fa.ret && a.fa.do_integrate) {
-#if STEP_BODY_SUB == 1
-            carry_ret = a.fa.ret[e];
-#endif
-            carry_ret += (float)(-sqrt(tot));
-            a.fa.ret[e] = carry_ret;
-        }
-#endif
     }
+#elif STEP_BODY_SUB == 1
+    // ---- the first step of a pair ends behind its centre of gravity --------------------------------------------------------
+    // The command of the next step, c_{k+1} = leak c_k + gain 1e-6 obs_{k-1} (the reference's one-frame delay, OOPAOEnv.py:508),
+    // depends on the observation the step BEFORE this one stored, not on this step's: it is complete here.  This step's own
+    // reconstruction (t = M s_k from the slopes above, o_k, the reward) is needed only by the integrator at the end of the second
+    // copy, whose stage C forms it beside its own from one fetch of the rows of M and M2C^T; coefs, dm_prev, obs and reward,
+    // which that copy overwrites unread, are not stored.  The contraction is written out -- the rounded increment, then one fma,
+    // which is what the compiler makes of `dm_prev * leak + act * 1e-6f` in every launch of one step: left to it, this copy rounds
+    // both products (a packed multiply).
+    if (has_act && a.fa.do_integrate) {
+        const float act = (a.fa.gain_from_obs != 0.f) ? a.fa.gain_from_obs * act_prev : act_prev;
+        carry_cn = __builtin_fmaf(dm_prev_c, a.fa.leak, act * 1e-6f);
+    }
+    // ---- the second step's prologue: its command image (zeroed behind the threshold barrier) and s1 = Gy C, as at the top ----
+    if (has_act) cimg[act_px] = carry_cn;
+    lds_barrier();                                             // cimg complete
+    {
+        const int ix = 16 * ct + lc;
+        float av[KS], bv[KS];
+        {
+            const float t[8] = {gy_nx[0][0], gy_nx[0][1], gy_nx[0][2], gy_nx[0][3], gy_nx[1][0], gy_nx[1][1], gy_nx[1][2], gy_nx[1][3]};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) av[ks] = t[ks];
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int iy = lq + 4 * ks;
+            bv[ks] = ld_or0(cimg, iy * nA + ix, iy < nA && ix < nA);
+        }
+        f32x4s d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) d = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ks], bv[ks], d, 0, 0, 0);
+        if (ix < nA) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s1[(16 * rt + 4 * lq + r) * SS + ix] = d[r];
+        }
+    }
+    // (the barrier between the copies, step_kernel_body.hpp, then also means "s1 complete")
+#else
+    // ---- stage C of both steps of a pair: one pass over the rows of M and of M2C^T ------------------------------------------
+    // Every sum has the operands and the order it has in a launch of one step; each operand register serves two steps.
+    //   t_k = M s_k (the first copy's slopes, StepLds::pair), t_k1 = M s_k1 ; o = -M2C t 1e6 for both ;
+    //   c_{k+2} = leak c_{k+1} + gain 1e-6 o_k ; the image, obs and reward of the second step ; return += r_k, then r_k1
+    const int img = nA * nA;
+    float* tm = img_s + img;                                     // [K] modal coefficients of this step
+    float* tm_k = lds + L.pair_tm;                               // [K] ... and of the first step
+    {
+        const f32x4s* s4 = reinterpret_cast<const f32x4s*>(sl);
+        const f32x4s* s4k = reinterpret_cast<const f32x4s*>(lds + L.pair);
+        float acc = 0.f, acck = 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+            const bool okj = l16 + 16 * j < n4;
+            const f32x4s sv = s4[okj ? l16 + 16 * j : 0], svk = s4k[okj ? l16 + 16 * j : 0];
+            // (a launch of one step rounds mv1 sv1 and chains three fmas onto it)
+            const float d = __builtin_fmaf(mv[j][3], sv[3], __builtin_fmaf(mv[j][2], sv[2], __builtin_fmaf(mv[j][0], sv[0], mv[j][1] * sv[1])));
+            const float dk = __builtin_fmaf(mv[j][3], svk[3], __builtin_fmaf(mv[j][2], svk[2], __builtin_fmaf(mv[j][0], svk[0], mv[j][1] * svk[1])));
+            acc += okj ? d : 0.f;
+            acck += okj ? dk : 0.f;
+        }
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) {
+            acc += __shfl_xor(acc, off, 16);
+            acck += __shfl_xor(acck, off, 16);
+        }
+        if (km < a.n_modes && l16 == 0) {
+            tm[km] = acc;
+            tm_k[km] = acck;
+        }
+    }
+    // M2C^T rows for the lane's group of 4 actuators (4 lanes per group, lane part p takes the modes p, p + 4, ...):
+    // requested before the barrier, they do not depend on t
+    const int n_grp = (A + 3) / 4, g = tid >> 2, part = tid & 3;
+    const bool g_ok = g < n_grp;
+    f32x4s cv[13];
+    int late1;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(late1) : "v"(late0));
+    if (16 * w < n_grp) {                                        // (wave-uniform: a wave holds the groups 16 w .. 16 w + 15)
+#pragma unroll
+        for (int j = 0; j < 13; ++j)
+            __builtin_memcpy(&cv[j], a.fac_m2c_t + (part + 4 * j < a.n_modes ? (size_t)(part + 4 * j) * A + 4 * (g_ok ? g : 0) : 0) + late1, 16);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 13; ++j) cv[j] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    }
+    lds_barrier();
+    double ss = 0.0, ssk = 0.0;
+    {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f}, acck[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 13; ++j) {
+            const bool okj = part + 4 * j < a.n_modes;
+            const float t = tm[okj ? part + 4 * j : 0], tk = tm_k[okj ? part + 4 * j : 0];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) acc[d] += okj ? cv[j][d] * t : 0.f;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) acck[d] += okj ? cv[j][d] * tk : 0.f;
+        }
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            acc[d] += __shfl_xor(acc[d], 1, 4);
+            acc[d] += __shfl_xor(acc[d], 2, 4);
+            acck[d] += __shfl_xor(acck[d], 1, 4);
+            acck[d] += __shfl_xor(acck[d], 2, 4);
+        }
+        // lane tid finishes actuator k = tid (= 4 g + part) of both steps
+        if (has_act) {
+            const float mine = part == 0 ? acc[0] : (part == 1 ? acc[1] : (part == 2 ? acc[2] : acc[3]));
+            const float minek = part == 0 ? acck[0] : (part == 1 ? acck[1] : (part == 2 ? acck[2] : acck[3]));
+            const float o_k = -minek * 1e6f;                       // the first step's observation: this step's integrator input
+            {
+                const float act = (a.fa.gain_from_obs != 0.f) ? a.fa.gain_from_obs * o_k : o_k;
+                // (the contraction written out, as in the first copy)
+                const float cn = __builtin_fmaf(dm_prev_c, a.fa.leak, act * 1e-6f);
+                a.fa.coefs[(size_t)e * A + tid] = cn;
+                a.fa.dm_prev[(size_t)e * A + tid] = cn;
+            }
+            const float o = -mine * 1e6f;
+            img_s[act_px] = o;
+            ssk += (double)o_k * (double)o_k;
+            ss += (double)o * (double)o;
+        }
+    }
+    lds_barrier();
+    {
+        float* ob = a.fa.obs + (size_t)e * img;
+        for (int q = tid; q < img; q += 1024) ob[q] = img_s[q];
+    }
+    ssk = wave_sum_f64(ssk);
+    ss = wave_sum_f64(ss);
+    if (lane == 0) {
+        red[0][w] = ssk;                                         // (the pupil sums there were consumed in front of the spots)
+        red_tail[w] = ss;
+    }
+    lds_barrier();
+    if (tid == 0) {
+        double totk = 0, tot = 0;
+        for (int q = 0; q < 16; ++q) totk += red[0][q];
+        for (int q = 0; q < 16; ++q) tot += red_tail[q];
+        if (a.fa.reward) a.fa.reward[e] = (float)(-sqrt(tot));
+        // the return takes the first step's reward, then the second's: what two launches add to it one after the other
+        if (a.fa.ret && a.fa.do_integrate) a.fa.ret[e] = (a.fa.ret[e] + (float)(-sqrt(totk))) + (float)(-sqrt(tot));
+    }
+#endif
 #undef STEP_BODY_DET
 #undef STEP_BODY_STORE_FRAME
 #undef STEP_BODY_SUB

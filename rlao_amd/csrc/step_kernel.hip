@@ -7,7 +7,7 @@
 
 namespace ao {
 
-static StepLds step_lds_layout(int n_act, int n_subap, int n_valid, int n_modes) {
+StepLds step_lds_layout(int n_act, int n_subap, int n_valid, int n_modes) {
     using namespace fstep;
     StepLds L;
     const int nAp = (n_act + 3) & ~3, SS = nAp + 1;
@@ -28,6 +28,18 @@ static StepLds step_lds_layout(int n_act, int n_subap, int n_valid, int n_modes)
     L.sl = L.e0;
     L.img = L.e0 + sl_words;
     L.total = o;
+    L.pair = L.pair_tm = 0;
+    return L;
+}
+
+// A launch of two steps: the first copy's slopes (2 n_valid words) and modal coefficients (n_modes words) behind everything else.
+// `sl` and `img` lie in E0, which stage A of the second step overwrites while the first step's slopes are still to be
+// reconstructed.  At C2 (316 valid lenslets, 50 modes): 632 + 52 = 684 words, 2 736 bytes.
+StepLds step_pair_lds_layout(int n_act, int n_subap, int n_valid, int n_modes) {
+    StepLds L = step_lds_layout(n_act, n_subap, n_valid, n_modes);
+    L.pair = L.total;
+    L.pair_tm = L.pair + ((2 * n_valid + 3) & ~3);
+    L.total = L.pair_tm + ((n_modes + 3) & ~3);
     return L;
 }
 
@@ -37,7 +49,7 @@ int step_fused_supported(int R, int n_subap, int n_valid, int n_act, int n_modes
     if (n_valid > 16 * 21 || n_subap * n_subap > 32767 || n_act > 32) return 0;
     if (n_modes < 1 || n_modes > 52 || (2 * n_valid) % 4 != 0 || 2 * n_valid > 640) return 0;   // stage C register blocking
     const StepLds L = step_lds_layout(n_act, n_subap, n_valid, n_modes);
-    return (size_t)L.total * 4 <= 160 * 1024 - 1024 ? 1 : 0;     // static __shared__ of the kernel: < 1 KB
+    return (size_t)L.total * 4 <= (size_t)kStepLdsBytes ? 1 : 0;     // static __shared__ of the kernel: < 1 KB
 }
 
 // words of LDS the fused kernel has for the camera's alias tables (where stage A's buffers were): the env keeps the part of the
@@ -83,11 +95,13 @@ bool env_step_pairable(const StepArgs& a, const StarEnv<float>& star) {
     // exact and every form gives the same slopes; with float pixels (the ideal detector, read-out noise or a quantum efficiency
     // without an ADC) the slopes of a pair differed from one launch per step in the last bit, so those launches do not pair.
     if (a.k.pa.env_taps != nullptr) return false;
+    // ... and only where the pair's own LDS words fit beside the single step's layout; otherwise one launch per step, as before
+    if ((size_t)step_pair_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes).total * 4 > (size_t)kStepLdsBytes) return false;
     return s == STEP_PHOTON || (s == STEP_CAMERA && a.det.bits > 0 && a.det.bits <= 21);   // (5 (2^bits - 1) < 2^24)
 }
 
 int launch_env_step_pair(const StepArgs& a, hipStream_t st) {
-    const StepLds L = step_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
+    const StepLds L = step_pair_lds_layout(a.k.n_act, a.n_subap, a.n_valid, a.n_modes);
     const StarEnv<float> star{nullptr, nullptr};
     if (!env_step_pairable(a, star)) return fail("internal: a step pair on a launch that has no pair kernel");
     // (the second step takes the integrator's inputs from the first one's registers)
@@ -100,3 +114,24 @@ int launch_env_step_pair(const StepArgs& a, hipStream_t st) {
 }
 
 }  // namespace ao
+
+extern "C" int aoenv_test_step_lds(int n_act, int n_subap, int n_valid, int n_modes, int32_t* h_out) {
+    using namespace ao;
+    if (!h_out || n_act < 1 || n_subap < 1 || n_valid < 1 || n_modes < 1) return fail("aoenv_test_step_lds: bad arguments");
+    const StepLds one = step_lds_layout(n_act, n_subap, n_valid, n_modes), two = step_pair_lds_layout(n_act, n_subap, n_valid, n_modes);
+    StepArgs a{};                                                  // a photon-noise launch of this geometry: pairable but for the layout
+    a.sc.fast_trig = 1;
+    a.det.active = a.det.photon_noise = 1;
+    a.det.qe = a.det.gain = 1.f;
+    a.k.n_act = n_act;
+    a.n_subap = n_subap;
+    a.n_valid = n_valid;
+    a.n_modes = n_modes;
+    h_out[0] = one.total;
+    h_out[1] = two.total;
+    h_out[2] = two.pair;
+    h_out[3] = two.pair_tm;
+    h_out[4] = kStepLdsBytes;
+    h_out[5] = env_step_pairable(a, StarEnv<float>{nullptr, nullptr}) ? 1 : 0;
+    return 0;
+}

@@ -25,7 +25,15 @@ constexpr int NV4 = (WR * WC4 + 63) / 64;              // 16-byte staging loads 
 struct StepLds {
     int cimg, s1, mapt, slot, e0, sl, img, total;      // offsets in 4-byte words
     int tab, tab_cap;                                  // the camera's alias tables (stage B) and the words there are for them
+    // a launch of two steps only (step_pair_lds_layout; 0 otherwise): the first step's slopes and modal coefficients, in words
+    // that no stage of the second step aliases -- its stage C reconstructs both steps
+    int pair, pair_tm;
 };
+
+// the layouts (step_kernel.hip); what a workgroup has for them beside the kernels' static __shared__ (< 1 KB)
+constexpr int kStepLdsBytes = 160 * 1024 - 1024;
+StepLds step_lds_layout(int n_act, int n_subap, int n_valid, int n_modes);
+StepLds step_pair_lds_layout(int n_act, int n_subap, int n_valid, int n_modes);   // the same, plus the pair's words at the end
 
 template <int SPEC>
 int launch_env_step_spec(const StepArgs& a, const StepLds& L, const StarEnv<float>& star, hipStream_t st);

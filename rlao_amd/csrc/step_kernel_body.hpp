@@ -74,13 +74,17 @@ __global__ void __launch_bounds__(1024) k_env_step_sh6(const StepArgs a, const S
 // The second copy reads the kernel arguments, the lane and the env through values the compiler cannot tie to the first copy's
 // (an opaque zero added to the arguments' addresses, opaque copies of the indices): what it would otherwise keep in registers
 // from one copy into the other -- every argument, every lane address -- is more than the 128 registers a 1024-lane workgroup has.
+// The integrator's command for step k + 1 does not depend on the observation of step k (the one-frame delay), so the first copy
+// stops behind its centre of gravity: it leaves its slopes in the pair's LDS words (step_pair_lds_layout) and the lane's next
+// command in carry_cn, and forms Gy C of the second step on its last barriers.  The second copy starts at stage A and
+// reconstructs both steps in one pass of stage C (step_body_text.hpp).
 template <int KS, int SPEC>
 __global__ void __launch_bounds__(1024) k_env_step_pair_sh6(const StepArgs a, const StepLds L, const StarEnv<float> star) {
     constexpr bool PE = false;
-    float carry_cn = 0.f, carry_o = 0.f, carry_ret = 0.f;
+    float carry_cn = 0.f;
 #define STEP_BODY_SUB 1
 #include "step_body_text.hpp"
-    lds_barrier();                                               // the second step re-uses the LDS of the first
+    lds_barrier();                                               // the second step re-uses the LDS of the first; its s1 is complete
     int kz;
     asm volatile("s_mov_b32 %0, 0" : "=s"(kz));
     const StepArgs* a_p2 = reinterpret_cast<const StepArgs*>(reinterpret_cast<const char*>(&a) + kz);
@@ -91,7 +95,7 @@ __global__ void __launch_bounds__(1024) k_env_step_pair_sh6(const StepArgs a, co
     asm volatile("" : "+s"(e2));
     // The second inclusion shadows `a`, `L`, `star` with the opaque references below and declares its own locals; from the first one
     // it takes, by name, the static LDS arrays red, red_tail, red_mx and lohi (lohi with its contents), and from this kernel's
-    // scope the registers carry_cn, carry_o, carry_ret and the opaque indices tid2, e2.
+    // scope the register carry_cn and the opaque indices tid2, e2.
     {
         const StepArgs& a = *a_p2;
         const StepLds& L = *L_p2;
