@@ -31,7 +31,25 @@ extern "C" {
 #define AOENV_ABI_VERSION 7
 
 enum { AOENV_F32 = 0, AOENV_F64 = 1 };
-enum { AOENV_WFS_SH = 0, AOENV_WFS_PYRAMID = 1 };
+/* AOENV_WFS_SH_GEOMETRIC replaces ShackHartmann(..., is_geometric=True) (OOPAO/ShackHartmann.py:382-394, 676-695; the reference's
+ * own SH initialisation calibrates in this mode, OOPAO/calibration/initialization_AO_SHWFS.py:114-127).  With phi = src.phase_no_pupil
+ * = (atm.OPD_no_pupil + dm.OPD) 2 pi / lambda_src, NOT pupil-masked, and p = R / n_subap:
+ *     gx = np.gradient(phi, axis=0) * pupil;  gy = np.gradient(phi, axis=1) * pupil      central differences, one-sided on the edges
+ *     signal = [bin(gy) | bin(gx)][valid lenslets] / units,    bin = the sum over a lenslet's p x p pixels
+ * No spots, no camera, no threshold, no reference slopes, no noise (:712-713).  Such a shard uses n_subap, n_valid_subap, n_signal,
+ * AOENV_C_SH_SUBAP_IDX (at most 32767 valid lenslets) and AOENV_C_WFS_UNITS as a Shack-Hartmann does and ignores AOENV_C_SH_REF,
+ * AOENV_C_WFS_AMP, threshold_cog and max_group; cam_res is kept so that AOENV_B_FRAME and d_frame are defined: they are zero.
+ * AoCfg has no diameter: the HOST folds the gradient's 1 / pixelSize into the uploaded units, AOENV_C_WFS_UNITS = slopes_units *
+ * pixelSize (rlao_amd keeps env.slopes_units the reference's value).
+ * The phase kernels of such a shard also store the unmasked phase (aoenv_get_phase_no_pupil); a step is the phase kernel and one launch
+ * for slopes + reconstruction + integrator (k_geo_tail) where the fused tail applies (AOENV_OPT_FUSED_TAIL, reconstructor factors,
+ * <= 1024 envs, the LDS plan of rlao_amd/csrc/sh_geometric.hpp), otherwise the stand-alone slopes kernel (k_sh_geometric, also
+ * aoenv_measure's) and the reconstruction kernels; the signal is the same bits either way.  The fused step kernel and the step
+ * pairs never run: aoenv_fused_step_active is 0.  aoenv_set_detector is accepted and has no effect (frame zero, no noise frame
+ * counted); aoenv_set_flux_env and aoenv_set_threshold_env with an array are refused: there are neither photons nor a threshold.
+ * The new launches count under AOENV_K_SH_CENTROID (stand-alone) and AOENV_K_SH_TAIL (fused) in aoenv_profile.
+ * Additive: a shard of the other two kinds runs what it ran, and the ABI version stays. */
+enum { AOENV_WFS_SH = 0, AOENV_WFS_PYRAMID = 1, AOENV_WFS_SH_GEOMETRIC = 2 };
 
 /* Geometry and loop constants of one shard.  Filled by the host (rlao_amd/calib.py) from the same
  * parameter-file keys the reference uses (MAIN/Conf/parameterFile_oopao_parser.py:19-79). */
@@ -49,7 +67,7 @@ typedef struct AoCfg {
     int32_t n_act;           /* actuators across the diameter, nSubap+1 (OOPAO/DeformableMirror.py:288) */
     int32_t n_valid_act;     /* A: controlled actuators */
     int32_t dm_separable;    /* 1: OPD = Gy C Gx^T (Cartesian Gaussian DM, no rotation); 0: dense modes GEMM */
-    int32_t wfs_type;        /* AOENV_WFS_SH | AOENV_WFS_PYRAMID */
+    int32_t wfs_type;        /* AOENV_WFS_SH | AOENV_WFS_PYRAMID | AOENV_WFS_SH_GEOMETRIC */
     int32_t n_subap;         /* lenslets (SH) / pupil samples (Pyramid) across the diameter */
     int32_t n_valid_subap;   /* SH: valid lenslets;  Pyramid: valid pixels per quadrant */
     int32_t n_signal;        /* length of wfs.signal */
@@ -741,6 +759,11 @@ int aoenv_set_return_accumulator(AoEnv* env, void* d_return);
 int aoenv_buffer(AoEnv* env, int which, void** d_ptr, size_t* bytes);
 int aoenv_download(AoEnv* env, int which, void* h_dst, size_t bytes, void* stream);
 int aoenv_upload_state(AoEnv* env, int which, const void* h_src, size_t bytes, void* stream);
+/* Replaces: reading src.phase_no_pupil (OOPAO/Telescope.py:404-412) on a geometric shard (AOENV_WFS_SH_GEOMETRIC): h_dst [n_env][R*R]
+ * in the env dtype, the unmasked phase (atm.OPD_no_pupil + dm.OPD) 2 pi / lambda_src the last phase kernel wrote -- inside the pupil
+ * AOENV_B_PHASE bit for bit (the same add and the same multiply).  Derived, not checkpoint state, and no AoBuf: the buffer exists on
+ * geometric shards only.  Synchronises the stream.  Refused: any other shard, a null pointer, bytes other than that size. */
+int aoenv_get_phase_no_pupil(AoEnv* env, void* h_dst, size_t bytes, void* stream);
 /* host-side atmosphere clock: h_buff [n_layer][2] float64 (layer.buff, OOPAO/Atmosphere.py:392-404) */
 int aoenv_get_buff(AoEnv* env, double* h_buff);
 int aoenv_set_buff(AoEnv* env, const double* h_buff);

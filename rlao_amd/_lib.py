@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("AOENV_LIB") or os.path.join(_HERE, "csrc", "libaoenv.
 
 ABI_VERSION = 7
 F32, F64 = 0, 1
-WFS_SH, WFS_PYRAMID = 0, 1
+WFS_SH, WFS_PYRAMID, WFS_SH_GEOMETRIC = 0, 1, 2
 
 # enum AoConst
 (C_PUPIL, C_AB, C_INNER_IDX, C_OUTER_IDX, C_LAYER_WEIGHT, C_DM_GX, C_DM_GY, C_DM_MODES, C_ACT_IDX, C_WFS_AMP,
@@ -150,6 +150,7 @@ EXPORTS = {
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "aoenv_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aoenv_upload_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "aoenv_get_phase_no_pupil": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "aoenv_set_wind_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_get_clock_env": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_set_clock_env": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -169,7 +170,7 @@ EXPORTS = {
 
 
 _LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
-                  "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds")
+                  "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds", "aoenv_get_phase_no_pupil")
 
 
 class AoEnvError(RuntimeError):

@@ -63,6 +63,8 @@ class AOParams:
     psfCentering: bool = True            # Pyramid default used by OOPAOEnv.set_params (the call does not pass it)
     postProcessing: str = "slopesMaps_incidence_flux"
     threshold_cog: float = 0.01          # OOPAO/ShackHartmann.py:42
+    is_geometric: bool = False           # Shack-Hartmann: gradient slopes instead of spots (OOPAO/ShackHartmann.py:382-394, 676-695;
+                                         # param['is_geometric'], OOPAO/calibration/initialization_AO_SHWFS.py:114-127)
     nModes: int = 50                     # Zernike modes kept from the M2C (MAIN/OOPAOEnv/OOPAOEnv.py:260)
     nMeasurements: int = 6               # MAIN/OOPAOEnv/OOPAOEnv.py:285
     fov: float = 0.0

@@ -274,7 +274,9 @@ KArgs<T> make_phase_kargs(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int R,
                           double atm_wavelength, double src_wavelength);
 template <typename T>
 int launch_phase(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int n_env, int R, int n_act, int n_valid_act,
-                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st);
+                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st, T* phase_np = nullptr);
+// (phase_np [E][R*R]: a geometric shard's unmasked phase, written beside pb.phase by every phase kernel; null = no such store.  It is
+//  a kernel argument of its own, not a member of PhaseBuffers: the argument block of the fused step kernel stays what it was)
 
 template <typename T>
 struct ShConst {
@@ -333,6 +335,14 @@ template <typename T>
 int launch_sh_tail(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, const T* fac_m,
                    const T* fac_m2c_t, int n_modes, const FinishArgs<T>& fa, int n_env, int R, int n_subap, int n_valid,
                    int max_group, hipStream_t st);
+// geometric Shack-Hartmann (sh_geometric.hpp, sh_geometric_kernels.hip): the stand-alone sensor and the fused tail (-1: no LDS fit)
+template <typename T>
+int launch_sh_geometric(const T* phase_np, const uint8_t* pupil, const short* slot_of, double units, T* signal, int n_env, int R,
+                        int n_subap, int n_valid, hipStream_t st);
+template <typename T>
+int launch_geo_tail(const T* phase_np, const uint8_t* pupil, const short* slot_of, double units, T* signal, const T* fac_m,
+                    const T* fac_m2c_t, int n_modes, const FinishArgs<T>& fa, int n_env, int R, int n_subap, int n_valid,
+                    hipStream_t st);
 // WFS camera model (detector.hpp)
 struct DetectorCfg {           // by value into kernels
     int active;                // 0: ideal detector (identity)

@@ -18,6 +18,7 @@
 #include "modal.hpp"
 #include "policy.hpp"
 #include "sh_device.hpp"
+#include "sh_geometric.hpp"
 #include "science.hpp"
 #include "star_env.hpp"
 #include "wavefront.hpp"
@@ -213,6 +214,8 @@ struct AoEnv {
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
+    void* phase_np = nullptr;               // [E][R*R] geometric shards only: the unmasked phase the slopes are differentiated from
+    bool geometric() const { return c.wfs_type == AOENV_WFS_SH_GEOMETRIC; }
     void* scal = nullptr;                   // [E][4]
     double* part = nullptr;                 // [E][tiles][4] telemetry partial sums of the phase kernel
     int n_tiles = 0;
@@ -745,8 +748,10 @@ int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int sto
     PhaseBuffers<T> pb;
     fill_phase_args<T>(env, pa, pb, update_atm, store_atm, store_phase);
     AO_PROF(env, PHASE, st);
+    // (a geometric shard: every phase path it can take writes the unmasked phase too -- launch_phase hands the target to whichever
+    //  kernel it selects, there is none without the store)
     return launch_phase<T>(pa, pb, env->E, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength,
-                           env->use_mfma, env->force_path, st);
+                           env->use_mfma, env->force_path, st, env->as<T>(env->phase_np));
 }
 
 // the WFS camera on the frame in HBM (detector.hpp); every measurement is a new frame of the noise streams
@@ -776,6 +781,11 @@ int run_spots_and_camera(AoEnv* env, const ShConst<T>& sc, hipStream_t st) {
 
 template <typename T>
 int run_wfs(AoEnv* env, hipStream_t st) {
+    if (env->geometric()) {                                        // no spots, no camera: the frame stays zero, no noise frame is counted
+        AO_PROF(env, SH_CENTROID, st);
+        return launch_sh_geometric<T>(env->as<T>(env->phase_np), env->pupil, env->slot_of, env->units, env->as<T>(env->signal), env->E,
+                                      env->R, env->nSub, env->nVal, st);
+    }
     if (env->c.wfs_type == AOENV_WFS_PYRAMID) {
         if (!env->have[AOENV_C_PYR_MASK] || (env->c.pyr_n_theta > 1 && !env->have[AOENV_C_PYR_TT]))
             return fail("pyramid mask / modulation table has not been uploaded");
@@ -1345,7 +1355,27 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
     // one workgroup per env re-reads the factors from L2: wins while launch latency dominates (measured: 19.5 us vs
     // 32.5 us at 256 envs, 96 us vs 75 us at 2048), the batched MFMA GEMM path takes over for large shards
     const bool fused = env->c.wfs_type == AOENV_WFS_SH && env->use_fused_tail && env->n_modes > 0 && env->E <= 1024;
-    if (fused) {
+    if (env->geometric()) {                                        // two launches: the phase above, slopes + tail here
+        int rc = -1;
+        // (the fit is decided before the profile scope opens: a step that takes the separate kernels counts nothing under sh_tail)
+        if (env->use_fused_tail && env->n_modes > 0 && env->E <= 1024 &&
+            geo_tail_band(env->R, env->nSub, env->nVal, env->nAct, env->n_modes, sizeof(T)) > 0) {
+            FinishArgs<T> fa = finish_args<T>(env, static_cast<const T*>(d_action), static_cast<T*>(d_obs),
+                                              static_cast<T*>(d_reward), static_cast<T*>(d_strehl), i, 1, gain, 1);
+            AO_PROF(env, SH_TAIL, st);
+            rc = launch_geo_tail<T>(env->as<T>(env->phase_np), env->pupil, env->slot_of, env->units, env->as<T>(env->signal),
+                                    env->as<T>(env->fac_m), env->as<T>(env->fac_m2c_t), env->n_modes, fa, env->E, env->R, env->nSub,
+                                    env->nVal, st);
+        }
+        if (rc > 0) return rc;
+        if (rc == 0) {
+            AO_TRY(refresh_dense_dm<T>(env, st));
+        } else {                                                   // no fused tail, or it does not fit in LDS: the separate kernels
+            AO_TRY(run_wfs<T>(env, st));
+            AO_TRY(run_recon<T>(env, static_cast<const T*>(d_action), static_cast<T*>(d_obs), static_cast<T*>(d_reward),
+                                static_cast<T*>(d_strehl), i, 1, gain, st));
+        }
+    } else if (fused) {
         const ShConst<T> sc = sh_const<T>(env);
         AO_TRY(run_spots_and_camera<T>(env, sc, st));
         FinishArgs<T> fa = finish_args<T>(env, static_cast<const T*>(d_action), static_cast<T*>(d_obs),
@@ -1571,7 +1601,9 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
                 return fail("layer_res_l[%d] = %d < R + 4", l, cfg->layer_res_l[l]);
     }
     if (cfg->n_signal != 2 * cfg->n_valid_subap) return fail("n_signal != 2 n_valid_subap");
-    if (cfg->wfs_type != AOENV_WFS_SH && cfg->wfs_type != AOENV_WFS_PYRAMID) return fail("unknown wfs_type %d", cfg->wfs_type);
+    if (cfg->wfs_type != AOENV_WFS_SH && cfg->wfs_type != AOENV_WFS_PYRAMID && cfg->wfs_type != AOENV_WFS_SH_GEOMETRIC)
+        return fail("unknown wfs_type %d", cfg->wfs_type);
+    if (cfg->wfs_type == AOENV_WFS_SH_GEOMETRIC && cfg->cam_res < 1) return fail("geometric sensor: cam_res must be >= 1 (the frame is defined, and zero)");
     if (cfg->wfs_type == AOENV_WFS_PYRAMID) {
         if (cfg->pyr_n_res < cfg->resolution || cfg->pyr_n_res % 2 || cfg->cam_res < 1 || cfg->pyr_n_res % cfg->cam_res)
             return fail("pyramid: nRes %d must be even, >= R and a multiple of the camera size %d", cfg->pyr_n_res, cfg->cam_res);
@@ -1651,6 +1683,7 @@ int aoenv_create(const AoCfg* cfg, int device, AoEnv** out) {
     A_(&e->coefs_seen, E * e->A * z);                              // zero until a disturbed step writes it
     A_(&e->dm_prev, E * e->A * z);                                 // self.dm_prev = self.dm.coefs.copy() = 0 (OOPAOEnv.py:313-314)
     A_(&e->phase, E * R2 * z);
+    if (cfg->wfs_type == AOENV_WFS_SH_GEOMETRIC) A_(&e->phase_np, E * R2 * z);
     A_(&e->scal, E * 4 * z);
     e->n_tiles = phase_tiles(e->R, e->nAct, e->esz);
     A_((void**)&e->part, E * (size_t)e->n_tiles * 4 * sizeof(double));
@@ -1816,6 +1849,7 @@ int aoenv_upload(AoEnv* env, int kind, const void* h, size_t bytes) {
             const int32_t* ix = static_cast<const int32_t*>(h);
             for (int i = 0; i < env->nVal; ++i)
                 if (ix[i] < 0 || ix[i] >= env->nSub * env->nSub) return fail("lenslet index %d out of range", ix[i]);
+            if (env->geometric() && env->nVal > 32767) return fail("geometric sensor: %d valid lenslets, at most 32767", env->nVal);
             AO_HIP(hipMemcpy(env->subap_idx, h, (size_t)env->nVal * 4, hipMemcpyHostToDevice));
             std::vector<uint8_t> v2((size_t)env->nSub * env->nSub, 0);
             for (int i = 0; i < env->nVal; ++i) v2[ix[i]] = 1;
@@ -2095,7 +2129,7 @@ int aoenv_get_r0_env(AoEnv* env, double* h_r0) {
 static int require_step_constants(AoEnv* env, bool atmosphere) {
     static const int base[] = {AOENV_C_PUPIL, AOENV_C_ACT_IDX, AOENV_C_WFS_AMP, AOENV_C_SH_SUBAP_IDX};
     for (int k : base)
-        if (!env->have[k]) return fail("constant table %d has not been uploaded", k);
+        if (!env->have[k] && !(k == AOENV_C_WFS_AMP && env->geometric())) return fail("constant table %d has not been uploaded", k);
     if (env->c.dm_separable ? !(env->have[AOENV_C_DM_GX] && env->have[AOENV_C_DM_GY]) : !env->have[AOENV_C_DM_MODES])
         return fail("DM influence functions have not been uploaded");
     if (atmosphere && env->L > 0) {
@@ -2708,6 +2742,7 @@ int aoenv_set_flux_env(AoEnv* env, const double* h_scale, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     AoEnv::StarDev& s = env->star;
     if (!h_scale) return clear_star_row(s.amp_mem, s.amp, st);
+    if (env->geometric()) return fail("aoenv_set_flux_env: a geometric sensor has neither photons nor a threshold");
     char msg[96];
     if (star_flux_check(h_scale, env->E, msg, sizeof msg)) return fail("aoenv_set_flux_env: %s", msg);
     const auto fill = [](const double* h, int n, auto* out) { star_amp_factors(h, n, out); };
@@ -2727,6 +2762,7 @@ int aoenv_set_threshold_env(AoEnv* env, const double* h_thr, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     AoEnv::StarDev& s = env->star;
     if (!h_thr) return clear_star_row(s.thr_mem, s.thr, st);
+    if (env->geometric()) return fail("aoenv_set_threshold_env: a geometric sensor has neither photons nor a threshold");
     if (const char* why = star_threshold_refusal(env->c.wfs_type == AOENV_WFS_PYRAMID, env->c.max_group)) return fail("aoenv_set_threshold_env: %s", why);
     char msg[96];
     if (star_threshold_check(h_thr, env->E, msg, sizeof msg)) return fail("aoenv_set_threshold_env: %s", msg);
@@ -3534,6 +3570,7 @@ int aoenv_set_detector(AoEnv* env, const AoDetector* cfg, void* stream) {
         if (!d.photon_noise && d.bits == 0 && d.qe == 1.f && d.dark_e == 0.f && d.fwc == 0.f && d.gain == 1.f && d.readout_noise == 0.f)
             d.active = 0;
     }
+    if (env->geometric()) return 0;                                // checked and accepted, no effect: no frame, no noise, no frame counted
     if (env->det.active)                                           // no stale noise outside the valid lenslets (the new camera may not write there)
         AO_HIP(hipMemsetAsync(env->frame, 0, (size_t)env->E * env->c.cam_res * env->c.cam_res * env->esz, st));
     if (!cfg) {                                                    // ideal detector: the stream position and its seed are kept
@@ -3625,6 +3662,17 @@ int aoenv_download(AoEnv* env, int which, void* h_dst, size_t bytes, void* strea
         AO_HIP(hipStreamSynchronize(st));
     }
     AO_HIP(hipMemcpy(h_dst, b.ptr, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int aoenv_get_phase_no_pupil(AoEnv* env, void* h_dst, size_t bytes, void* stream) {
+    AO_CHECK_ENV(env);
+    if (!h_dst) return fail("aoenv_get_phase_no_pupil: null destination");
+    if (!env->phase_np) return fail("aoenv_get_phase_no_pupil: the unmasked phase is kept by geometric shards only (AOENV_WFS_SH_GEOMETRIC)");
+    const size_t want = (size_t)env->E * env->R * env->R * env->esz;
+    if (bytes != want) return fail("aoenv_get_phase_no_pupil: got %zu bytes, expected %zu", bytes, want);
+    AO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    AO_HIP(hipMemcpy(h_dst, env->phase_np, bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -25,8 +25,11 @@ namespace ao {
 
 constexpr int kTY = 16, kTXmax = 128;
 
-template <typename T>
-__global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
+// NP (every phase kernel): the shard's sensor is geometric and `np` [E][R*R] receives the UNMASKED phase (atm + dm) src_scale of
+// every pixel -- the add and the multiply of residual_pixel, so inside the pupil it is AOENV_B_PHASE bit for bit.  NP = false
+// instantiations never look at `np`: a diffractive shard runs the code it ran before.
+template <typename T, bool NP>
+__global__ void __launch_bounds__(256) k_phase(const KArgs<T> a, T* __restrict__ np) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int R = a.R, nA = a.n_act, TX = a.tx;
     const int MW = TX + 4;                                   // row stride of the staged layer tile (TX + 3 used)
@@ -153,6 +156,9 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
                 }
                 const T phi = residual_pixel(atm, dm, a.pb.pupil[q] != 0, a.src_scale, sums);
                 if (a.pa.store_phase) a.pb.phase[pix0 + q] = phi;
+                if constexpr (NP) {
+                    if (a.pa.store_phase) np[pix0 + q] = (atm + dm) * a.src_scale;
+                }
             }
         }
     }
@@ -173,7 +179,8 @@ __global__ void __launch_bounds__(256) k_phase(const KArgs<T> a) {
 // Per MFMA (1024 MACs) a lane reads one s1 and one Gx^T value from LDS -- 32x less LDS traffic than the
 // per-pixel dot products of the generic kernel, which were the bottleneck there.
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
+template <bool NP>
+__global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a, float* __restrict__ np) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int R = a.R, nA = a.n_act;
     constexpr int TX = kTXmax, MW = TX + 4;
@@ -323,6 +330,9 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
                 }
                 const float phi = residual_pixel(atm, dmv[r], pup[tt][r], a.src_scale, sums);
                 if (a.pa.store_phase) a.pb.phase[pix0 + q] = phi;
+                if constexpr (NP) {
+                    if (a.pa.store_phase) np[pix0 + q] = (atm + dmv[r]) * a.src_scale;
+                }
             }
         }
     }
@@ -346,8 +356,8 @@ __global__ void __launch_bounds__(256) k_phase_mfma(const KArgs<float> a) {
 // in flight together, instead of a 19 x 132 tile per 128-column chunk: one memory latency and one pair of barriers per workgroup
 // instead of four (ELT size: a wave lived 43 us, 56 % of it waiting).
 // NQ: 16-byte loads per lane of a DM operand (Gy C rows, gx columns): ga_stride / 4 rounded up to even, <= 8 (n_act <= 128)
-template <bool BAND, int NQ>
-__global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
+template <bool BAND, int NQ, bool NP>
+__global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a, float* __restrict__ np) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int R = a.R, nA = a.n_act;
     constexpr int TX = kTXmax, MW = TX + 4;
@@ -512,6 +522,14 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
             residual_pixel4(a.pa.update_atm, sup[tt], dmv, pup[tt], a.atm_scale, a.src_scale, atm, phi, sums);
             if (a.pa.update_atm && a.pa.store_atm) *reinterpret_cast<f32x4*>(a.pb.opd_atm + pix0 + q) = atm;
             if (a.pa.store_phase) *reinterpret_cast<f32x4*>(a.pb.phase + pix0 + q) = phi;
+            if constexpr (NP) {
+                if (a.pa.store_phase) {
+                    f32x4 u;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) u[r] = (atm[r] + dmv[r]) * a.src_scale;
+                    *reinterpret_cast<f32x4*>(np + pix0 + q) = u;
+                }
+            }
         }
     }
     }
@@ -527,16 +545,23 @@ __global__ void __launch_bounds__(256, 4) k_phase_mfma4(const KArgs<float> a) {
 }
 
 template <typename T>
-int launch_phase_mfma(const KArgs<T>&, int, int, hipStream_t) { return -1; }
+int launch_phase_mfma(const KArgs<T>&, int, int, T*, hipStream_t) { return -1; }
+template <bool BAND, bool NP>
+static void (*phase_mfma4_kernel(int nq))(const KArgs<float>, float*) {
+    if (nq <= 2) return k_phase_mfma4<BAND, 2, NP>;
+    if (nq <= 4) return k_phase_mfma4<BAND, 4, NP>;
+    if (nq <= 6) return k_phase_mfma4<BAND, 6, NP>;
+    return k_phase_mfma4<BAND, 8, NP>;
+}
 template <>
-int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, int force_path, hipStream_t st) {
+int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, int force_path, float* np, hipStream_t st) {
     const int nA = a.n_act, nAp = (nA + 3) & ~3, TX = kTXmax, MW = TX + 4;
     const size_t lds = sizeof(float) * ((a.pb.s1a ? 0 : (size_t)nA * nA + (size_t)kTY * (nAp + 1)) + (size_t)(kTY + 3) * MW);
     if (a.pb.gxa == nullptr || nA > 128) return -1;
     if (lds > 160 * 1024) return -1;
     if (lds > 64 * 1024)
-        AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_phase_mfma), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
+        AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(np ? k_phase_mfma<true> : k_phase_mfma<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid(cdiv(a.R, TX), cdiv(a.R, kTY), n_env);
     if (a.R % 4 == 0 && !(force_path & AOENV_PATH_PHASE_DWORD)) {
         // one layer: its tile of the whole 16-row band in LDS (19 x (R + 4) floats) instead of one 19 x 132 tile per chunk
@@ -544,16 +569,16 @@ int launch_phase_mfma<float>(const KArgs<float>& a, int n_env, int force_path, h
         const bool band = a.pa.n_layer == 1 && a.pa.update_atm && lds_band <= 160 * 1024 && !(force_path & AOENV_PATH_GENERIC);
         const size_t l4 = band ? lds_band : lds;
         const int nq = a.pb.ga_stride / 4;
-        void (*kern)(const KArgs<float>);
-        if (nq <= 2) kern = band ? k_phase_mfma4<true, 2> : k_phase_mfma4<false, 2>;
-        else if (nq <= 4) kern = band ? k_phase_mfma4<true, 4> : k_phase_mfma4<false, 4>;
-        else if (nq <= 6) kern = band ? k_phase_mfma4<true, 6> : k_phase_mfma4<false, 6>;
-        else kern = band ? k_phase_mfma4<true, 8> : k_phase_mfma4<false, 8>;
+        void (*kern)(const KArgs<float>, float*);
+        if (np) kern = band ? phase_mfma4_kernel<true, true>(nq) : phase_mfma4_kernel<false, true>(nq);
+        else kern = band ? phase_mfma4_kernel<true, false>(nq) : phase_mfma4_kernel<false, false>(nq);
         if (l4 > 64 * 1024)
             AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4));
-        hipLaunchKernelGGL(kern, dim3(1, grid.y, grid.z), dim3(256), l4, st, a);      // one workgroup per 16-row band
+        hipLaunchKernelGGL(kern, dim3(1, grid.y, grid.z), dim3(256), l4, st, a, np);  // one workgroup per 16-row band
+    } else if (np) {
+        hipLaunchKernelGGL(k_phase_mfma<true>, grid, dim3(256), lds, st, a, np);
     } else {
-        hipLaunchKernelGGL(k_phase_mfma, grid, dim3(256), lds, st, a);
+        hipLaunchKernelGGL(k_phase_mfma<false>, grid, dim3(256), lds, st, a, np);
     }
     AO_HIP(hipGetLastError());
     return 0;
@@ -692,31 +717,31 @@ template KArgs<double> make_phase_kargs<double>(const PhaseArgs&, const PhaseBuf
 
 template <typename T>
 int launch_phase(const PhaseArgs& pa, const PhaseBuffers<T>& pb, int n_env, int R, int n_act, int n_valid_act,
-                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st) {
+                 double atm_wavelength, double src_wavelength, bool use_mfma, int force_path, hipStream_t st, T* phase_np) {
     KArgs<T> a = make_phase_kargs<T>(pa, pb, R, n_act, n_valid_act, atm_wavelength, src_wavelength);
     if (use_mfma && sizeof(T) == 4 && pb.dm_opd == nullptr) {
         // the MFMA kernel tiles with TX = 128 whatever R is (phase_tiles() is the same count for R <= 128 and
         // for R a multiple of 128; otherwise fall through to the generic kernel)
         if (cdiv(R, kTXmax) == cdiv(R, a.tx)) {
-            const int rc = launch_phase_mfma<T>(a, n_env, force_path, st);
+            const int rc = launch_phase_mfma<T>(a, n_env, force_path, phase_np, st);
             if (rc >= 0) return rc;
         }
     }
     const int TX = a.tx;
     const size_t lds = phase_lds_bytes(n_act, TX, sizeof(T));
     if (lds > 160 * 1024) return fail("phase kernel: %d actuators across need %zu B of LDS", n_act, lds);
+    void (*kern)(const KArgs<T>, T*) = phase_np ? k_phase<T, true> : k_phase<T, false>;
     if (lds > 64 * 1024)
-        AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_phase<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
+        AO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid(cdiv(R, TX), cdiv(R, kTY), n_env);
-    hipLaunchKernelGGL(k_phase<T>, grid, dim3(64, 4), lds, st, a);
+    hipLaunchKernelGGL(kern, grid, dim3(64, 4), lds, st, a, phase_np);
     AO_HIP(hipGetLastError());
     return 0;
 }
 
 template int launch_phase<float>(const PhaseArgs&, const PhaseBuffers<float>&, int, int, int, int, double, double, bool, int,
-                                 hipStream_t);
+                                 hipStream_t, float*);
 template int launch_phase<double>(const PhaseArgs&, const PhaseBuffers<double>&, int, int, int, int, double, double, bool,
-                                  int, hipStream_t);
+                                  int, hipStream_t, double*);
 
 }  // namespace ao

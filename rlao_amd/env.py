@@ -528,6 +528,12 @@ class Shard:
         L.call(self, "aoenv_download", which, out, out.nbytes, stream)
         return out
 
+    def phase_no_pupil(self, shape, stream=0) -> np.ndarray:
+        """aoenv_get_phase_no_pupil: the unmasked phase of a geometric shard (refused on any other)."""
+        out = np.empty(shape, dtype=self.np_dtype)
+        L.call(self, "aoenv_get_phase_no_pupil", out, out.nbytes, stream)
+        return out
+
     def upload_state(self, which: int, arr, stream=0, dtype=None):
         a = np.ascontiguousarray(arr, dtype=self.np_dtype if dtype is None else dtype)
         L.call(self, "aoenv_upload_state", which, a, a.nbytes, stream)
@@ -921,6 +927,17 @@ class _WfsProxy:
         return self._e.nSignal
 
     @property
+    def is_geometric(self):
+        """True on an env built with ``set_params(..., is_geometric=True)`` (OOPAO/ShackHartmann.py:44).  Read-only: slope units,
+        interaction matrix and reconstructor are all calibrated in the mode."""
+        return self._e.is_geometric
+
+    @is_geometric.setter
+    def is_geometric(self, value):
+        raise AttributeError("wfs.is_geometric cannot be assigned: the slope units, the interaction matrix and the reconstructor "
+                             "depend on it -- build the env with set_params(..., is_geometric=...)")
+
+    @property
     def signal(self):
         return self._e._fetch(L.B_SIGNAL, (self._e.nSignal,))
 
@@ -1050,6 +1067,7 @@ class BatchedAOEnv:
         self.action_buffer = []
         self.atm = self.dm = self.tel = self.wfs = None
         self._shard = None
+        self.is_geometric = False                                  # set_params(..., is_geometric=True): the gradient Shack-Hartmann
         self._done = None
         self._wind_env = None                                      # (speed, direction) [n_envs, nLayer] once per-env winds are set
         self._per_env_clock = False
@@ -1119,6 +1137,11 @@ class BatchedAOEnv:
         sees ideal spot intensities, as in the reference: the WFS constructor measures its reference slopes before the camera is
         configured, and the interaction-matrix pokes go through the Shack-Hartmann's multi-wave-front branch, which computes the
         centroids from the intensities without passing them through the detector (OOPAO/ShackHartmann.py:605-672).
+        ``is_geometric=True`` (a keyword, or the parameter-file key of that name; Shack-Hartmann only): the geometric sensor of
+        ``ShackHartmann(..., is_geometric=True)`` (OOPAO/ShackHartmann.py:382-394, 676-695) -- the signal is the pupil-masked gradient
+        of the unmasked phase summed per lenslet, over ``slopes_units``: no spots, no camera, no threshold, no reference slopes, no
+        noise.  Units, interaction matrix and reconstructor are calibrated in that mode; the camera flavours are accepted and change
+        nothing (``wfs.cam.frame`` is zeros); ``fused_step`` is False (a step is the phase kernel and one launch for the rest).
         ``atm_AB``: the ring operators handed over instead of recomputed -- one pair (A, B) when the layers share a grid, a list
         with one pair per layer when they have grids of their own (``_atmosphere_tables``); a wrong form or shape is refused
         before anything of the env is touched."""
@@ -1133,6 +1156,9 @@ class BatchedAOEnv:
             self.wfs_type = "pyr"
         else:
             raise ValueError(f"unknown wfs_type {wfs_type!r}")
+        if p.is_geometric and self.wfs_type != "sh":
+            raise ValueError("is_geometric is a mode of the Shack-Hartmann: there is no geometric Pyramid")
+        self.is_geometric = bool(p.is_geometric)
         torch = _torch()
         self.gainCL = gainCL
         self.param = p
@@ -1192,7 +1218,7 @@ class BatchedAOEnv:
         sh.upload_ring_tables(at)
         sh.upload(L.C_LAYER_WEIGHT, at.weights)
         sh.upload(L.C_SH_REF, ref)
-        sh.upload(L.C_WFS_UNITS, np.array([units]))
+        sh.upload(L.C_WFS_UNITS, self._units_table(units))
         sh.upload(L.C_RECON, self.reconstructor)
         sh.upload(L.C_RECON_FACTORS, np.concatenate([self.modal_CM.reshape(-1), self.M2C_CL.reshape(-1)]))
         self.set_noise_filter(np.linalg.pinv(self.M2C_CL), self.M2C_CL)      # the factors of self.F (OOPAOEnv.py:383)
@@ -1226,7 +1252,7 @@ class BatchedAOEnv:
                    atm_wavelength=calib.ATM_WAVELENGTH, src_wavelength=self.src_wavelength, leak=p.leak,
                    threshold_cog=p.threshold_cog)
         if self.wfs_type == "sh":
-            cfg.update(wfs_type=L.WFS_SH)
+            cfg.update(wfs_type=L.WFS_SH_GEOMETRIC if self.is_geometric else L.WFS_SH)
         else:
             pt = self._pyr_tables
             cfg.update(wfs_type=L.WFS_PYRAMID, pyr_n_res=pt.nRes, pyr_n_theta=self._wfs_n_theta,
@@ -1286,12 +1312,30 @@ class BatchedAOEnv:
             cal.close()
         return ref, 1.0
 
+    def _units_table(self, units):
+        """AOENV_C_WFS_UNITS as the library takes it: the geometric sensor's gradient is per metre and the library has no diameter,
+        so the host folds the pixel size into the divisor (include/aoenv.h).  ``slopes_units`` itself stays the reference's value."""
+        return np.array([units * self.param.diameter / self.R if self.is_geometric else units], dtype=np.float64)
+
     def _calibrate_wfs(self):
         """initialize_wfs (OOPAO/ShackHartmann.py:254-312): reference centroids from a flat wave-front,
-        slope units from a five-point tip ramp, measured by the HIP kernels in float64."""
+        slope units from a five-point tip ramp, measured by the HIP kernels in float64.  Geometric mode: the same ramp, handed over
+        unmasked (``OPD_no_pupil = Tip (i - 2) amp``, :296-297: ``set_atm_opd`` takes exactly that buffer), fitted with units 1;
+        no reference is measured or subtracted (:676-695), ``reference_centroids`` is zeros."""
         R, nv = self.R, self._sh_tables.nValid
         self.nSignal = 2 * nv
         cal = self._make_shard(5, "f64", n_layer=0, max_group=1)
+        if self.is_geometric:
+            try:
+                cal.upload(L.C_WFS_UNITS, self._units_table(1.0))
+                amp = 10e-9
+                cal.set_atm_opd(np.stack([calib.tip_ramp(R) * (i - 2) * amp for i in range(5)]).reshape(5, R * R))
+                cal.measure()
+                sig = cal.download(L.B_SIGNAL, (5, 2 * nv))
+                fit = np.polyfit(np.linspace(-2, 2, 5) * amp, sig[:, :nv].mean(axis=1), deg=1)
+                return np.zeros(2 * nv), float(np.abs(fit[0]) * (self.src_wavelength / 2 / np.pi))
+            finally:
+                cal.close()
         try:
             cal.upload(L.C_SH_REF, np.zeros(2 * nv))
             cal.upload(L.C_WFS_UNITS, np.array([1.0]))
@@ -1332,7 +1376,7 @@ class BatchedAOEnv:
             cal = self._make_shard(n, "f64", n_layer=0, max_group=n_meas)
             try:
                 cal.upload(L.C_SH_REF, ref)
-                cal.upload(L.C_WFS_UNITS, np.array([units]))
+                cal.upload(L.C_WFS_UNITS, self._units_table(units))
                 coefs = np.zeros((n, A_))
                 coefs[np.arange(n), a0 + np.arange(n)] = stroke
                 cal.set_coefs(coefs)
@@ -1349,6 +1393,12 @@ class BatchedAOEnv:
     def _fetch(self, which, shape):
         out = self._shard.download(which, (self.n_envs,) + tuple(shape), self._stream())
         return out[0] if self.n_envs == 1 else out
+
+    @property
+    def phase_no_pupil(self):
+        """``src.phase_no_pupil`` of every env, ``[n_envs, R, R]`` rad at the guide star's wavelength: what the geometric sensor
+        differentiates.  Geometric envs only (the library keeps the buffer for them alone and refuses otherwise)."""
+        return self._shard.phase_no_pupil((self.n_envs, self.R, self.R), self._stream())
 
     def _push_detector(self):
         """wfs.cam.* -> aoenv_set_detector (OOPAO/Detector.py:232-301).  ``detector_seed`` keys the noise streams."""
