@@ -723,6 +723,31 @@ int aoenv_science_residual(AoEnv* env, void* d_phase_sci, void* d_opd_atm_sci, v
  * front of the window's); aoenv_compute_psf keeps the guide star's direction. */
 int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int n_slots);
 
+/* Replaces: a guide star off axis, `ngs.coordinates = [zenith arcsec, azimuth deg]` with `atm * ngs` and then `tel * dm * wfs`
+ * (OOPAO/Atmosphere.py:313-334, 439-450): per env, the SENSOR's line of sight through the layers.  The model, the host plan and the
+ * refusals are the science direction's (rlao_amd/csrc/offaxis.hpp): [n_env] arrays, the footprints copied before the call returns,
+ * the stream waited for once; both arrays NULL forget the direction.  Refused, with nothing changed: no field set, a shard without
+ * layers, one array NULL, a zenith that is negative, not finite or above fov / 2, an azimuth that is not finite, a footprint whose
+ * taps would leave the layer's screen.  aoenv_set_field is refused while a guide direction is set.
+ * While a direction is set, wherever the library derives the atmosphere from the screens -- aoenv_step, aoenv_measure,
+ * aoenv_atm_update, aoenv_reset_soft, aoenv_run_integrator, both rollouts, the modal calls, aoenv_download(AOENV_B_OPD_ATM),
+ * aoenv_project_wavefront(AOENV_WF_ATMOSPHERE), aoenv_get_phase_no_pupil, aoenv_science_residual -- one launch (a workgroup per
+ * 16 x 64 pixel tile and env, no sums, no atomics) writes OPD_no_pupil toward every env's guide star into AOENV_B_OPD_ATM, and the
+ * phase kernel takes it from there, as it takes a user-defined OPD.  Everything behind it -- the mirror of any kind, the delay, a
+ * disturbance, the sensor of any kind, the camera, reward, Strehl and telemetry -- follows without a change.  A user-defined OPD
+ * (aoenv_set_atm_opd) still wins until the atmosphere advances.  An env has the same bits in any shard and at any place in it; at
+ * zenith 0 every output is bit for bit that of the batched kernels without a direction.
+ * The shard leaves the fused step kernel while a direction is set (aoenv_fused_step_active reports 0; the batched kernels run, as
+ * for a rotated mirror) and returns to it, bit-identical to an untouched shard, when the direction is forgotten.
+ * The science arm differences against the OPD the sensor saw: phase_sci = AOENV_B_PHASE + (OPD_no_pupil_sci - AOENV_B_OPD_ATM) 2 pi /
+ * lambda_src.  So with no science direction the science camera keeps looking at the guide star, wherever it is; with a science
+ * direction of zenith 0 it looks along the axis while the sensor looks off it (classical anisoplanatism); with both directions
+ * equal OPD_no_pupil_sci and phase_sci are bit for bit AOENV_B_OPD_ATM and AOENV_B_PHASE.
+ * Configuration: in no checkpoint buffer, untouched by aoenv_reset_envs and aoenv_new_screens*.  No buffer id, no profiled kernel
+ * and no ABI version go with it. */
+int aoenv_set_guide_direction(AoEnv* env, const double* h_zenith_arcsec, const double* h_azimuth_deg, void* stream);
+int aoenv_get_guide_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azimuth_deg);
+
 /* Replaces: the WFS camera settings wfs.cam.{photonNoise, readoutNoise, QE, darkCurrent, integrationTime, FWC, bits, gain,
  * sensor} (OOPAO/Detector.py:19-60; Papyrus: photonNoise = True, MAIN/OOPAOEnv/OOPAOEnv.py:379; Razor:
  * OOPAOEnvRazor.py:243-250, 333).  The frame of every measurement then goes through integrate() + readout()

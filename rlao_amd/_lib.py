@@ -145,6 +145,8 @@ EXPORTS = {
     "aoenv_get_science_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_science_residual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_science_direction_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "aoenv_set_guide_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_get_guide_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -170,7 +172,8 @@ EXPORTS = {
 
 
 _LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
-                  "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds", "aoenv_get_phase_no_pupil")
+                  "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds", "aoenv_get_phase_no_pupil",
+                  "aoenv_set_guide_direction", "aoenv_get_guide_direction")
 
 
 class AoEnvError(RuntimeError):

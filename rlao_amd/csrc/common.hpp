@@ -541,6 +541,19 @@ struct OaArgs {
 template <typename T>
 int launch_science_residual(const OaArgs<T>& a, hipStream_t st);
 
+// the unmasked atmosphere OPD toward every env's guide star (offaxis_kernels.hip, k_guide_opd): one launch, a workgroup per (row
+// tile, column tile, env), no sums.  `pa` as for launch_science_residual
+template <typename T>
+struct GuideArgs {
+    PhaseArgs pa;
+    const OaShift* dir;    // [n_layer][E] the footprints toward the guide star
+    T* opd_atm;            // [E][R*R] m
+    int R;
+    T atm_scale;
+};
+template <typename T>
+int launch_guide_opd(const GuideArgs<T>& a, hipStream_t st);
+
 template <typename T>
 int launch_convert_from_f64(const double* src, T* dst, size_t n, hipStream_t st);
 

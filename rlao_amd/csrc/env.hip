@@ -211,6 +211,14 @@ struct AoEnv {
         // stepped frame i needs the step's phase and on-axis atmosphere OPD in HBM
         bool reads_step(bool accumulates) const { return rec || (set && accumulates); }
     } oa;
+    // off-axis guide star (aoenv_set_guide_direction, offaxis.hpp): the footprints toward the star of every env, in ONE block of its
+    // own (NULL arrays free it).  While set, run_phase forms the atmosphere OPD toward the star (k_guide_opd) ahead of the phase kernel
+    struct Guide {
+        bool set = false;
+        std::vector<double> zenith, azimuth;   // [E] arcsec, deg
+        Block mem;
+        OaShift* dir = nullptr;             // [L][E]
+    } guide;
     float* dm_rows = nullptr;               // [E][Rpad128][4][ga_stride] Gy C per env (float32; k_dm_rows), the same switch
     void* coefs_img = nullptr;              // [E][nAct^2] command images for the phase kernels of large DMs (A > 1024)
     void* phase = nullptr;
@@ -747,6 +755,16 @@ int run_phase(AoEnv* env, int update_atm, int store_atm, hipStream_t st, int sto
     PhaseArgs pa;
     PhaseBuffers<T> pb;
     fill_phase_args<T>(env, pa, pb, update_atm, store_atm, store_phase);
+    if (env->guide.set && pa.update_atm) {                         // the sensor's line of sight: the OPD toward the guide star, then
+        GuideArgs<T> ga{};                                         // the phase kernel on a given OPD, as after aoenv_set_atm_opd
+        ga.pa = pa;
+        ga.dir = env->guide.dir;
+        ga.opd_atm = pb.opd_atm;
+        ga.R = env->R;
+        ga.atm_scale = make_phase_kargs<T>(pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength).atm_scale;
+        AO_TRY(launch_guide_opd<T>(ga, st));
+        pa.update_atm = 0;
+    }
     AO_PROF(env, PHASE, st);
     // (a geometric shard: every phase path it can take writes the unmasked phase too -- launch_phase hands the target to whichever
     //  kernel it selects, there is none without the store)
@@ -952,7 +970,7 @@ template <typename T>
 bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
-    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && env->n_modes > 0 &&
+    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && !env->guide.set && env->n_modes > 0 &&
            env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
@@ -3056,11 +3074,37 @@ int aoenv_set_field(AoEnv* env, double diameter, double fov_arcsec, const double
     for (int l = 0; l < env->L; ++l)
         if (!(std::isfinite(h_altitude[l]) && h_altitude[l] >= 0)) return fail("aoenv_set_field: altitude %g of layer %d is negative or not finite", h_altitude[l], l);
     if (env->oa.set) return fail("aoenv_set_field: a science direction is set; forget it first (aoenv_set_science_direction with NULL)");
+    if (env->guide.set) return fail("aoenv_set_field: a guide direction is set; forget it first (aoenv_set_guide_direction with NULL)");
     AoEnv::OffAxis& oa = env->oa;
     oa.D = diameter;
     oa.fov = fov_arcsec;
     for (int l = 0; l < env->L; ++l) oa.altitude[l] = h_altitude[l];
     oa.have_field = true;
+    return 0;
+}
+
+// what aoenv_set_science_direction and aoenv_set_guide_direction check, with `who` in every message, and the table [L][E] they upload
+static int oa_plan_direction(const AoEnv* env, const char* who, const double* h_zenith_arcsec, const double* h_azimuth_deg,
+                             std::vector<OaShift>& dir) {
+    const AoEnv::OffAxis& oa = env->oa;
+    if (!h_zenith_arcsec || !h_azimuth_deg) return fail("%s: one of the two arrays is null", who);
+    if (env->L < 1) return fail("%s: the shard has no layers to look through", who);
+    if (!oa.have_field) return fail("%s: the field is not set (aoenv_set_field)", who);
+    const int E = env->E, L = env->L;
+    int N_l[kMaxLayer], we = 0, wl = 0;
+    for (int l = 0; l < L; ++l) N_l[l] = env->layer[l].N;
+    dir.resize((size_t)L * E);
+    switch (oa_make(L, E, env->R, oa.D, oa.fov, oa.altitude, N_l, h_zenith_arcsec, h_azimuth_deg, dir.data(), &we, &wl)) {
+        case kOaOk: break;
+        case kOaNoLayers: return fail("%s: the shard has no layers to look through", who);
+        case kOaNull: return fail("%s: null argument", who);
+        case kOaGeometry: return fail("%s: the field is not valid (aoenv_set_field)", who);
+        case kOaZenith:
+            return fail("%s: zenith %g arcsec of env %d is negative, not finite or above fov / 2 = %g", who, h_zenith_arcsec[we], we, oa.fov / 2);
+        case kOaAzimuth: return fail("%s: azimuth of env %d is not finite", who, we);
+        case kOaPlan:
+            return fail("%s: the footprint of env %d in layer %d (grid %d) would read beyond the layer's screen", who, we, wl, N_l[wl]);
+    }
     return 0;
 }
 
@@ -3080,24 +3124,9 @@ int aoenv_set_science_direction(AoEnv* env, const double* h_zenith_arcsec, const
         oa.set = false;
         return 0;
     }
-    if (!h_zenith_arcsec || !h_azimuth_deg) return fail("aoenv_set_science_direction: one of the two arrays is null");
-    if (env->L < 1) return fail("aoenv_set_science_direction: the shard has no layers to look through");
-    if (!oa.have_field) return fail("aoenv_set_science_direction: the field is not set (aoenv_set_field)");
-    const int E = env->E, L = env->L;
-    int N_l[kMaxLayer], we = 0, wl = 0;
-    for (int l = 0; l < L; ++l) N_l[l] = env->layer[l].N;
-    std::vector<OaShift> dir((size_t)L * E);
-    switch (oa_make(L, E, env->R, oa.D, oa.fov, oa.altitude, N_l, h_zenith_arcsec, h_azimuth_deg, dir.data(), &we, &wl)) {
-        case kOaOk: break;
-        case kOaNoLayers: return fail("aoenv_set_science_direction: the shard has no layers to look through");
-        case kOaNull: return fail("aoenv_set_science_direction: null argument");
-        case kOaGeometry: return fail("aoenv_set_science_direction: the field is not valid (aoenv_set_field)");
-        case kOaZenith:
-            return fail("aoenv_set_science_direction: zenith %g arcsec of env %d is negative, not finite or above fov / 2 = %g", h_zenith_arcsec[we], we, oa.fov / 2);
-        case kOaAzimuth: return fail("aoenv_set_science_direction: azimuth of env %d is not finite", we);
-        case kOaPlan:
-            return fail("aoenv_set_science_direction: the footprint of env %d in layer %d (grid %d) would read beyond the layer's screen", we, wl, N_l[wl]);
-    }
+    const int E = env->E;
+    std::vector<OaShift> dir;
+    AO_TRY(oa_plan_direction(env, "aoenv_set_science_direction", h_zenith_arcsec, h_azimuth_deg, dir));
     const size_t R2 = (size_t)env->R * env->R;
     const std::initializer_list<size_t> parts = {dir.size() * sizeof(OaShift), (size_t)E * R2 * env->esz};
     AO_HIP(hipStreamSynchronize(st));                              // a launch in flight reads the table in place
@@ -3141,6 +3170,39 @@ int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int 
     oa.rec = d_rec;
     oa.i_base = i_base;
     oa.n_slots = n_slots;
+    return 0;
+}
+
+// ---- off-axis guide star (offaxis.hpp, k_guide_opd) ----------------------------------------------------------------------------------
+int aoenv_set_guide_direction(AoEnv* env, const double* h_zenith_arcsec, const double* h_azimuth_deg, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AoEnv::Guide& gd = env->guide;
+    if (!h_zenith_arcsec && !h_azimuth_deg) {                      // forget the direction: the sensor looks along the axis again
+        AO_HIP(hipStreamSynchronize(st));
+        gd = AoEnv::Guide{};
+        return 0;
+    }
+    std::vector<OaShift> dir;
+    AO_TRY(oa_plan_direction(env, "aoenv_set_guide_direction", h_zenith_arcsec, h_azimuth_deg, dir));
+    const std::initializer_list<size_t> parts = {dir.size() * sizeof(OaShift)};
+    AO_HIP(hipStreamSynchronize(st));                              // a launch in flight reads the table in place
+    Block mem;                                                     // (built whole before the direction in use is given up)
+    if (mem.alloc(parts, true)) return fail("aoenv_set_guide_direction: no device memory for %zu bytes", dev_layout(parts).total);
+    if (mem.upload(0, dir.data(), dir.size() * sizeof(OaShift))) return fail("aoenv_set_guide_direction: the copy of the footprints failed");
+    gd.mem = std::move(mem);
+    gd.dir = static_cast<OaShift*>(gd.mem.part(0));
+    gd.zenith.assign(h_zenith_arcsec, h_zenith_arcsec + env->E);
+    gd.azimuth.assign(h_azimuth_deg, h_azimuth_deg + env->E);
+    gd.set = true;
+    return 0;
+}
+
+int aoenv_get_guide_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azimuth_deg) {
+    if (!env || !h_zenith_arcsec || !h_azimuth_deg) return fail("aoenv_get_guide_direction: null argument");
+    if (!env->guide.set) return fail("aoenv_get_guide_direction: no guide direction is set (aoenv_set_guide_direction)");
+    std::copy(env->guide.zenith.begin(), env->guide.zenith.end(), h_zenith_arcsec);
+    std::copy(env->guide.azimuth.begin(), env->guide.azimuth.end(), h_azimuth_deg);
     return 0;
 }
 

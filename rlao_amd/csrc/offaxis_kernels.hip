@@ -16,6 +16,12 @@
 // order by lane 0.  No atomics, nothing depends on n_env or on the env's place in the shard.
 // The host has asserted (oa_plan_layer) that every tap of every patch lies inside the screen; the staging loads are bounds-checked
 // all the same, as the phase kernels' are.
+//
+// k_guide_opd (aoenv_set_guide_direction) writes the same sum toward every env's GUIDE star into the atmosphere OPD buffer the phase
+// kernels then read (update_atm = 0): opd_atm = sum_l blend_l(...) sqrt(fractionalR0_l) * lambda_atm / 2 pi for all R x R pixels.
+// It needs no pupil sums, so nothing ties an env's tiles together: a workgroup of 64 x 16 lanes per (16-row x 64-column tile, env),
+// one pixel per lane, (R / 16) (R / 64) E workgroups where k_science_residual has E.  Per (tile, layer) both kernels run ONE
+// function, oa_layer_patch, and one accumulate, oa_add_pixel: for the same direction they give the same bits.
 #include "phase_device.hpp"
 #include "offaxis.hpp"
 
@@ -41,6 +47,62 @@ __device__ __forceinline__ T oa_tap4(T w0, T w1, T w2, T w3, T t0, T t1, T t2, T
     }
 }
 
+// One layer of one tile of TY = 16 rows x txe <= PW - 1 columns at (y0, x0) of env e, by a workgroup of 64 x 16 lanes (lx, ly): the
+// (tye + 3 + b) x (txe + 3 + b) apron of the torus screen into mapt (row stride MW), the horizontal pass into ht and the vertical
+// pass with the clip into the (tye + b) x (txe + b) patch pt (row stride PW); b = 1 where the env blends.  Opens with the barrier
+// behind which the previous layer's patch is no longer read and closes with the one that completes the patch.  Returns the layer
+// weight.  k_science_residual and k_guide_opd agree because they run this function.
+template <typename T, int MW, int PW>
+__device__ __forceinline__ T oa_layer_patch(const PhaseArgs& pa, const OaShift& sh, int b, int l, int e, int y0, int x0, int tye, int txe,
+                                            int lx, int ly, T* mapt, T* ht, T* pt) {
+    const LayerTaps& tp = layer_taps(pa, l, e);
+    const int S = pa.S_l[l], foot = pa.foot_l[l];
+    const T* map = static_cast<const T*>(pa.screen[l]) + (size_t)e * S * S;
+    const int r0 = y0 + foot + sh.fy + tp.dy - 1, c0 = x0 + foot + sh.fx + tp.dx - 1;
+    __syncthreads();                                          // the previous layer's patch is no longer read
+    for (int r = ly; r < tye + 3 + b; r += 16) {
+        const int rr = r0 + r;
+        for (int c = lx; c < txe + 3 + b; c += 64) {
+            const int cc = c0 + c;
+            const bool ok = rr >= 0 && rr < S && cc >= 0 && cc < S;
+            int pr = (ok ? rr : 0) + tp.oy, pc = (ok ? cc : 0) + tp.ox;   // torus: physical = (logical + origin) mod S
+            pr = pr >= S ? pr - S : pr;
+            pc = pc >= S ? pc - S : pc;
+            const T v = map[(size_t)pr * S + pc];
+            mapt[r * MW + c] = ok ? v : (T)0;
+        }
+    }
+    __syncthreads();
+    const T wx0 = (T)tp.wx[0], wx1 = (T)tp.wx[1], wx2 = (T)tp.wx[2], wx3 = (T)tp.wx[3];
+    for (int r = ly; r < tye + 3 + b; r += 16) {
+        const T* m = mapt + r * MW;
+        for (int x = lx; x < txe + b; x += 64)
+            ht[r * PW + x] = oa_tap4<T>(wx0, wx1, wx2, wx3, m[x], m[x + 1], m[x + 2], m[x + 3]);
+    }
+    __syncthreads();
+    const T wy0 = (T)tp.wy[0], wy1 = (T)tp.wy[1], wy2 = (T)tp.wy[2], wy3 = (T)tp.wy[3];
+    const T* mm = static_cast<const T*>(pa.minmax[l]) + 2 * e;
+    const T lo = mm[0], hi = mm[1];
+    const bool zero_outside = (lo > (T)0 || hi < (T)0);
+    for (int y = ly; y < tye + b; y += 16) {
+        for (int x = lx; x < txe + b; x += 64) {
+            const T* h = ht + y * PW + x;
+            const T v = oa_tap4<T>(wy0, wy1, wy2, wy3, h[0], h[PW], h[2 * PW], h[3 * PW]);
+            pt[y * PW + x] = clip_to_range(v, lo, hi, zero_outside);
+        }
+    }
+    __syncthreads();
+    return (T)tp.weight;
+}
+
+// ... and a lane's pixel of that patch: the four neighbours blended (oa_blend), or the first alone where the env does not blend, the
+// layer weight last
+template <typename T, int PW>
+__device__ __forceinline__ void oa_add_pixel(T& sup, const T* p, bool blend, T ty, T tx, T wl) {
+    const T v = blend ? oa_blend<T>(p[0], p[1], p[PW], p[PW + 1], ty, tx) : p[0];
+    sup += v * wl;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(1024) k_science_residual(const OaArgs<T> a) {
     __shared__ T mapt[(kOaTY + 4) * kOaMW];
@@ -59,56 +121,15 @@ __global__ void __launch_bounds__(1024) k_science_residual(const OaArgs<T> a) {
             const int txe = min(kOaTX, R - x0);
             T sup[2] = {(T)0, (T)0};
             for (int l = 0; l < a.pa.n_layer; ++l) {
-                const LayerTaps& tp = layer_taps(a.pa, l, e);
                 const OaShift sh = a.dir[(size_t)l * a.pa.n_env + e];
                 const bool blend = oa_blends(sh.ty, sh.tx);  // (the same for the whole workgroup)
-                const int b = blend ? 1 : 0;
-                const int S = a.pa.S_l[l], foot = a.pa.foot_l[l];
-                const T* map = static_cast<const T*>(a.pa.screen[l]) + (size_t)e * S * S;
-                const int r0 = y0 + foot + sh.fy + tp.dy - 1, c0 = x0 + foot + sh.fx + tp.dx - 1;
-                __syncthreads();                              // the previous layer's patch is no longer read
-                for (int r = ly; r < tye + 3 + b; r += 16) {
-                    const int rr = r0 + r;
-                    for (int c = lx; c < txe + 3 + b; c += 64) {
-                        const int cc = c0 + c;
-                        const bool ok = rr >= 0 && rr < S && cc >= 0 && cc < S;
-                        int pr = (ok ? rr : 0) + tp.oy, pc = (ok ? cc : 0) + tp.ox;   // torus: physical = (logical + origin) mod S
-                        pr = pr >= S ? pr - S : pr;
-                        pc = pc >= S ? pc - S : pc;
-                        const T v = map[(size_t)pr * S + pc];
-                        mapt[r * kOaMW + c] = ok ? v : (T)0;
-                    }
-                }
-                __syncthreads();
-                const T wx0 = (T)tp.wx[0], wx1 = (T)tp.wx[1], wx2 = (T)tp.wx[2], wx3 = (T)tp.wx[3];
-                for (int r = ly; r < tye + 3 + b; r += 16) {
-                    const T* m = mapt + r * kOaMW;
-                    for (int x = lx; x < txe + b; x += 64)
-                        ht[r * kOaPW + x] = oa_tap4<T>(wx0, wx1, wx2, wx3, m[x], m[x + 1], m[x + 2], m[x + 3]);
-                }
-                __syncthreads();
-                const T wy0 = (T)tp.wy[0], wy1 = (T)tp.wy[1], wy2 = (T)tp.wy[2], wy3 = (T)tp.wy[3];
-                const T* mm = static_cast<const T*>(a.pa.minmax[l]) + 2 * e;
-                const T lo = mm[0], hi = mm[1], wl = (T)tp.weight;
-                const bool zero_outside = (lo > (T)0 || hi < (T)0);
-                for (int y = ly; y < tye + b; y += 16) {
-                    for (int x = lx; x < txe + b; x += 64) {
-                        const T* h = ht + y * kOaPW + x;
-                        const T v = oa_tap4<T>(wy0, wy1, wy2, wy3, h[0], h[kOaPW], h[2 * kOaPW], h[3 * kOaPW]);
-                        pt[y * kOaPW + x] = clip_to_range(v, lo, hi, zero_outside);
-                    }
-                }
-                __syncthreads();
+                const T wl = oa_layer_patch<T, kOaMW, kOaPW>(a.pa, sh, blend ? 1 : 0, l, e, y0, x0, tye, txe, lx, ly, mapt, ht, pt);
                 if (ly < tye) {
                     const T ty = (T)sh.ty, tx = (T)sh.tx;
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         const int x = lx + 64 * i;
-                        if (x < txe) {
-                            const T* p = pt + ly * kOaPW + x;
-                            const T v = blend ? oa_blend<T>(p[0], p[1], p[kOaPW], p[kOaPW + 1], ty, tx) : p[0];
-                            sup[i] += v * wl;
-                        }
+                        if (x < txe) oa_add_pixel<T, kOaPW>(sup[i], pt + ly * kOaPW + x, blend, ty, tx, wl);
                     }
                 }
             }
@@ -163,5 +184,41 @@ int launch_science_residual(const OaArgs<T>& a, hipStream_t st) {
 }
 template int launch_science_residual<float>(const OaArgs<float>&, hipStream_t);
 template int launch_science_residual<double>(const OaArgs<double>&, hipStream_t);
+
+// ---- the guide star's line of sight ----------------------------------------------------------------------------------------------
+constexpr int kGdTY = 16, kGdTX = 64;                        // one pixel per lane
+constexpr int kGdMW = kGdTX + 8, kGdPW = kGdTX + 1;
+
+template <typename T>
+__global__ void __launch_bounds__(1024) k_guide_opd(const GuideArgs<T> a, int tiles_x, int tiles) {
+    __shared__ T mapt[(kGdTY + 4) * kGdMW];
+    __shared__ T ht[(kGdTY + 4) * kGdPW];
+    __shared__ T pt[(kGdTY + 1) * kGdPW];
+
+    const int R = a.R, e = blockIdx.x / tiles, tile = blockIdx.x - e * tiles;
+    const int y0 = (tile / tiles_x) * kGdTY, x0 = (tile % tiles_x) * kGdTX;
+    const int lx = threadIdx.x, ly = threadIdx.y;
+    const int tye = min(kGdTY, R - y0), txe = min(kGdTX, R - x0);
+    const bool mine = ly < tye && lx < txe;
+    T sup = (T)0;
+    for (int l = 0; l < a.pa.n_layer; ++l) {
+        const OaShift sh = a.dir[(size_t)l * a.pa.n_env + e];
+        const bool blend = oa_blends(sh.ty, sh.tx);          // (the same for the whole workgroup)
+        const T wl = oa_layer_patch<T, kGdMW, kGdPW>(a.pa, sh, blend ? 1 : 0, l, e, y0, x0, tye, txe, lx, ly, mapt, ht, pt);
+        if (mine) oa_add_pixel<T, kGdPW>(sup, pt + ly * kGdPW + lx, blend, (T)sh.ty, (T)sh.tx, wl);
+    }
+    if (mine) a.opd_atm[(size_t)e * R * R + (size_t)(y0 + ly) * R + (x0 + lx)] = sup * a.atm_scale;
+}
+
+template <typename T>
+int launch_guide_opd(const GuideArgs<T>& a, hipStream_t st) {
+    if (a.pa.n_env < 1 || a.R < 1) return 0;
+    const int tiles_x = (a.R + kGdTX - 1) / kGdTX, tiles = tiles_x * ((a.R + kGdTY - 1) / kGdTY);
+    hipLaunchKernelGGL(k_guide_opd<T>, dim3((unsigned)a.pa.n_env * tiles), dim3(64, 16), 0, st, a, tiles_x, tiles);
+    AO_HIP(hipGetLastError());
+    return 0;
+}
+template int launch_guide_opd<float>(const GuideArgs<float>&, hipStream_t);
+template int launch_guide_opd<double>(const GuideArgs<double>&, hipStream_t);
 
 }  // namespace ao

@@ -836,7 +836,8 @@ class _Cam:
 class _SourceProxy:
     """``env.source`` / ``env.ngs`` (MAIN/OOPAOEnvRazor/OOPAOEnvRazor.py:644-647 reaches into ``source.nPhoton``): the guide star
     of every env.  ``magnitude`` and ``nPhoton`` are ``[n_envs]``; assigning either (a scalar or an array) is
-    ``set_magnitude_per_env``."""
+    ``set_magnitude_per_env``.  ``coordinates`` is ``[n_envs, 2]`` (zenith arcsec, azimuth deg; zeros while no direction is set);
+    assigning one pair for every env or an ``[n_envs, 2]`` array is ``set_guide_direction``."""
     tag = "source"
     type = "NGS"
 
@@ -863,8 +864,15 @@ class _SourceProxy:
     def nPhoton(self):
         return self._e.nPhoton * calib.flux_scale(self._e.magnitude, self._e.param.magnitude)
 
+    @property
+    def coordinates(self):
+        d = self._e.guide_direction
+        return np.zeros((self._e.n_envs, 2)) if d is None else d
+
     def __setattr__(self, name, value):
-        if name == "magnitude":
+        if name == "coordinates":
+            _assign_coordinates(value, self._e.n_envs, self._e.set_guide_direction)
+        elif name == "magnitude":
             self._e.set_magnitude_per_env(value)
         elif name == "nPhoton":
             v = np.asarray(_host(value), dtype=np.float64)
@@ -873,6 +881,17 @@ class _SourceProxy:
             self._e.set_magnitude_per_env(-2.5 * np.log10(v / self.zeroPoint))
         else:
             raise AttributeError(f"cannot set source.{name}")
+
+
+def _assign_coordinates(value, n_envs, setter):
+    """``source.coordinates = value``: one ``[zenith, azimuth]`` pair for every env, or an ``[n_envs, 2]`` array."""
+    v = as_float64(value, "coordinates")
+    if v.shape == (2,):
+        setter(v[0], v[1])
+    elif v.shape == (n_envs, 2):
+        setter(np.ascontiguousarray(v[:, 0]), np.ascontiguousarray(v[:, 1]))
+    else:
+        raise ValueError(f"coordinates must be [zenith, azimuth] or have shape ({n_envs}, 2), got {v.shape}")
 
 
 class _ScienceSourceProxy:
@@ -897,13 +916,7 @@ class _ScienceSourceProxy:
     def __setattr__(self, name, value):
         if name != "coordinates":
             raise AttributeError(f"cannot set src.{name}")
-        v = as_float64(value, "coordinates")
-        if v.shape == (2,):
-            self._e.set_science_direction(v[0], v[1])
-        elif v.shape == (self._e.n_envs, 2):
-            self._e.set_science_direction(np.ascontiguousarray(v[:, 0]), np.ascontiguousarray(v[:, 1]))
-        else:
-            raise ValueError(f"coordinates must be [zenith, azimuth] or have shape ({self._e.n_envs}, 2), got {v.shape}")
+        _assign_coordinates(value, self._e.n_envs, self._e.set_science_direction)
 
 
 class _WfsProxy:
@@ -1085,6 +1098,7 @@ class BatchedAOEnv:
         self._le = None                                            # (sum, sum_log10 or None, count) of an attached long exposure
         self._oa = None                                            # [n_envs, 2] (zenith arcsec, azimuth deg) while a science direction is set
         self._oa_rec = None                                        # the tensor of an attached science-direction record (kept alive here)
+        self._guide = None                                         # [n_envs, 2] while a guide direction is set
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
         self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
         self.source = self.ngs = None
@@ -1210,6 +1224,7 @@ class BatchedAOEnv:
         self._wf = self._wf_rec = None                               # ... and no wavefront basis (it is indexed by the pupil's pixels)
         self._sci = self._le = None                                  # ... and no science camera (it holds the pupil's amplitude)
         self._oa = self._oa_rec = None                               # ... and no science direction
+        self._guide = None                                           # ... and no guide direction
         self._surface = "zonal"
         sh = self._shard
         if p.nLayer > 0 and hasattr(sh.lib, "aoenv_set_field"):     # what a science direction is computed from (absent: an A/B library of AOENV_LIB)
@@ -1994,12 +2009,7 @@ class BatchedAOEnv:
         ``science_atmosphere()``, ``project_wavefront("science")``, ``science_psf()`` and the long exposure look through the layers
         toward the target, behind the mirror surface the guide star's sensor saw (MAIN_CODE/OOPAOEnv/OOPAOEnv.py:140-146, 303-304;
         OOPAO/Atmosphere.py:313-334, 439-450).  Bad arguments raise before anything is touched.  Not part of ``get_state``."""
-        cur = self._oa if self._oa is not None else np.zeros((self.n_envs, 2))
-        zen = assign_per_env(zenith, env_ids, self.n_envs, cur[:, 0], "zenith")
-        az = assign_per_env(azimuth, env_ids, self.n_envs, cur[:, 1], "azimuth")
-        fov = float(self.param.fov)
-        if (zen < 0).any() or (zen > fov / 2).any():
-            raise ValueError(f"zenith must lie in [0, fov / 2 = {fov / 2}] arcsec")
+        zen, az = self._directions(self._oa, zenith, azimuth, env_ids)
         L.call(self._shard, "aoenv_set_science_direction", zen, az, self._stream())
         self._oa = np.stack([zen, az], axis=1)
 
@@ -2056,6 +2066,42 @@ class BatchedAOEnv:
         """Detaches the record; the loops run as without one."""
         L.call(self._shard, "aoenv_set_science_direction_record", None, 0, 0)
         self._oa_rec = None
+
+    # -- off-axis guide star (aoenv_set_guide_direction; the reference's `ngs.coordinates = [zenith, azimuth]`, atm * ngs) -------------
+    def _directions(self, cur, zenith, azimuth, env_ids):
+        """The ``[n_envs]`` zenith and azimuth arrays of a per-env assignment on top of ``cur``, range-checked."""
+        cur = cur if cur is not None else np.zeros((self.n_envs, 2))
+        zen = assign_per_env(zenith, env_ids, self.n_envs, cur[:, 0], "zenith")
+        az = assign_per_env(azimuth, env_ids, self.n_envs, cur[:, 1], "azimuth")
+        fov = float(self.param.fov)
+        if (zen < 0).any() or (zen > fov / 2).any():
+            raise ValueError(f"zenith must lie in [0, fov / 2 = {fov / 2}] arcsec")
+        return zen, az
+
+    def set_guide_direction(self, zenith, azimuth=0.0, env_ids=None):
+        """The guide star of every env: ``zenith`` [arcsec, ``0 .. fov / 2``] and ``azimuth`` [deg], scalars or one value per
+        (listed) env; the other envs keep their direction, or sit on axis if none was set.  From here on the sensor of every loop
+        looks through the layers toward the star (``atm * ngs`` with ``ngs.coordinates``, OOPAO/Atmosphere.py:313-334, 439-450):
+        observation, reward, Strehl, telemetry and ``AOENV_B_OPD_ATM`` are those of that line of sight, and the science read-outs
+        difference against it.  The shard runs the batched kernels while a direction is set (``fused_step`` is False).  Bad
+        arguments raise before anything is touched.  Not part of ``get_state``."""
+        zen, az = self._directions(self._guide, zenith, azimuth, env_ids)
+        L.call(self._shard, "aoenv_set_guide_direction", zen, az, self._stream())
+        self._guide = np.stack([zen, az], axis=1)
+
+    def clear_guide_direction(self):
+        """No guide direction: the sensor looks along the axis again, on the path the shard had, nothing is left behind."""
+        L.call(self._shard, "aoenv_set_guide_direction", None, None, self._stream())
+        self._guide = None
+
+    @property
+    def guide_direction(self):
+        """``[n_envs, 2]`` (zenith arcsec, azimuth deg) as the library holds it, None while no direction is set."""
+        if self._guide is None:
+            return None
+        zen, az = np.zeros(self.n_envs), np.zeros(self.n_envs)
+        L.call(self._shard, "aoenv_get_guide_direction", zen, az)
+        return np.stack([zen, az], axis=1)
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

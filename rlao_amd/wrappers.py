@@ -172,6 +172,16 @@ class TorchWrapper:
     def science_direction(self):
         return self._env.science_direction
 
+    def set_guide_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_guide_direction(zenith, azimuth, env_ids)
+
+    def clear_guide_direction(self):
+        return self._env.clear_guide_direction()
+
+    @property
+    def guide_direction(self):
+        return self._env.guide_direction
+
     @property
     def src(self):
         return self._env.src
@@ -350,6 +360,16 @@ class TimeDelayEnv:
     def science_direction(self):
         return self._env.science_direction
 
+    def set_guide_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_guide_direction(zenith, azimuth, env_ids)
+
+    def clear_guide_direction(self):
+        return self._env.clear_guide_direction()
+
+    @property
+    def guide_direction(self):
+        return self._env.guide_direction
+
     @property
     def src(self):
         return self._env.src
@@ -498,6 +518,16 @@ class HistoryEnv:
     @property
     def science_direction(self):
         return self._env.science_direction
+
+    def set_guide_direction(self, zenith, azimuth=0.0, env_ids=None):
+        return self._env.set_guide_direction(zenith, azimuth, env_ids)
+
+    def clear_guide_direction(self):
+        return self._env.clear_guide_direction()
+
+    @property
+    def guide_direction(self):
+        return self._env.guide_direction
 
     @property
     def src(self):
