@@ -748,6 +748,53 @@ int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int 
 int aoenv_set_guide_direction(AoEnv* env, const double* h_zenith_arcsec, const double* h_azimuth_deg, void* stream);
 int aoenv_get_guide_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azimuth_deg);
 
+/* Replaces: a static optical-path map in the optical train, the reference's OPD_map and NCPA objects (OOPAO/OPD_map.py,
+ * OOPAO/NCPA.py; `ngs*tel*map*dm*wfs`, applied as tel.OPD += obj.OPD, tel.OPD_no_pupil += obj.OPD, OOPAO/Telescope.py:502-512) -- for
+ * the envs of ONE shard, one map per env and per arm.  h_wfs is the map S_w the wavefront sensor sees, h_sci the map S_s the
+ * science camera sees: float64, metres, unmasked.  per_env is the number of maps in each array: n_env for [n_env][R*R], one map
+ * per env, or 0 for ONE map [R*R] for the whole shard (one copy is held and read with stride 0).  A NULL arm is a zero arm; both NULL clear the feature and free its memory.  A common-path
+ * aberration is the same map in both arms; the classic non-common-path case is h_wfs = N, h_sci = NULL: the loop drives the
+ * sensor's residual to zero and prints -N into the science image.
+ * Sensor arm:  OPD_no_pupil = atm + S_w + dm,  OPD = that times the pupil.  Observation, reward, Strehl, residual rms,
+ * AOENV_B_PHASE and a geometric shard's unmasked phase (S_w unmasked there) include S_w; the atmosphere's own numbers
+ * (AOENV_B_OPD_ATM, the `total` telemetry, aoenv_project_wavefront(AOENV_WF_ATMOSPHERE)) do not.  The map is added on the mirror
+ * side of the sum: while S_w is set the shard forms mirror surface + S_w ahead of the phase kernel, wherever the command changes,
+ * and k_phase<T> reads it (as for actuator factor pairs and a dense mirror): the batched kernels run, aoenv_fused_step_active
+ * reports 0 and the step pairs stand down until the map is cleared, when the shard launches what it launched before.  A separable
+ * mirror (shared tables, aoenv_set_dm_env's, the composite two-mirror tables) forms Gy C Gx^T + S_w on the fp32 matrix cores on
+ * float32 shards up to 128 actuators across (k_dm_rows, then k_dm_static_mfma, whose accumulators start from the map), and as one
+ * fma chain per pixel on float64 shards, above 128 actuators across and under AOENV_PATH_DM_STATIC_GENERAL (k_dm_static); the order
+ * of either sum depends on (R, n_act) alone, there are no atomics, and an env has the same bits in any shard and at any place in
+ * it.  A shard that forms its surface ahead anyway (actuator pairs, a dense mirror) gets one trailing launch that adds the map into
+ * a buffer of its own; aoenv_get_dm_surface keeps returning the mirror alone (and stays refused on a separable mirror).
+ * Science arm:  phase_sci = AOENV_B_PHASE + ((OPD_no_pupil_sci - AOENV_B_OPD_ATM) + (S_s - S_w)) 2 pi / lambda_src inside the pupil, 0
+ * outside; the first bracket only while a science direction is set.  The host forms D = S_s - S_w in float64 and the device holds
+ * S_w and D in the env dtype; S_w is held whenever h_wfs is not NULL (zeros included: the shard then takes the path
+ * of a shard with a map), D only where it is not zero everywhere in the env dtype (a common-path aberration leaves the science arm
+ * on the sensor's phase).  While D is held, "the science arm differs from the sensor's"
+ * exactly as under a science direction: aoenv_science_psf(flat = 0), the long exposure, aoenv_science_residual,
+ * aoenv_project_wavefront(AOENV_WF_SCIENCE) and aoenv_set_science_direction_record look at phase_sci, formed by one light launch
+ * that walks no layer (k_science_static; pupil sums in float64 in a fixed order) or, under a direction, by k_science_residual with D
+ * as one more term.  Without a direction aoenv_science_residual's d_opd_atm_sci must be NULL.
+ * Calibration never sees the maps (set them after the tables are uploaded): a sensor-arm map is an offset in the slopes.
+ * Configuration like the guide direction: copied before the call returns (the stream is waited for once), in no checkpoint buffer,
+ * untouched by aoenv_reset_envs and aoenv_new_screens*.  No buffer id, no profiled kernel and no ABI version go with it.
+ * Device memory (ONE block): the maps held, R^2 sizeof(dtype) each per env (or once); with S_w n_env R^2 sizeof(dtype) of surface
+ * and, on a separable mirror, n_env (R pad 128) 4 ga_stride sizeof(float) of Gy C or n_env n_act^2 sizeof(dtype) of command images;
+ * with D n_env R^2 sizeof(dtype) of phase_sci.
+ * Refused, with nothing changed and nothing launched: per_env that is neither 0 nor the shard's n_env (arrays made for a shard of
+ * another size), a non-finite entry or one that is not finite in the env dtype (the arm and index are reported), an allocation
+ * that fails.
+ * aoenv_get_static_opd fills h_wfs and h_sci ([n_env][R*R] float64 each, either may be NULL) with the maps as given (a shared map
+ * repeated for every env, a zero arm as zeros); refused while no map is set. */
+int aoenv_set_static_opd(AoEnv* env, const double* h_wfs, const double* h_sci, int per_env, void* stream);
+int aoenv_get_static_opd(AoEnv* env, double* h_wfs, double* h_sci);
+/* Which launch forms mirror surface + S_w with the maps, tables and options as they are now (an answer, not a status, like
+ * aoenv_fused_step_active): 0 = no sensor-arm map, 1 = k_dm_rows + k_dm_static_mfma, 2 = k_coefs_image + k_dm_static<T>, 3 = the
+ * trailing k_static_add behind actuator pairs or a dense mirror; -1 for a null env.  h_launches, if not NULL, receives int64 [4]:
+ * how often each of these has refreshed a surface since the shard was created (index 0 is never counted). */
+int aoenv_static_surface_path(AoEnv* env, int64_t* h_launches);
+
 /* Replaces: the WFS camera settings wfs.cam.{photonNoise, readoutNoise, QE, darkCurrent, integrationTime, FWC, bits, gain,
  * sensor} (OOPAO/Detector.py:19-60; Papyrus: photonNoise = True, MAIN/OOPAOEnv/OOPAOEnv.py:379; Razor:
  * OOPAOEnvRazor.py:243-250, 333).  The frame of every measurement then goes through integrate() + readout()
@@ -831,7 +878,7 @@ enum AoOption {
                                  whole-pixel round or crosses a pixel in that one (two steps, one workgroup per env, nothing read back
                                  from global memory in between; bit-identical results).  0: one launch per step */
     AOENV_OPT_FORCE_PATH = 99 /* AoPath bits (default 0): force the general kernel where a specialised one applies; any bit set
-                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL, AOENV_PATH_SCI_GENERAL and AOENV_PATH_DM_PAIRS_GENERAL also keeps the shard off the fused step
+                                 other than AOENV_PATH_MODAL_GEMM, AOENV_PATH_SH_PLAIN, AOENV_PATH_WF_GENERAL, AOENV_PATH_SCI_GENERAL, AOENV_PATH_DM_PAIRS_GENERAL and AOENV_PATH_DM_STATIC_GENERAL also keeps the shard off the fused step
                                  kernel; other bits are rejected */
 };
 /* Bits of AOENV_OPT_FORCE_PATH: each selects another correct implementation (parity tests compare it with the default). */
@@ -853,6 +900,9 @@ enum AoPath {
     AOENV_PATH_DM_PAIRS_GENERAL = 32768, /* the surface of actuator factor pairs (aoenv_set_dm_pairs) as one fma chain per pixel on float32
                                           shards too, instead of the matrix-core kernel.  It touches nothing of a shard without pairs,
                                           which stays on the fused step kernel */
+    AOENV_PATH_DM_STATIC_GENERAL = 65536, /* the surface of a separable mirror with a sensor-arm static map (aoenv_set_static_opd) as
+                                          one fma chain per pixel on float32 shards too, instead of the matrix-core kernel.  It touches
+                                          nothing of a shard without such a map, which stays on the fused step kernel */
     AOENV_PATH_SH_PLAIN = 4096         /* the general instantiation of the fused step kernel (run-time camera and trig tests, the
                                           pixel-by-pixel stage A epilogue) and the plain C++ lenslet transform, there and in the
                                           batched spots kernel, instead of the forms specialised for the launch and the register-pair

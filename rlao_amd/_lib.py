@@ -30,6 +30,7 @@ MAX_DELAY = 8                                                      # AOENV_MAX_D
 PATH_PHASE_DWORD, PATH_GENERIC, PATH_PYR_ROUND_ROBIN, PATH_MODAL_GEMM, PATH_SH_PLAIN, PATH_WF_GENERAL = 256, 512, 1024, 2048, 4096, 8192
 PATH_SCI_GENERAL = 16384
 PATH_DM_PAIRS_GENERAL = 32768
+PATH_DM_STATIC_GENERAL = 65536
 SCI_LOG10 = 1                                                      # enum AoScienceFlag
 WF_RESIDUAL, WF_ATMOSPHERE, WF_SCIENCE = 1, 2, 4                   # enum AoWavefront
 MAX_WF_MODES = 1024                                                # AOENV_MAX_WF_MODES
@@ -147,6 +148,9 @@ EXPORTS = {
     "aoenv_set_science_direction_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "aoenv_set_guide_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_get_guide_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_set_static_opd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "aoenv_get_static_opd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "aoenv_static_surface_path": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -173,7 +177,8 @@ EXPORTS = {
 
 _LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
                   "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds", "aoenv_get_phase_no_pupil",
-                  "aoenv_set_guide_direction", "aoenv_get_guide_direction")
+                  "aoenv_set_guide_direction", "aoenv_get_guide_direction", "aoenv_set_static_opd", "aoenv_get_static_opd",
+                  "aoenv_static_surface_path")
 
 
 class AoEnvError(RuntimeError):

@@ -535,6 +535,39 @@ def zernike_basis(pupil: np.ndarray, D: float, n_modes: int) -> np.ndarray:
     return out
 
 
+def ncpa_map(pupil: np.ndarray, D: float, f2=None, coefficients=None, seed: int = 5, basis: str = "zernike") -> np.ndarray:
+    """A static aberration map ``[R, R]`` in metres, zero outside the pupil, as the reference's ``NCPA`` object makes it on its
+    Zernike basis (OOPAO/NCPA.py; ``B[:, :, i]`` there is column ``i`` of ``zernike_basis``: Noll mode ``i + 2``).
+    ``f2=[amplitude, first, last, cutoff]``: the 1/f^2 law of ``NCPA_f2_law`` -- mode ``i`` in ``range(first, last)`` gets the
+    coefficient ``RandomState(i * seed).randn() / sqrt(i + cutoff)``, and the sum is scaled to ``amplitude`` rms over the pupil.
+    ``coefficients=[c0, c1, ...]``: the linear form, ``sum_i c_i B_i`` (NCPA.py:73-84).  Exactly one of the two.  The ``KL`` and
+    ``M2C`` bases of the reference are not restated.  Pure host code."""
+    if basis != "zernike":
+        raise ValueError(f"ncpa_map: basis {basis!r} is not restated here, only 'zernike'")
+    if (f2 is None) == (coefficients is None):
+        raise ValueError("ncpa_map: give exactly one of f2=[amplitude, first, last, cutoff] and coefficients=[...]")
+    pupil = np.asarray(pupil) > 0
+    if f2 is not None:
+        if len(f2) != 4:
+            raise ValueError("ncpa_map: f2 is [amplitude, first mode, last mode, cutoff]")
+        amplitude, first, last, cutoff = float(f2[0]), int(f2[1]), int(f2[2]), float(f2[3])
+        if not 0 <= first < last:
+            raise ValueError("ncpa_map: f2 needs 0 <= first < last")
+        c = np.zeros(last)
+        for i in range(first, last):
+            c[i] = np.random.RandomState(i * int(seed)).randn() / np.sqrt(i + cutoff)
+    else:
+        c = np.asarray(coefficients, dtype=np.float64).reshape(-1)
+        if c.size < 1 or not np.isfinite(c).all():
+            raise ValueError("ncpa_map: coefficients must be a non-empty list of finite numbers")
+    on_pupil = zernike_basis(pupil, D, c.size) @ c
+    if f2 is not None:
+        on_pupil = on_pupil / np.std(on_pupil) * amplitude
+    out = np.zeros(pupil.shape)
+    out[pupil] = on_pupil
+    return out
+
+
 def zernike_m2c(dm: DMTables, pupil: np.ndarray, D: float, n_modes: int) -> np.ndarray:
     """M2C = pinv(dm.modes[pupil]) @ Z.modes  (MAIN/OOPAOEnv/OOPAOEnv.py:258, OOPAOEnvRazor.py:261).
     Beyond ~2000 actuators (ELT: 5209 actuators x 181 k pupil pixels) the SVD behind ``pinv`` takes hours on the host:

@@ -537,6 +537,8 @@ struct OaArgs {
     int R, n_pupil;
     T atm_scale, src_scale;
     double src_scale_d;    // 2 pi / lambda_src
+    const T* delta;        // static difference map S_s - S_w (aoenv_set_static_opd), env e at + e * delta_env, or null: no such term
+    size_t delta_env;
 };
 template <typename T>
 int launch_science_residual(const OaArgs<T>& a, hipStream_t st);

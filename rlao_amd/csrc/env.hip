@@ -21,6 +21,7 @@
 #include "sh_geometric.hpp"
 #include "science.hpp"
 #include "star_env.hpp"
+#include "static_opd.hpp"
 #include "wavefront.hpp"
 #include "offaxis.hpp"
 
@@ -208,8 +209,6 @@ struct AoEnv {
         void* phase_sci = nullptr;          // [E][R*R] what the science camera and the projection look at
         void* rec = nullptr;                // caller-owned [n_slots][2][E] (rms nm, Strehl), or null: nothing is recorded
         int i_base = 0, n_slots = 0;
-        // stepped frame i needs the step's phase and on-axis atmosphere OPD in HBM
-        bool reads_step(bool accumulates) const { return rec || (set && accumulates); }
     } oa;
     // off-axis guide star (aoenv_set_guide_direction, offaxis.hpp): the footprints toward the star of every env, in ONE block of its
     // own (NULL arrays free it).  While set, run_phase forms the atmosphere OPD toward the star (k_guide_opd) ahead of the phase kernel
@@ -257,9 +256,43 @@ struct AoEnv {
         float *pya = nullptr, *pxa = nullptr;
     } dm_pairs;
     PairsLayout pairs_layout() const { PairsLayout l; l.R = R; l.A = A; return l; }
-    // this shard forms its DM surface ahead of the phase kernel (refresh_dense_dm), which reads it from surface()
-    bool dm_surface_ahead() const { return !c.dm_separable || dm_pairs.on; }
-    void* surface() const { return dm_pairs.on ? dm_pairs.opd : dm_opd; }
+    // static aberrations (aoenv_set_static_opd, static_opd.hpp): configuration like the guide direction, in ONE block of its own
+    // (two NULL arms free it).  w: the sensor arm's map S_w; delta: S_s - S_w, what the science arm adds to the sensor's phase;
+    // either may be absent: w is held whenever the caller passed the sensor arm (zeros included: the shard then takes the path of a
+    // shard with a map), delta only where it is not zero everywhere in the env dtype
+    struct Static {
+        Block mem;
+        void* w = nullptr;                  // [n][R*R] env dtype, n = E or 1 (map_env = 0)
+        void* delta = nullptr;              // [n][R*R]
+        size_t map_env = 0;                 // elements between the envs' maps: R*R, or 0 for one map for the shard
+        void* surf = nullptr;               // [E][R*R] mirror surface + S_w, what k_phase<T> reads while w is set
+        float* rows = nullptr;              // [E][Rpad128][4][ga_stride] Gy C (k_dm_rows): float32 separable mirrors up to 128 across
+        void* cimg = nullptr;               // [E][nAct^2] command images: the other separable mirrors
+        void* phase_sci = nullptr;          // [E][R*R] the science arm's phase while delta is set and no science direction owns one
+        std::vector<double> h_w, h_s;       // the arms as given ([n][R*R]; empty: a NULL arm), for aoenv_get_static_opd
+        bool on = false;
+    } stat;
+    // the mirror's own surface is formed ahead of the phase kernel (actuator pairs, a dense mirror) in mirror_surface()
+    bool mirror_ahead() const { return !c.dm_separable || dm_pairs.on; }
+    void* mirror_surface() const { return dm_pairs.on ? dm_pairs.opd : dm_opd; }
+    // this shard forms its DM surface ahead of the phase kernel (refresh_dense_dm), which reads it from surface(): the mirror's own
+    // where there is one, and the sum of mirror and map for every kind of mirror while a sensor-arm static map is set
+    bool dm_surface_ahead() const { return mirror_ahead() || stat.w; }
+    // which launch forms mirror + map (aoenv_static_surface_path): 0 no sensor-arm map, 1 k_dm_rows + k_dm_static_mfma, 2
+    // k_coefs_image + k_dm_static<T>, 3 the trailing k_static_add behind a mirror that is formed ahead anyway.  refresh_dense_dm
+    // branches on this and counts what it launched
+    int static_path() const {
+        if (!stat.w) return 0;
+        if (mirror_ahead()) return 3;
+        return esz == 4 && stat.rows && use_mfma && !(force_path & AOENV_PATH_DM_STATIC_GENERAL) ? 1 : 2;
+    }
+    int64_t static_launches[4] = {0, 0, 0, 0};                     // refreshes of the surface by path, for the shard's life
+    void* surface() const { return stat.w ? stat.surf : mirror_surface(); }
+    // the science arm differs from the sensor's: a science direction, or a static difference map; its phase lives in sci_phase()
+    bool sci_differs() const { return oa.set || stat.delta; }
+    void* sci_phase() const { return oa.set ? oa.phase_sci : stat.phase_sci; }
+    // stepped frame i needs the step's phase (and, for a direction, the on-axis atmosphere OPD) in HBM
+    bool sci_reads_step(bool accumulates) const { return oa.rec || (sci_differs() && accumulates); }
     // per-env guide stars (aoenv_set_flux_env / aoenv_set_threshold_env, star_env.hpp): [E] each in the env dtype, a block of its
     // own each (NULL frees it); absent = null, and the kernels are then handed null pointers
     struct StarDev {
@@ -856,9 +889,53 @@ int run_wfs(AoEnv* env, hipStream_t st) {
 // The one place that forms the DM surface of a shard that forms it ahead of the phase kernel (AoEnv::dm_surface_ahead).
 // Actuator factor pairs: S_e = (Py_e diag(c_e)) Px_e^T per env (dm_pairs_kernels.hip).
 // dm.OPD = modes @ coefs for a dense (non-separable, e.g. two chained mirrors) DM: [E][R^2] = coefs [E][A] . modes [R^2][A]^T
+// With a sensor-arm static map (static_opd.hpp) every kind of mirror forms surface + S_w here: a separable mirror Gy C Gx^T + S_w in
+// one product whose accumulators start from the map (k_dm_rows + k_dm_static_mfma, or k_coefs_image + k_dm_static<T>), a mirror that
+// is formed ahead anyway by one trailing launch that adds the map into the buffer k_phase<T> reads (the mirror's own stays the
+// mirror alone, aoenv_get_dm_surface).
+template <typename T>
+int refresh_mirror_surface(AoEnv* env, hipStream_t st);
 template <typename T>
 int refresh_dense_dm(AoEnv* env, hipStream_t st) {
     if (!env->dm_surface_ahead()) return 0;
+    if (env->mirror_ahead()) AO_TRY(refresh_mirror_surface<T>(env, st));
+    const AoEnv::Static& sa = env->stat;
+    if (!sa.w) return 0;
+    StaticDmArgs<T> a{};
+    a.map = env->as<T>(sa.w);
+    a.map_env = sa.map_env;
+    a.out = env->as<T>(sa.surf);
+    a.R = env->R;
+    a.n_act = env->nAct;
+    const int path = env->static_path();
+    env->static_launches[path] += 1;
+    if (path == 3) {
+        a.base = env->as<T>(env->mirror_surface());
+        return launch_static_add<T>(a, env->E, st);
+    }
+    const AoEnv::DmEnv& de = env->dm_env;                          // every env its own mirror: its tables, a block apart
+    const DmLayout dl = env->dm_layout();
+    if constexpr (std::is_same<T, float>::value) {
+        if (path == 1) {
+            const size_t ga_env = de.on ? dl.ga_elems() : 0;
+            AO_TRY(launch_dm_rows(env->as<float>(env->cmd()), env->act_idx, de.on ? de.gya : env->gya, ga_env, sa.rows, env->E, env->R,
+                                  env->nAct, env->A, env->ga_stride, st));
+            a.s1a = sa.rows;
+            a.gxa = de.on ? de.gxa : env->gxa;
+            a.ga_env = ga_env;
+            a.ga_stride = env->ga_stride;
+            return launch_dm_static_mfma(a, env->E, st);
+        }
+    }
+    AO_TRY(launch_coefs_image<T>(env->as<T>(env->cmd()), env->act_idx, env->as<T>(sa.cimg), env->E, env->nAct, env->A, st));
+    a.coefs_img = env->as<T>(sa.cimg);
+    a.gx = env->as<T>(de.on ? de.gx : env->gx);
+    a.gy = env->as<T>(de.on ? de.gy : env->gy);
+    a.g_env = de.on ? dl.g_elems() : 0;
+    return launch_dm_static<T>(a, env->E, st);
+}
+template <typename T>
+int refresh_mirror_surface(AoEnv* env, hipStream_t st) {
     if (env->dm_pairs.on) {
         const AoEnv::DmPairs& dp = env->dm_pairs;
         const PairsLayout pl = env->pairs_layout();
@@ -971,7 +1048,7 @@ bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
     return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && !env->guide.set && env->n_modes > 0 &&
-           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL)) == 0 &&
+           env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL | AOENV_PATH_DM_STATIC_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
 
@@ -1044,7 +1121,7 @@ int run_fused_step<float>(AoEnv* env, int i, const void* d_action, void* d_obs, 
     // (a wavefront record reads the phase -- and the atmosphere, if it records it -- of EVERY step: both stores, not the frame's;
     // the long exposure reads the phase of every frame it accumulates)
     const int rec = env->wf.recorded();
-    const bool oa = env->oa.reads_step(env->sci.accumulates(i));   // (the science direction reads both of every step it serves)
+    const bool oa = env->sci_reads_step(env->sci.accumulates(i));  // (the science arm reads both of every step it serves)
     fill_phase_args<float>(env, pa, pb, 1, (env->store_opd_atm || (rec & AOENV_WF_ATMOSPHERE) || oa) ? 1 : 0, 1);
     a.k = make_phase_kargs<float>(pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
     a.sc = sh_const<float>(env);
@@ -1200,7 +1277,7 @@ int wf_project(AoEnv* env, int what, void* out, hipStream_t st) {
     WfArgs<T> a{};
     int w = 0;
     if (what & (AOENV_WF_RESIDUAL | AOENV_WF_SCIENCE)) {            // (the residual toward the target: the caller has formed it)
-        a.x[w] = env->as<T>((what & AOENV_WF_SCIENCE) ? env->oa.phase_sci : env->phase);
+        a.x[w] = env->as<T>((what & AOENV_WF_SCIENCE) ? env->sci_phase() : env->phase);
         a.scale[w] = (T)(env->c.src_wavelength / (2.0 * M_PI));
         a.use_scale[w] = 1;
         ++w;
@@ -1268,10 +1345,28 @@ static int wf_window_check(const AoEnv* env, int i0, int n) {
 
 // ---- off-axis science target (offaxis.hpp, offaxis_kernels.hip) -------------------------------------------------------------------
 // The residual toward the target from the screens, AOENV_B_PHASE and the on-axis atmosphere OPD as they stand.  One launch, not
-// attributed by aoenv_profile.
+// attributed by aoenv_profile.  This is the one place the science arm's phase is formed: callers have checked AoEnv::sci_differs(),
+// and without a direction it is AOENV_B_PHASE plus the static difference map (k_science_static; opd_atm_sci is then not written).
 template <typename T>
 int oa_residual(AoEnv* env, void* phase_sci, void* opd_atm_sci, void* rms_nm, void* strehl, hipStream_t st) {
+    if (!env->oa.set) {                                            // a static difference map alone: no layer is walked
+        SciStaticArgs<T> s{};
+        s.pupil = env->pupil;
+        s.phase = env->as<T>(env->phase);
+        s.delta = env->as<T>(env->stat.delta);
+        s.delta_env = env->stat.map_env;
+        s.phase_sci = static_cast<T*>(phase_sci);
+        s.rms_nm = static_cast<T*>(rms_nm);
+        s.strehl = static_cast<T*>(strehl);
+        s.R = env->R;
+        s.n_pupil = env->n_pupil;
+        s.src_scale = (T)(6.283185307179586476925286766559 / env->c.src_wavelength);
+        s.src_scale_d = 6.283185307179586476925286766559 / env->c.src_wavelength;
+        return launch_science_static<T>(s, env->E, st);
+    }
     OaArgs<T> a{};
+    a.delta = env->as<T>(env->stat.delta);
+    a.delta_env = env->stat.map_env;
     PhaseBuffers<T> pb;
     fill_phase_args<T>(env, a.pa, pb, 1, 0, 0);
     const KArgs<T> k = make_phase_kargs<T>(a.pa, pb, env->R, env->nAct, env->A, env->c.atm_wavelength, env->c.src_wavelength);
@@ -1305,7 +1400,11 @@ int oa_record_step(AoEnv* env, int i, hipStream_t st) {
 // first, as aoenv_download(AOENV_B_OPD_ATM) does
 template <typename T>
 int oa_residual_now(AoEnv* env, const char* who, void* phase_sci, void* opd_atm_sci, void* rms_nm, void* strehl, hipStream_t st) {
-    if (!env->oa.set) return fail("%s: no science direction is set (aoenv_set_science_direction)", who);
+    if (!env->sci_differs()) return fail("%s: no science direction is set (aoenv_set_science_direction) and no static map makes the science arm differ (aoenv_set_static_opd)", who);
+    if (!env->oa.set) {                                            // a static difference map alone: AOENV_B_PHASE as it stands
+        if (opd_atm_sci) return fail("%s: no science direction is set (aoenv_set_science_direction): there is no atmosphere toward a target", who);
+        return oa_residual<T>(env, phase_sci, nullptr, rms_nm, strehl, st);
+    }
     if (env->atm_user_defined)
         return fail("%s: the atmosphere OPD is user-defined (aoenv_set_atm_opd): there are no layers to look through until the atmosphere advances", who);
     if (env->L < 1) return fail("%s: the shard has no layers", who);
@@ -1320,8 +1419,9 @@ template <typename T>
 int sci_window(AoEnv* env, int flat, void* out, hipStream_t st) {
     const AoEnv::Science& sc = env->sci;
     SciArgs<T> a{};
-    // (under a science direction the camera looks at the target: the caller has formed phase_sci in the launch before this one)
-    a.phase = env->as<T>(env->oa.set && !flat ? env->oa.phase_sci : env->phase);
+    // (where the science arm differs from the sensor's the camera looks at phase_sci: the caller has formed it in the launch before
+    //  this one)
+    a.phase = env->as<T>(env->sci_differs() && !flat ? env->sci_phase() : env->phase);
     a.amp = env->as<T>(sc.amp);
     a.table = env->as<T>(sc.table);
     a.out = static_cast<T*>(out);
@@ -1342,7 +1442,7 @@ int sci_window(AoEnv* env, int flat, void* out, hipStream_t st) {
 template <typename T>
 int sci_accumulate_step(AoEnv* env, int i, hipStream_t st) {
     if (!env->sci.accumulates(i)) return 0;
-    if (env->oa.set) AO_TRY(oa_residual<T>(env, env->oa.phase_sci, nullptr, nullptr, nullptr, st));   // (the step stored what it reads)
+    if (env->sci_differs()) AO_TRY(oa_residual<T>(env, env->sci_phase(), nullptr, nullptr, nullptr, st));   // (the step stored what it reads)
     return sci_window<T>(env, 0, nullptr, st);
 }
 
@@ -1365,7 +1465,7 @@ int step_t(AoEnv* env, int i, const void* d_action, void* d_obs, void* d_frame, 
                                   hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE) || env->oa.reads_step(env->sci.accumulates(i))) ? 1 : 0, st));
+    AO_TRY(run_phase<T>(env, 1, (env->store_opd_atm || (env->wf.recorded() & AOENV_WF_ATMOSPHERE) || env->sci_reads_step(env->sci.accumulates(i))) ? 1 : 0, st));
     AO_TRY(wf_record_step<T>(env, i, st));                         // (the phase kernel has written what the sensor is about to see)
     AO_TRY(oa_record_step<T>(env, i, st));
     AO_TRY(sci_accumulate_step<T>(env, i, st));
@@ -2610,7 +2710,7 @@ int set_dm_env_t(AoEnv* env, const double* h_gx, const double* h_gy, hipStream_t
     AO_HIP(hipMemcpy(de.gxa, h.gxa.data(), h.gxa.size() * sizeof(float), hipMemcpyHostToDevice));
     AO_HIP(hipMemcpy(de.gya, h.gya.data(), h.gya.size() * sizeof(float), hipMemcpyHostToDevice));
     de.on = true;
-    return 0;
+    return env->stat.w ? refresh_dense_dm<T>(env, st) : 0;         // (a sensor-arm static map: mirror + map on the new tables)
 }
 }  // namespace
 }  // extern "C++"
@@ -2625,7 +2725,7 @@ int aoenv_set_dm_env(AoEnv* env, const double* h_gx, const double* h_gy, void* s
     if (!h_gx) {
         if (env->dm_env.mem) AO_HIP(hipStreamSynchronize(st));
         env->dm_env = AoEnv::DmEnv{};
-        return 0;
+        return env->stat.w ? AO_DISPATCH(env, refresh_dense_dm, env, st) : 0;   // (a sensor-arm static map: mirror + map on the shared tables)
     }
     const size_t n = (size_t)env->E * env->R * env->nAct;
     const size_t ix = first_not_finite(h_gx, n), iy = first_not_finite(h_gy, n);   // (the lower index is reported, gx first)
@@ -2697,7 +2797,7 @@ int aoenv_set_dm_pairs(AoEnv* env, const double* h_py, const double* h_px, void*
     if (!h_py) {
         if (env->dm_pairs.mem) AO_HIP(hipStreamSynchronize(st));
         env->dm_pairs = AoEnv::DmPairs{};
-        return 0;
+        return env->stat.w ? AO_DISPATCH(env, refresh_dense_dm, env, st) : 0;   // (a sensor-arm static map: mirror + map of the separable mirror)
     }
     if (!env->c.dm_separable) return fail("aoenv_set_dm_pairs: this shard's DM is dense (dm_separable == 0): upload its modes instead");
     if (env->dm_env.on)
@@ -2720,13 +2820,13 @@ int aoenv_get_dm_pairs(AoEnv* env, double* h_py, double* h_px, void* stream) {
 int aoenv_get_dm_surface(AoEnv* env, double* h_surface, void* stream) {
     AO_CHECK_ENV(env);
     if (!h_surface) return fail("aoenv_get_dm_surface: null destination");
-    if (!env->dm_surface_ahead())
+    if (!env->mirror_ahead())                                      // (a static map's buffer holds mirror + map: not the mirror's surface)
         return fail("aoenv_get_dm_surface: this shard forms its mirror surface inside the phase kernel and has no surface buffer "
                     "(a dense DM or aoenv_set_dm_pairs has one)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     AO_TRY(AO_DISPATCH(env, refresh_dense_dm, env, st));            // (outside a step: the pure command)
     AO_HIP(hipStreamSynchronize(st));
-    return download_real(env, h_surface, env->surface(), (size_t)env->E * env->R * env->R);
+    return download_real(env, h_surface, env->mirror_surface(), (size_t)env->E * env->R * env->R);
 }
 
 // ---- per-env guide stars (star_env.hpp) ------------------------------------------------------------------------------------------
@@ -2944,10 +3044,10 @@ int aoenv_project_wavefront(AoEnv* env, int what, void* d_out, void* stream) {
     if (!d_out) return fail("aoenv_project_wavefront: null output");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (what == AOENV_WF_SCIENCE) {                                // the residual toward the target, formed now
-        if (!env->oa.set)
-            return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE (AOENV_WF_SCIENCE: no science direction is set, aoenv_set_science_direction)", what);
+        if (!env->sci_differs())
+            return fail("aoenv_project_wavefront: what = %d is not exactly one of AOENV_WF_RESIDUAL, AOENV_WF_ATMOSPHERE (AOENV_WF_SCIENCE: no science direction is set, aoenv_set_science_direction, and no static map makes the science arm differ, aoenv_set_static_opd)", what);
         AO_TRY(require_step_constants(env, false));
-        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_project_wavefront", env->oa.phase_sci, nullptr, nullptr, nullptr, st));
+        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_project_wavefront", env->sci_phase(), nullptr, nullptr, nullptr, st));
     }
     if (what == AOENV_WF_ATMOSPHERE && env->L > 0 && !env->atm_user_defined && !env->store_opd_atm) {
         // not written by the step kernels unless asked to: re-derived from the screens now, as aoenv_download(AOENV_B_OPD_ATM) does
@@ -3040,9 +3140,9 @@ int aoenv_science_psf(AoEnv* env, int flat, void* d_out, void* stream) {
     if (!env->sci.set) return fail("aoenv_science_psf: no science camera is set (aoenv_set_science)");
     if (!d_out) return fail("aoenv_science_psf: null output");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (env->oa.set && !flat) {                                    // the camera looks at the target
+    if (env->sci_differs() && !flat) {                             // the camera looks at the target, through its own arm
         AO_TRY(require_step_constants(env, false));
-        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_science_psf", env->oa.phase_sci, nullptr, nullptr, nullptr, st));
+        AO_TRY(AO_DISPATCH(env, oa_residual_now, env, "aoenv_science_psf", env->sci_phase(), nullptr, nullptr, nullptr, st));
     }
     return AO_DISPATCH(env, sci_window, env, flat, d_out, st);
 }
@@ -3152,7 +3252,7 @@ int aoenv_get_science_direction(AoEnv* env, double* h_zenith_arcsec, double* h_a
 
 int aoenv_science_residual(AoEnv* env, void* d_phase_sci, void* d_opd_atm_sci, void* d_rms_nm, void* d_strehl, void* stream) {
     AO_CHECK_ENV(env);
-    if (!env->oa.set) return fail("aoenv_science_residual: no science direction is set (aoenv_set_science_direction)");
+    if (!env->sci_differs()) return fail("aoenv_science_residual: no science direction is set (aoenv_set_science_direction) and no static map makes the science arm differ (aoenv_set_static_opd)");
     AO_TRY(require_step_constants(env, false));
     return AO_DISPATCH(env, oa_residual_now, env, "aoenv_science_residual", d_phase_sci, d_opd_atm_sci, d_rms_nm, d_strehl, static_cast<hipStream_t>(stream));
 }
@@ -3165,7 +3265,7 @@ int aoenv_set_science_direction_record(AoEnv* env, void* d_rec, int i_base, int 
         oa.i_base = oa.n_slots = 0;
         return 0;
     }
-    if (!oa.set) return fail("aoenv_set_science_direction_record: no science direction is set (aoenv_set_science_direction)");
+    if (!env->sci_differs()) return fail("aoenv_set_science_direction_record: no science direction is set (aoenv_set_science_direction) and no static map makes the science arm differ (aoenv_set_static_opd)");
     if (i_base < 0 || n_slots < 1) return fail("aoenv_set_science_direction_record: window [%d, %d + %d) is empty or negative", i_base, i_base, n_slots);
     oa.rec = d_rec;
     oa.i_base = i_base;
@@ -3203,6 +3303,111 @@ int aoenv_get_guide_direction(AoEnv* env, double* h_zenith_arcsec, double* h_azi
     if (!env->guide.set) return fail("aoenv_get_guide_direction: no guide direction is set (aoenv_set_guide_direction)");
     std::copy(env->guide.zenith.begin(), env->guide.zenith.end(), h_zenith_arcsec);
     std::copy(env->guide.azimuth.begin(), env->guide.azimuth.end(), h_azimuth_deg);
+    return 0;
+}
+
+// ---- static aberrations (static_opd.hpp) -------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// one arm, or the difference of the two, in the env dtype: h_a - h_b element by element in float64 (a null array is zeros), rounded
+// once.  Returns the index of the first value that is not finite in the env dtype, n if there is none; *nonzero: any value != 0
+template <typename T>
+size_t static_round(const double* h_a, const double* h_b, size_t n, std::vector<T>& out, bool* nonzero) {
+    out.resize(n);
+    *nonzero = false;
+    for (size_t i = 0; i < n; ++i) {
+        const double d = (h_a ? h_a[i] : 0.0) - (h_b ? h_b[i] : 0.0);
+        out[i] = (T)d;
+        if (!std::isfinite((double)out[i])) return i;
+        if (out[i] != (T)0) *nonzero = true;
+    }
+    return n;
+}
+template <typename T>
+int set_static_t(AoEnv* env, const double* h_wfs, const double* h_sci, int per_env, hipStream_t st) {
+    const size_t E = (size_t)env->E, R2 = (size_t)env->R * env->R, nm = (per_env ? E : 1) * R2;
+    std::vector<T> tw, td;
+    bool nz_w = false, nz_d = false;
+    if (h_wfs)
+        if (const size_t i = static_round<T>(h_wfs, nullptr, nm, tw, &nz_w); i < nm)
+            return fail("aoenv_set_static_opd: wfs[%zu] = %g is not finite in the env dtype", i, h_wfs[i]);
+    if (const size_t i = static_round<T>(h_sci, h_wfs, nm, td, &nz_d); i < nm)
+        return fail("aoenv_set_static_opd: science[%zu] - wfs[%zu] is not finite in the env dtype", i, i);
+    // (the sensor arm's map is held as given, zeros included: the shard then runs the path of a shard with a map; a difference that
+    //  is zero everywhere is not held: the science arm IS the sensor's)
+    const bool have_w = h_wfs != nullptr, have_d = nz_d, sep = env->c.dm_separable != 0;
+    if (have_w) AO_TRY(require_step_constants(env, false));        // (the surface is formed before this call returns)
+    const size_t z = sizeof(T), surf = E * R2 * z;
+    const size_t rows = have_w && sep && sizeof(T) == 4 && env->nAct <= 128 ? E * env->dm_layout().ga_elems() * sizeof(float) : 0;
+    const size_t cimg = have_w && sep ? E * env->nAct * env->nAct * z : 0;
+    const std::initializer_list<size_t> parts = {have_w ? nm * z : 0, have_d ? nm * z : 0, have_w ? surf : 0, rows, cimg, have_d ? surf : 0};
+    AO_HIP(hipStreamSynchronize(st));                              // a launch in flight reads the maps in place
+    Block mem;                                                     // (built whole before the maps in use are given up; zeroed: the
+    if (mem.alloc(parts, true))                                    //  padding of Gy C stays zero from here on)
+        return fail("aoenv_set_static_opd: no device memory for %zu bytes of maps, surface and scratch", dev_layout(parts).total);
+    if ((have_w && mem.upload(0, tw.data(), nm * z)) || (have_d && mem.upload(1, td.data(), nm * z)))
+        return fail("aoenv_set_static_opd: the copy of the maps failed");
+    AoEnv::Static& sa = env->stat;
+    sa = AoEnv::Static{};
+    sa.mem = std::move(mem);
+    sa.on = true;
+    sa.w = sa.mem.part(0);
+    sa.delta = sa.mem.part(1);
+    sa.map_env = per_env ? R2 : 0;
+    sa.surf = sa.mem.part(2);
+    sa.rows = static_cast<float*>(sa.mem.part(3));
+    sa.cimg = sa.mem.part(4);
+    sa.phase_sci = sa.mem.part(5);
+    if (h_wfs) sa.h_w.assign(h_wfs, h_wfs + nm);
+    if (h_sci) sa.h_s.assign(h_sci, h_sci + nm);
+    if (!env->sci_differs()) {                                     // (no science arm of its own any more: its record goes with it)
+        env->oa.rec = nullptr;
+        env->oa.i_base = env->oa.n_slots = 0;
+    }
+    return refresh_dense_dm<T>(env, st);                           // the surface of the command held, with the map
+}
+}  // namespace
+}  // extern "C++"
+
+int aoenv_set_static_opd(AoEnv* env, const double* h_wfs, const double* h_sci, int per_env, void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_wfs && !h_sci) {                                        // no maps: the shard launches what it launched before
+        if (env->stat.on) AO_HIP(hipStreamSynchronize(st));
+        env->stat = AoEnv::Static{};
+        if (!env->sci_differs()) {
+            env->oa.rec = nullptr;
+            env->oa.i_base = env->oa.n_slots = 0;
+        }
+        return 0;
+    }
+    if (per_env != 0 && per_env != env->E)
+        return fail("aoenv_set_static_opd: per_env = %d maps, the shard has %d envs (0: one map for the shard)", per_env, env->E);
+    const size_t nm = (size_t)(per_env ? env->E : 1) * env->R * env->R;
+    const struct { const double* p; const char* name; } arms[] = {{h_wfs, "wfs"}, {h_sci, "science"}};
+    for (const auto& a : arms)
+        if (a.p)
+            if (const size_t i = first_not_finite(a.p, nm); i < nm) return fail("aoenv_set_static_opd: %s[%zu] is not finite", a.name, i);
+    return AO_DISPATCH(env, set_static_t, env, h_wfs, h_sci, per_env, st);
+}
+
+int aoenv_static_surface_path(AoEnv* env, int64_t* h_launches) {
+    if (!env) return -1;
+    if (h_launches) std::copy(env->static_launches, env->static_launches + 4, h_launches);
+    return env->static_path();
+}
+
+int aoenv_get_static_opd(AoEnv* env, double* h_wfs, double* h_sci) {
+    AO_CHECK_ENV(env);
+    const AoEnv::Static& sa = env->stat;
+    if (!sa.on) return fail("aoenv_get_static_opd: no static map is set (aoenv_set_static_opd)");
+    const size_t R2 = (size_t)env->R * env->R;
+    const struct { double* dst; const std::vector<double>& src; } arms[] = {{h_wfs, sa.h_w}, {h_sci, sa.h_s}};
+    for (const auto& a : arms) {
+        if (!a.dst) continue;
+        for (size_t e = 0; e < (size_t)env->E; ++e)
+            for (size_t q = 0; q < R2; ++q) a.dst[e * R2 + q] = a.src.empty() ? 0.0 : a.src[(sa.map_env ? e * R2 : 0) + q];
+    }
     return 0;
 }
 
@@ -3837,7 +4042,7 @@ int aoenv_set_option(AoEnv* env, int option, int value) {
             return 0;
         case AOENV_OPT_FORCE_PATH:
             if (value & ~(AOENV_PATH_PHASE_DWORD | AOENV_PATH_GENERIC | AOENV_PATH_PYR_ROUND_ROBIN | AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN |
-                          AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL))
+                          AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL | AOENV_PATH_DM_STATIC_GENERAL))
                 return fail("AOENV_OPT_FORCE_PATH: %d is not a combination of AOENV_PATH_* bits", value);
             env->force_path = value;
             return 0;

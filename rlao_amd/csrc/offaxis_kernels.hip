@@ -3,6 +3,7 @@
 // surface is the one the sensor saw, taken over from the step's own outputs:
 //     opd_atm_sci = sum_l blend_l(clip(warp(screen_l))[footprint_l(env)]) sqrt(fractionalR0_l) * lambda_atm / 2 pi
 //     phase_sci   = phase + (opd_atm_sci - opd_atm) * 2 pi / lambda_src   inside the pupil, 0 outside
+//                   (with a static difference map D = S_s - S_w, aoenv_set_static_opd: ((opd_atm_sci - opd_atm) + D) * 2 pi / lambda_src)
 //     rms_nm      = std(phase_sci[pupil]) * lambda_src / 2 pi * 1e9,   strehl = exp(-var(phase_sci[pupil]))
 // with `phase` = AOENV_B_PHASE and `opd_atm` the on-axis atmosphere OPD of the same step: the mirror product is not repeated and
 // every kind of mirror is served.
@@ -142,7 +143,12 @@ __global__ void __launch_bounds__(1024) k_science_residual(const OaArgs<T> a) {
                         const T atm_sci = sup[i] * a.atm_scale;
                         if (a.opd_atm_sci) a.opd_atm_sci[pix0 + q] = atm_sci;
                         const bool in = a.pupil[q] != 0;
-                        const T phi = in ? a.phase[pix0 + q] + (atm_sci - a.opd_atm[pix0 + q]) * a.src_scale : (T)0;
+                        T phi = (T)0;
+                        if (in) {                             // (a static difference map is one more term of the bracket)
+                            T d = atm_sci - a.opd_atm[pix0 + q];
+                            if (a.delta) d += a.delta[(size_t)e * a.delta_env + q];
+                            phi = a.phase[pix0 + q] + d * a.src_scale;
+                        }
                         if (a.phase_sci) a.phase_sci[pix0 + q] = phi;
                         if (in) {
                             const double d = (double)phi;

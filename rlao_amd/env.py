@@ -619,6 +619,29 @@ class Shard:
         L.call(self, "aoenv_get_dm_pairs", py, px, stream)
         return py, px
 
+    # static aberration maps (aoenv_set_static_opd): wfs, science [n_env][R][R] float64 metres (per_env) or [R][R], one map for the
+    # shard; a None arm is a zero arm, both None clear the feature
+    def set_static_opd(self, wfs, science, per_env: bool, stream=0):
+        tail = (self.cfg.resolution, self.cfg.resolution)
+        arms = []
+        for a in (wfs, science):
+            a = _f64(a)
+            if a is not None and a.shape != ((self.cfg.n_env,) + tail if per_env else tail):
+                raise ValueError(f"static maps must have shape {(self.cfg.n_env,) + tail if per_env else tail}")
+            arms.append(a)
+        L.call(self, "aoenv_set_static_opd", arms[0], arms[1], self.cfg.n_env if per_env else 0, stream)
+
+    def static_surface_path(self, launches=None) -> int:
+        """aoenv_static_surface_path: 0 no sensor-arm map, 1 k_dm_static_mfma, 2 k_dm_static<T>, 3 the trailing add; ``launches``:
+        an int64 [4] array that receives how often each has refreshed a surface."""
+        return int(L.invoke(self, "aoenv_static_surface_path", launches))
+
+    def get_static_opd(self):
+        shape = (self.cfg.n_env, self.cfg.resolution, self.cfg.resolution)
+        wfs, science = np.zeros(shape), np.zeros(shape)
+        L.call(self, "aoenv_get_static_opd", wfs, science)
+        return wfs, science
+
     # dm.OPD [n_env][R*R] of the command held (dense-DM shards and shards with actuator pairs)
     def get_dm_surface(self, stream=0):
         out = np.zeros((self.cfg.n_env, self.cfg.resolution * self.cfg.resolution))
@@ -1099,6 +1122,7 @@ class BatchedAOEnv:
         self._oa = None                                            # [n_envs, 2] (zenith arcsec, azimuth deg) while a science direction is set
         self._oa_rec = None                                        # the tensor of an attached science-direction record (kept alive here)
         self._guide = None                                         # [n_envs, 2] while a guide direction is set
+        self._static = False                                       # True while static aberration maps are set
         self._dm_misreg = None                                     # resolve_dm_misregistration()'s dict while the per-env mirrors are mis-registrations
         self._mag_env = self._thr_env = None                       # [n_envs] magnitudes / thresholds once per-env stars are set
         self.source = self.ngs = None
@@ -1225,6 +1249,7 @@ class BatchedAOEnv:
         self._sci = self._le = None                                  # ... and no science camera (it holds the pupil's amplitude)
         self._oa = self._oa_rec = None                               # ... and no science direction
         self._guide = None                                           # ... and no guide direction
+        self._static = False                                         # ... and no static aberration maps
         self._surface = "zonal"
         sh = self._shard
         if p.nLayer > 0 and hasattr(sh.lib, "aoenv_set_field"):     # what a science direction is computed from (absent: an A/B library of AOENV_LIB)
@@ -2033,8 +2058,10 @@ class BatchedAOEnv:
 
     def science_residual(self):
         """``(phase, rms_nm, strehl)`` toward the science target of the buffers as they stand: the residual phase ``[n_envs, R, R]``
-        [rad at the source wavelength], ``std(OPD[pupil]) * 1e9`` and ``exp(-var(phase[pupil]))`` per env.  New tensors every call."""
-        self._require_science_direction()
+        [rad at the source wavelength], ``std(OPD[pupil]) * 1e9`` and ``exp(-var(phase[pupil]))`` per env.  New tensors every call.
+        Also without a direction while static maps make the science arm differ from the sensor's (``set_static_aberration``)."""
+        if not getattr(self, "_static", False):                    # (with maps the library knows whether the arms differ)
+            self._require_science_direction()
         torch = _torch()
         phase = torch.empty((self.n_envs, self.R, self.R), device=self.device, dtype=self.tdtype)
         rms = torch.empty((self.n_envs,), device=self.device, dtype=self.tdtype)
@@ -2054,7 +2081,8 @@ class BatchedAOEnv:
         every stepped frame ``i0 <= i < i0 + n_steps`` of every loop fills: slot ``i - i0`` is what ``science_residual()`` gives
         after that step.  The loops' results do not change by a bit.  A call whose frames leave the window is refused;
         ``stop_science_direction_record()`` detaches."""
-        self._require_science_direction()
+        if not getattr(self, "_static", False):
+            self._require_science_direction()
         if int(n_steps) < 1 or int(i0) < 0:
             raise ValueError("record_science_direction: i0 >= 0 and n_steps >= 1")
         rec = _torch().zeros((int(n_steps), 2, self.n_envs), device=self.device, dtype=self.tdtype)
@@ -2102,6 +2130,63 @@ class BatchedAOEnv:
         zen, az = np.zeros(self.n_envs), np.zeros(self.n_envs)
         L.call(self._shard, "aoenv_get_guide_direction", zen, az)
         return np.stack([zen, az], axis=1)
+
+    # -- static aberrations (aoenv_set_static_opd; the reference's OPD_map / NCPA objects, `ngs*tel*map*dm*wfs`) -----------------------
+    def set_static_aberration(self, wfs=None, science=None, env_ids=None):
+        """A static optical-path map per env and per arm, in metres, unmasked: ``wfs`` is what the wavefront sensor sees,
+        ``science`` what the science camera sees; each ``[R, R]`` (every env, or every listed env, the same) or one map per
+        (listed) env, ``[n, R, R]``.  The same map in both arms is a common-path aberration; ``wfs=N`` alone is the classic NCPA: the
+        loop drives the sensor's residual to zero and prints ``-N`` into the science image (``ncpa_map`` makes such maps).  Without
+        ``env_ids`` the call states both arms of every env, an arm left out being zero; with them the listed envs are assigned,
+        the other envs keep what they hold (zeros if nothing is held) and an arm left out stays as held for every env.
+        Sensor arm: ``OPD_no_pupil = atm + wfs + dm``, ``OPD`` that times the pupil -- observation, reward, Strehl, residual rms,
+        the phase buffer and a geometric sensor's unmasked phase include the map, the atmosphere's own numbers (``total``
+        telemetry, ``project_wavefront("atmosphere")``) do not.  The shard runs the batched kernels while a sensor-arm map is set
+        (``fused_step`` is False).  Science arm: ``science_residual()``, ``science_psf()``, ``project_wavefront("science")``, the
+        long exposure and the science-direction record look at ``phase + ((opd_atm_sci - opd_atm) + (science - wfs)) 2 pi /
+        lambda`` inside the pupil, the first bracket only under a science direction.  Set the maps after ``set_params``: the
+        calibration never sees them, a sensor-arm map is an offset in the slopes.  Bad arguments raise before anything is
+        touched.  Not part of ``get_state``; ``reset_envs`` and new screens leave the maps alone."""
+        if wfs is None and science is None:
+            raise ValueError("set_static_aberration: give wfs and / or science (clear_static_aberration() removes the maps)")
+        tail = (self.R, self.R)
+        shared = env_ids is None and all(a is None or np.ndim(_host(a)) == 2 for a in (wfs, science))
+        if shared:
+            arms = [None if a is None else assign_per_env(a, None, 1, None, name, tail, scalar=False, row=True)[0]
+                    for a, name in ((wfs, "wfs"), (science, "science"))]
+        else:
+            held = self._shard.get_static_opd() if self._static and env_ids is not None else (None, None)
+            # (a sensor arm the library holds stays held, zeros included: such a shard keeps its path; a science arm of zeros and
+            #  an absent one are the same thing to the library)
+            keep = (held[0] is not None and self._shard.static_surface_path() != 0, held[1] is not None and bool(held[1].any()))
+            arms = []
+            for a, cur, kept, name in ((wfs, held[0], keep[0], "wfs"), (science, held[1], keep[1], "science")):
+                if a is None:                                      # (without env_ids: a zero arm; with them: as held, and an arm
+                    arms.append(cur if kept else None)             # that is not held stays absent)
+                else:
+                    arms.append(assign_per_env(a, env_ids, self.n_envs, cur, name, tail, scalar=False, row=True))
+        self._shard.set_static_opd(arms[0], arms[1], not shared, self._stream())
+        self._static = True
+
+    def ncpa_map(self, f2=None, coefficients=None, seed=5, basis="zernike"):
+        """``calib.ncpa_map`` on this env's pupil and diameter: the reference's ``NCPA(tel, dm, atm, modal_basis='Zernike', f2=... |
+        coefficients=..., seed=...).OPD``, ``[R, R]`` metres, for ``set_static_aberration``."""
+        return calib.ncpa_map(self.pupil, float(self.param.diameter), f2=f2, coefficients=coefficients, seed=seed, basis=basis)
+
+    def clear_static_aberration(self):
+        """No static maps: both arms are those of a shard that never had any, on the path the shard had; the device memory is
+        gone, nothing is left behind."""
+        L.call(self._shard, "aoenv_set_static_opd", None, None, 0, self._stream())
+        self._static = False
+
+    @property
+    def static_aberration(self):
+        """``dict(wfs=[n_envs, R, R], science=[n_envs, R, R])`` (float64 metres, as given; an arm left out as zeros), None while no
+        map is set."""
+        if not self._static:
+            return None
+        wfs, science = self._shard.get_static_opd()
+        return dict(wfs=wfs, science=science)
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

@@ -182,6 +182,19 @@ class TorchWrapper:
     def guide_direction(self):
         return self._env.guide_direction
 
+    def set_static_aberration(self, wfs=None, science=None, env_ids=None):
+        return self._env.set_static_aberration(wfs, science, env_ids)
+
+    def clear_static_aberration(self):
+        return self._env.clear_static_aberration()
+
+    def ncpa_map(self, f2=None, coefficients=None, seed=5, basis="zernike"):
+        return self._env.ncpa_map(f2, coefficients, seed, basis)
+
+    @property
+    def static_aberration(self):
+        return self._env.static_aberration
+
     @property
     def src(self):
         return self._env.src
@@ -370,6 +383,19 @@ class TimeDelayEnv:
     def guide_direction(self):
         return self._env.guide_direction
 
+    def set_static_aberration(self, wfs=None, science=None, env_ids=None):
+        return self._env.set_static_aberration(wfs, science, env_ids)
+
+    def clear_static_aberration(self):
+        return self._env.clear_static_aberration()
+
+    def ncpa_map(self, f2=None, coefficients=None, seed=5, basis="zernike"):
+        return self._env.ncpa_map(f2, coefficients, seed, basis)
+
+    @property
+    def static_aberration(self):
+        return self._env.static_aberration
+
     @property
     def src(self):
         return self._env.src
@@ -528,6 +554,19 @@ class HistoryEnv:
     @property
     def guide_direction(self):
         return self._env.guide_direction
+
+    def set_static_aberration(self, wfs=None, science=None, env_ids=None):
+        return self._env.set_static_aberration(wfs, science, env_ids)
+
+    def clear_static_aberration(self):
+        return self._env.clear_static_aberration()
+
+    def ncpa_map(self, f2=None, coefficients=None, seed=5, basis="zernike"):
+        return self._env.ncpa_map(f2, coefficients, seed, basis)
+
+    @property
+    def static_aberration(self):
+        return self._env.static_aberration
 
     @property
     def src(self):
