@@ -795,6 +795,36 @@ int aoenv_get_static_opd(AoEnv* env, double* h_wfs, double* h_sci);
  * how often each of these has refreshed a surface since the shard was created (index 0 is never counted). */
 int aoenv_static_surface_path(AoEnv* env, int64_t* h_launches);
 
+/* Replaces: the spot elongation of a laser guide star in the diffractive Shack-Hartmann (OOPAO/ShackHartmann.py:189-192, 239-240,
+ * 396-503, 554-556: behind a Source with a sodium profile and an up-link FWHM the sensor convolves every valid lenslet's unbinned
+ * n x n spot intensity, n = 2 p, with a kernel of that lenslet's own, I = fftshift(abs(ifft2(fft2(I) * C))), before the 2 x 2
+ * binning, the camera and the centroid) -- for the envs of ONE shard, one table per env or one for the shard.
+ * h_taps is float64 [per_env ? n_env : 1][n_valid_subap][n*n]: the kernels K = real(ifft2(C)) with the shift and the binning folded in,
+ *     Kb[x][y]     = K[x][y] + K[x+1][y] + K[x][y+1] + K[x+1][y+1]                                  (indices mod n)
+ *     camera[P][Q] = sum_{s,t} I[s][t] Kb[(2 P + n/2 - s) mod n][(2 Q + n/2 - t) mod n]              (I = |FFT2(E) / n|^2, unbinned)
+ * (rlao_amd/calib.py: lgs_spot_kernels restates get_convolution_spot, lgs_binned_taps forms Kb and the box).  `bytes` is the size
+ * of h_taps; per_env is n_env for a table per env or 0 for ONE table (one copy is held and read with a per-env stride of 0, as the
+ * per-env mirror tables are).  box = {x0, y0, nx, ny}: every non-zero tap of every lenslet of the table lies in rows x0 .. x0 + nx - 1
+ * and columns y0 .. y0 + ny - 1 (mod n) of its n x n array; the kernel's tap loop runs over the box alone ({0, 0, n, n}: all taps).
+ * While a table is set the spots come from k_sh_spots_lgs<T> (sh_lgs_kernels.hip; timed under AOENV_K_SH_SPOTS): k_sh_spots'
+ * transform with the unbinned intensity kept in LDS, then the tap sum in ascending tap order, whatever the box -- a zero tap adds
+ * exactly nothing, so an env has the same bits under any box that holds its taps, beside any other envs' tables and at any place in
+ * the shard.  Everything behind the frame (camera and noise streams, centroid, thresholds, every loop) is what it was; the guide
+ * star's flux per env applies.  The shard leaves the fused step kernel (aoenv_fused_step_active reports 0; the batched kernels
+ * run) and returns to it, bit-identical to an untouched shard, when the table is forgotten: h_taps = NULL (bytes, per_env and box are
+ * then ignored).  Calibration shards are handed the table like any other (the reference calibrates behind the LGS source).
+ * Configuration like the mirror tables: copied before the call returns (the stream is waited for once), rounded once to the env
+ * dtype, in no checkpoint buffer, untouched by aoenv_reset_envs and aoenv_new_screens*.  No buffer id, no profiled kernel and no ABI
+ * version go with it.  Device memory (ONE block): the table in the env dtype.
+ * Refused, with nothing changed and nothing launched: a Pyramid or geometric shard; a per_env that is neither 0 nor n_env; a byte count
+ * that is not the table's; a box outside [0, n) (x0, y0 in [0, n), nx, ny in [1, n]); a tap that is negative, not
+ * finite (also once rounded to the env dtype) or non-zero outside the box; a lenslet whose taps sum to zero; a lenslet size whose
+ * LDS image does not fit; an allocation that fails.
+ * aoenv_get_lgs_spots returns the table as given (h_taps sized as it was set), *per_env (n_env or 0) and the box; any may be NULL;
+ * refused while no table is set. */
+int aoenv_set_lgs_spots(AoEnv* env, const double* h_taps, size_t bytes, int per_env, const int32_t box[4], void* stream);
+int aoenv_get_lgs_spots(AoEnv* env, double* h_taps, int32_t* per_env, int32_t box[4]);
+
 /* Replaces: the WFS camera settings wfs.cam.{photonNoise, readoutNoise, QE, darkCurrent, integrationTime, FWC, bits, gain,
  * sensor} (OOPAO/Detector.py:19-60; Papyrus: photonNoise = True, MAIN/OOPAOEnv/OOPAOEnv.py:379; Razor:
  * OOPAOEnvRazor.py:243-250, 333).  The frame of every measurement then goes through integrate() + readout()

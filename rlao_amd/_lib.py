@@ -151,6 +151,8 @@ EXPORTS = {
     "aoenv_set_static_opd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "aoenv_get_static_opd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_static_surface_path": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "aoenv_set_lgs_spots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "aoenv_get_lgs_spots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_detector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "aoenv_set_return_accumulator": (C.c_int, [C.c_void_p, C.c_void_p]),
     "aoenv_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -178,7 +180,7 @@ EXPORTS = {
 _LATER_ENTRIES = ("aoenv_step_counters", "aoenv_set_field", "aoenv_set_science_direction", "aoenv_get_science_direction",
                   "aoenv_science_residual", "aoenv_set_science_direction_record", "aoenv_test_step_lds", "aoenv_get_phase_no_pupil",
                   "aoenv_set_guide_direction", "aoenv_get_guide_direction", "aoenv_set_static_opd", "aoenv_get_static_opd",
-                  "aoenv_static_surface_path")
+                  "aoenv_static_surface_path", "aoenv_set_lgs_spots", "aoenv_get_lgs_spots")
 
 
 class AoEnvError(RuntimeError):

@@ -65,6 +65,9 @@ class AOParams:
     threshold_cog: float = 0.01          # OOPAO/ShackHartmann.py:42
     is_geometric: bool = False           # Shack-Hartmann: gradient slopes instead of spots (OOPAO/ShackHartmann.py:382-394, 676-695;
                                          # param['is_geometric'], OOPAO/calibration/initialization_AO_SHWFS.py:114-127)
+    lgs: dict = None                     # Shack-Hartmann behind a laser guide star: dict(Na_profile=[2, n_z], FWHM_spot_up=...,
+                                         # laser_coordinates=[x, y], threshold_convolution=0.05) -- OOPAO/Source.py:115-121,
+                                         # OOPAO/ShackHartmann.py:396-503 (lgs_spot_kernels below)
     nModes: int = 50                     # Zernike modes kept from the M2C (MAIN/OOPAOEnv/OOPAOEnv.py:260)
     nMeasurements: int = 6               # MAIN/OOPAOEnv/OOPAOEnv.py:285
     fov: float = 0.0
@@ -404,6 +407,113 @@ class SHTables:
         self.nValid = int(self.subap_idx.size)
         self.nSignal = 2 * self.nValid
         self.amp = np.sqrt(self.flux_map)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Laser guide star: the elongated spots of the diffractive Shack-Hartmann
+# ------------------------------------------------------------------------------------------------------
+def lgs_profile(Na_profile) -> np.ndarray:
+    """The sodium profile as float64 ``[2, n_z]`` (altitudes [m], densities), or ``ValueError``: OOPAO/Source.py:87."""
+    a = np.asarray(Na_profile, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != 2 or a.shape[1] < 1:
+        raise ValueError(f"Na_profile must have shape [2, n_z] (altitudes, densities), got {a.shape}")
+    if not np.isfinite(a).all() or (a[0] <= 0).any() or (a[1] < 0).any() or not (a[1] > 0).any():
+        raise ValueError("Na_profile needs finite positive altitudes and finite non-negative densities that are not all zero")
+    return a
+
+
+def lgs_altitude(Na_profile) -> float:
+    """The Na-weighted altitude a ``Source`` takes when it becomes an LGS (OOPAO/Source.py:120)."""
+    a = lgs_profile(Na_profile)
+    return float(np.sum(a[0, :] * a[1, :]))
+
+
+def lgs_spot_kernels(p: AOParams, sh_tables: "SHTables", Na_profile, FWHM_spot_up, laser_coordinates, threshold_convolution=0.05,
+                     shannon_sampling=True):
+    """``(K, elungation_factor)``: the convolution kernels ``K [n_valid][n][n]`` (float64, ``n = 2 p``) of a laser guide star's
+    elongated spots and the reference's ``elungation_factor`` [sic], ``get_convolution_spot`` (OOPAO/ShackHartmann.py:397-503)
+    restated line for line -- its mix of metres and arcseconds included: the golden pins it.  ``K[k] = real(ifft2(wfs.C[k]))``
+    for valid lenslet k: the reference stores ``C = fft2(I.T)``, so the kernel is the TRANSPOSED image of the sodium column,
+    truncated at ``threshold_convolution`` of its peak and normalised to sum 1.  ``shannon_sampling``: the sensor's flag, which
+    halves ``fov_pixel_arcsec`` (:181; True in every env here)."""
+    na = lgs_profile(Na_profile)
+    fwhm = float(FWHM_spot_up)
+    lc = np.asarray(laser_coordinates, dtype=np.float64).reshape(-1)
+    if lc.size != 2 or not np.isfinite(lc).all():
+        raise ValueError("laser_coordinates must be two finite numbers [x, y] in metres")
+    if not (np.isfinite(fwhm) and fwhm > 0):
+        raise ValueError("FWHM_spot_up must be a positive finite number")
+    thr = float(threshold_convolution)
+    if not 0 <= thr < 1:
+        raise ValueError("threshold_convolution must lie in [0, 1)")
+    D, ns, px, n = float(p.diameter), int(p.nSubaperture), sh_tables.p, sh_tables.n
+    wavelength = PHOTOMETRY[p.opticalBand][0]
+    X0, Y0 = lc[1], -lc[0]                                         # :400
+    x_subap = np.linspace(-D // 2, D // 2, ns)                     # :410-411 (floor division, as written)
+    y_subap = np.linspace(-D // 2, D // 2, ns)
+    d_pix = (D / ns) / n                                           # :417
+    v = np.linspace(-n * d_pix / 2, n * d_pix / 2, n)
+    alpha_x, alpha_y = np.meshgrid(v, v)
+    sigma_spot = fwhm / (2 * np.sqrt(np.log(2)))                   # :422
+    fov_lenslet_arcsec = (px * 206265 * wavelength / (D / ns)) / (1 + bool(shannon_sampling))      # :181 (binning, padding = 1)
+    fov_pixel_arcsec = fov_lenslet_arcsec / px
+    h, w = na[0, :], na[1, :]
+    nz = h.size
+    c3 = np.zeros((3, nz))
+    c3[0, :] = (D / 4) * (X0 / h)                                  # :450-451
+    c3[1, :] = (D / 4) * (Y0 / h)
+    c3[2, :] = D ** 2. / (8. * h) / (2. * np.sqrt(3.))
+    c3_ref = c3 - c3[:, [nz // 2]]                                 # :453
+    criterion = n * (D / ns) / n                                   # :433
+    K = np.zeros((sh_tables.nValid, n, n))
+    span_x, span_y = [], []
+    for slot, k in enumerate(sh_tables.subap_idx):
+        i_subap, j_subap = int(k) // ns, int(k) % ns
+        dx = c3_ref[0] * (4 / D) + c3_ref[2] * (np.sqrt(3) * (4 / D) ** 2) * x_subap[i_subap]      # :455-459
+        dy = c3_ref[1] * (4 / D) + c3_ref[2] * (np.sqrt(3) * (4 / D) ** 2) * y_subap[j_subap]
+        shift_X = 206265 * fov_pixel_arcsec * dx                   # :462-463
+        shift_Y = 206265 * fov_pixel_arcsec * dy
+        I = np.zeros((n, n))
+        for i in range(nz):                                        # :466-468, in the reference's order of summation
+            I += (w[i] / (h[i] ** 2)) * np.exp(-((alpha_x - shift_X[i]) ** 2 + (alpha_y - shift_Y[i]) ** 2) / (2 * sigma_spot ** 2))
+        I[I < thr * I.max()] = 0                                   # :471
+        I /= I.sum()                                               # :473
+        K[slot] = I.T                                              # :478: C = fft2(I.T)
+        span_x.append(shift_X.max() - shift_X.min())
+        span_y.append(shift_Y.max() - shift_Y.min())
+    elungation_factor = float(max(np.max(span_x), np.max(span_y)) / criterion)      # :484-492
+    return K, elungation_factor
+
+
+def _cyclic_span(used: np.ndarray):
+    """(start, length) of the smallest cyclic interval of range(len(used)) that holds every True of ``used``; (0, 1) if none."""
+    n = used.size
+    idx = np.flatnonzero(used)
+    if idx.size == 0:
+        return 0, 1
+    gaps = np.diff(np.concatenate([idx, [idx[0] + n]])) - 1         # zeros between consecutive used entries, cyclically
+    g = int(np.argmax(gaps))
+    start = int(idx[(g + 1) % idx.size])
+    return start, int(n - gaps[g])
+
+
+def lgs_binned_taps(K):
+    """``(Kb, box)`` for kernels ``K [..., n, n]``: the taps with the reference's ``fftshift`` and 2 x 2 binning folded in,
+
+        Kb[x][y] = K[x][y] + K[x+1][y] + K[x][y+1] + K[x+1][y+1]                                  (indices mod n)
+        camera[P][Q] = sum_{s,t} I[s][t] Kb[(2 P + n/2 - s) mod n][(2 Q + n/2 - t) mod n]          (I the unbinned |FFT2(E)/n|^2)
+
+    which is ``bin2x2(fftshift(ifft2(fft2(I) fft2(K))))`` (OOPAO/ShackHartmann.py:556, 565), and ``box = [x0, y0, nx, ny]``
+    (int32): the smallest cyclic box -- rows ``x0 .. x0 + nx - 1`` and columns ``y0 .. y0 + ny - 1`` mod n -- that holds every
+    non-zero tap of every kernel of the table; the whole ``n x n`` when the taps are dense."""
+    K = np.asarray(K, dtype=np.float64)
+    if K.ndim < 2 or K.shape[-1] != K.shape[-2] or K.shape[-1] % 2:
+        raise ValueError(f"lgs_binned_taps: kernels must be [..., n, n] with n even, got {K.shape}")
+    Kb = K + np.roll(K, -1, axis=-2) + np.roll(K, -1, axis=-1) + np.roll(np.roll(K, -1, axis=-2), -1, axis=-1)
+    nz = (Kb != 0).reshape(-1, K.shape[-2], K.shape[-1]).any(axis=0)
+    x0, nx = _cyclic_span(nz.any(axis=1))
+    y0, ny = _cyclic_span(nz.any(axis=0))
+    return Kb, np.array([x0, y0, nx, ny], dtype=np.int32)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -304,6 +304,11 @@ int launch_sh_spots(const T* phase, const ShConst<T>& sc, const T* amp_env, T* f
 template <typename T>
 int launch_sh_centroid(const T* frame, const T* wfs_max, const ShConst<T>& sc, const T* thr_env, T* signal, int n_env, int R,
                        int n_subap, int n_valid, int max_group, hipStream_t st);
+// laser-guide-star spots (sh_lgs.hpp, sh_lgs_kernels.hip): launch_sh_spots' operands, and every lenslet's taps [n_tab][n_valid][n*n]
+// (tap_env: elements between the envs' tables, 0 = one table for the shard) with their cyclic box {x0, y0, nx, ny} (host memory)
+template <typename T>
+int launch_sh_spots_lgs(const T* phase, const ShConst<T>& sc, const T* amp_env, const T* taps, size_t tap_env, const int32_t* box,
+                        T* frame, T* wfs_max, int n_env, int R, int n_subap, int n_valid, hipStream_t st);
 
 // Step epilogue (one workgroup per env): reconstruction image, reward, integrator, telemetry scalars.
 template <typename T>

@@ -19,6 +19,7 @@
 #include "policy.hpp"
 #include "sh_device.hpp"
 #include "sh_geometric.hpp"
+#include "sh_lgs.hpp"
 #include "science.hpp"
 #include "star_env.hpp"
 #include "static_opd.hpp"
@@ -272,6 +273,16 @@ struct AoEnv {
         std::vector<double> h_w, h_s;       // the arms as given ([n][R*R]; empty: a NULL arm), for aoenv_get_static_opd
         bool on = false;
     } stat;
+    // laser-guide-star spots (aoenv_set_lgs_spots, sh_lgs.hpp): every valid lenslet's binned taps in ONE block of its own (NULL frees
+    // it); configuration like the mirror tables.  While `on` the spots come from k_sh_spots_lgs and the shard runs the batched kernels
+    struct Lgs {
+        bool on = false;
+        Block mem;
+        void* taps = nullptr;               // [n][nVal][n_pix^2] env dtype, n = E or 1 (tap_env = 0)
+        size_t tap_env = 0;                 // elements between the envs' tables: nVal n_pix^2, or 0 for one table for the shard
+        int32_t box[4] = {0, 0, 0, 0};      // x0, y0, nx, ny: the cyclic box that holds every non-zero tap
+        std::vector<double> h_taps;         // the table as given, for aoenv_get_lgs_spots
+    } lgs;
     // the mirror's own surface is formed ahead of the phase kernel (actuator pairs, a dense mirror) in mirror_surface()
     bool mirror_ahead() const { return !c.dm_separable || dm_pairs.on; }
     void* mirror_surface() const { return dm_pairs.on ? dm_pairs.opd : dm_opd; }
@@ -824,6 +835,11 @@ template <typename T>
 int run_spots_and_camera(AoEnv* env, const ShConst<T>& sc, hipStream_t st) {
     {
         AO_PROF(env, SH_SPOTS, st);
+        if (env->lgs.on)                                           // elongated spots: every lenslet's own taps on the unbinned intensity
+            AO_TRY(launch_sh_spots_lgs<T>(env->as<T>(env->phase), sc, env->star_env<T>().amp, env->as<T>(env->lgs.taps), env->lgs.tap_env,
+                                          env->lgs.box, env->as<T>(env->frame), env->as<T>(env->wfs_max), env->E, env->R, env->nSub,
+                                          env->nVal, st));
+        else
         AO_TRY(launch_sh_spots<T>(env->as<T>(env->phase), sc, env->star_env<T>().amp, env->as<T>(env->frame), env->as<T>(env->wfs_max), env->E,
                                   env->R, env->nSub, env->nVal, st));
     }
@@ -1047,7 +1063,7 @@ template <typename T>
 bool fused_step_ok(const AoEnv*) { return false; }
 template <>
 bool fused_step_ok<float>(const AoEnv* env) {
-    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && !env->guide.set && env->n_modes > 0 &&
+    return env->use_fused_step && env->use_fast_wfs && env->use_mfma && env->use_fused_tail && env->c.wfs_type == AOENV_WFS_SH && !env->dm_surface_ahead() && !env->guide.set && !env->lgs.on && env->n_modes > 0 &&
            env->c.max_group == 1 && env->L > 0 && env->uniform && env->c.cam_res == env->R && (env->force_path & ~(AOENV_PATH_MODAL_GEMM | AOENV_PATH_SH_PLAIN | AOENV_PATH_WF_GENERAL | AOENV_PATH_SCI_GENERAL | AOENV_PATH_DM_PAIRS_GENERAL | AOENV_PATH_DM_STATIC_GENERAL)) == 0 &&
            step_fused_supported(env->R, env->nSub, env->nVal, env->nAct, env->n_modes) != 0;
 }
@@ -3408,6 +3424,78 @@ int aoenv_get_static_opd(AoEnv* env, double* h_wfs, double* h_sci) {
         for (size_t e = 0; e < (size_t)env->E; ++e)
             for (size_t q = 0; q < R2; ++q) a.dst[e * R2 + q] = a.src.empty() ? 0.0 : a.src[(sa.map_env ? e * R2 : 0) + q];
     }
+    return 0;
+}
+
+// ---- laser-guide-star spots (sh_lgs.hpp) -------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+template <typename T>
+int set_lgs_t(AoEnv* env, const double* h_taps, size_t count, int per_env, const int32_t box[4], hipStream_t st) {
+    std::vector<T> t(count);
+    for (size_t q = 0; q < count; ++q) t[q] = (T)h_taps[q];
+    AO_HIP(hipStreamSynchronize(st));                              // a launch in flight reads the table in place
+    Block mem;                                                     // (built whole before the table in use is given up)
+    if (mem.alloc({count * sizeof(T)}, false)) return fail("aoenv_set_lgs_spots: no device memory for %zu bytes of taps", count * sizeof(T));
+    if (mem.upload(0, t.data(), count * sizeof(T))) return fail("aoenv_set_lgs_spots: the copy of the taps failed");
+    AoEnv::Lgs& g = env->lgs;
+    g = AoEnv::Lgs{};
+    g.mem = std::move(mem);
+    g.on = true;
+    g.taps = g.mem.part(0);
+    g.tap_env = per_env ? count / (size_t)env->E : 0;
+    std::copy(box, box + 4, g.box);
+    g.h_taps.assign(h_taps, h_taps + count);
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int aoenv_set_lgs_spots(AoEnv* env, const double* h_taps, size_t bytes, int per_env, const int32_t box[4], void* stream) {
+    AO_CHECK_ENV(env);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h_taps) {                                                 // no table: the shard launches what it launched before
+        if (env->lgs.on) AO_HIP(hipStreamSynchronize(st));
+        env->lgs = AoEnv::Lgs{};
+        return 0;
+    }
+    if (env->c.wfs_type != AOENV_WFS_SH)
+        return fail("aoenv_set_lgs_spots: elongated spots belong to the diffractive Shack-Hartmann; this shard's sensor is %s",
+                    env->c.wfs_type == AOENV_WFS_PYRAMID ? "a Pyramid" : "the geometric Shack-Hartmann (no spots)");
+    if (!box) return fail("aoenv_set_lgs_spots: null box");
+    if (per_env != 0 && per_env != env->E)
+        return fail("aoenv_set_lgs_spots: per_env = %d tables, the shard has %d envs (0: one table for the shard)", per_env, env->E);
+    const int p = env->R / env->nSub, n = 2 * p;
+    if (lgs_lenslets_per_group(p, env->esz) == 0)
+        return fail("aoenv_set_lgs_spots: %d px per lenslet needs %zu B of LDS for one lenslet", p, lgs_lds_bytes(p, 1, env->esz));
+    const int n_tab = per_env ? env->E : 1;
+    const LgsCheck c = lgs_validate(h_taps, bytes, n_tab, env->nVal, n, box, env->esz == 4);
+    switch (c.verdict) {
+    case kLgsOk: break;
+    case kLgsBytes:
+        return fail("aoenv_set_lgs_spots: %zu bytes, expected %zu = [%d][%d][%d] float64 (per_env = %d, the shard has %d envs)", bytes,
+                    (size_t)n_tab * env->nVal * n * n * sizeof(double), n_tab, env->nVal, n * n, per_env, env->E);
+    case kLgsBox:
+        return fail("aoenv_set_lgs_spots: box {x0 %d, y0 %d, nx %d, ny %d} is not inside [0, %d)", box[0], box[1], box[2], box[3], n);
+    case kLgsNotFinite:
+        return fail("aoenv_set_lgs_spots: tap [%zu][%zu][%zu] is not finite in the env dtype", c.table, c.lenslet, c.tap);
+    case kLgsNegative:
+        return fail("aoenv_set_lgs_spots: tap [%zu][%zu][%zu] is negative", c.table, c.lenslet, c.tap);
+    case kLgsOutside:
+        return fail("aoenv_set_lgs_spots: tap [%zu][%zu][%zu] is not zero and lies outside the box", c.table, c.lenslet, c.tap);
+    case kLgsZeroSum:
+        return fail("aoenv_set_lgs_spots: the taps of lenslet [%zu][%zu] sum to zero in the env dtype", c.table, c.lenslet);
+    }
+    return AO_DISPATCH(env, set_lgs_t, env, h_taps, bytes / sizeof(double), per_env, box, st);
+}
+
+int aoenv_get_lgs_spots(AoEnv* env, double* h_taps, int32_t* per_env, int32_t box[4]) {
+    AO_CHECK_ENV(env);
+    const AoEnv::Lgs& g = env->lgs;
+    if (!g.on) return fail("aoenv_get_lgs_spots: no table is set (aoenv_set_lgs_spots)");
+    if (per_env) *per_env = g.tap_env ? env->E : 0;
+    if (box) std::copy(g.box, g.box + 4, box);
+    if (h_taps) std::copy(g.h_taps.begin(), g.h_taps.end(), h_taps);
     return 0;
 }
 

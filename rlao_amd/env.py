@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from collections import namedtuple
 from types import SimpleNamespace
 
@@ -441,6 +442,57 @@ def resolve_star_per_env(kind: str, value, env_ids, n_envs: int, current) -> np.
     return out
 
 
+LGS_KEYS = ("Na_profile", "FWHM_spot_up", "laser_coordinates", "threshold_convolution")
+
+
+def resolve_lgs(lgs) -> dict:
+    """The ``lgs=`` argument of ``set_params`` checked and in one form: ``dict(Na_profile [2, n_z], FWHM_spot_up, laser_coordinates
+    [2], threshold_convolution)``, float64.  ``ValueError`` for anything malformed; ``padding_extension_factor`` above 1 (the
+    reference's extended field of view, OOPAO/ShackHartmann.py:148-152) is not built and refused.  Pure host code."""
+    if not isinstance(lgs, dict):
+        raise ValueError("lgs must be a dict(Na_profile=[2, n_z], FWHM_spot_up=..., laser_coordinates=[x, y], threshold_convolution=0.05)")
+    if float(lgs.get("padding_extension_factor", 1)) > 1:
+        raise ValueError("lgs: padding_extension_factor above 1 is not built")
+    unknown = set(lgs) - set(LGS_KEYS) - {"padding_extension_factor"}
+    if unknown or "Na_profile" not in lgs or "FWHM_spot_up" not in lgs:
+        raise ValueError(f"lgs needs Na_profile and FWHM_spot_up and takes {LGS_KEYS}" + (f"; unknown: {sorted(unknown)}" if unknown else ""))
+    out = dict(Na_profile=calib.lgs_profile(_host(lgs["Na_profile"])),
+               FWHM_spot_up=as_float64(lgs["FWHM_spot_up"], "FWHM_spot_up"),
+               laser_coordinates=as_float64(lgs.get("laser_coordinates", [0.0, 0.0]), "laser_coordinates").reshape(-1),
+               threshold_convolution=float(lgs.get("threshold_convolution", 0.05)))
+    if out["FWHM_spot_up"].ndim != 0 or not np.isfinite(out["FWHM_spot_up"]) or out["FWHM_spot_up"] <= 0:
+        raise ValueError("lgs: FWHM_spot_up must be one positive finite number")
+    out["FWHM_spot_up"] = float(out["FWHM_spot_up"])
+    if out["laser_coordinates"].shape != (2,) or not np.isfinite(out["laser_coordinates"]).all():
+        raise ValueError("lgs: laser_coordinates must be two finite numbers [x, y] in metres")
+    if not 0 <= out["threshold_convolution"] < 1:
+        raise ValueError("lgs: threshold_convolution must lie in [0, 1)")
+    return out
+
+
+def resolve_lgs_per_env(Na_profile, FWHM_spot_up, laser_coordinates, env_ids, n_envs: int, current: dict) -> dict:
+    """The guide star of every env after a per-env assignment: ``dict(Na_profile [n_envs, 2, n_z], FWHM_spot_up [n_envs],
+    laser_coordinates [n_envs, 2])``.  Each argument is None (as held), one value for every written env (a profile ``[2, n_z]``, a
+    scalar FWHM, one launch ``[2]``) or one per written env.  ``current``: the same dict as held (the calibrated star broadcast
+    while nothing is set).  Pure host code."""
+    if Na_profile is None and FWHM_spot_up is None and laser_coordinates is None:
+        raise ValueError("set_lgs_per_env: give Na_profile, FWHM_spot_up and / or laser_coordinates (clear_lgs_per_env() returns to the calibrated star)")
+    out = {k: np.array(v, dtype=np.float64) for k, v in current.items()}
+    if Na_profile is not None:
+        out["Na_profile"] = assign_per_env(Na_profile, env_ids, n_envs, out["Na_profile"], "Na_profile", (2, out["Na_profile"].shape[2]),
+                                           scalar=False, row=True)
+        for prof in out["Na_profile"]:
+            calib.lgs_profile(prof)
+    if FWHM_spot_up is not None:
+        out["FWHM_spot_up"] = assign_per_env(FWHM_spot_up, env_ids, n_envs, out["FWHM_spot_up"], "FWHM_spot_up")
+        if (out["FWHM_spot_up"] <= 0).any():
+            raise ValueError("FWHM_spot_up must be above 0")
+    if laser_coordinates is not None:
+        out["laser_coordinates"] = assign_per_env(laser_coordinates, env_ids, n_envs, out["laser_coordinates"], "laser_coordinates", (2,),
+                                                  scalar=False, row=True)
+    return out
+
+
 def _f64(x):
     """Host memory an entry point reads as float64 (None, an argument left out, stays None)."""
     return None if x is None else np.ascontiguousarray(x, dtype=np.float64)
@@ -641,6 +693,27 @@ class Shard:
         wfs, science = np.zeros(shape), np.zeros(shape)
         L.call(self, "aoenv_get_static_opd", wfs, science)
         return wfs, science
+
+    # laser-guide-star spots (aoenv_set_lgs_spots): taps [n_env][n_valid][n][n] float64 (per_env) or [n_valid][n][n], one table for
+    # the shard, and their box [x0, y0, nx, ny]; taps None forgets the table
+    def set_lgs_spots(self, taps, box=None, per_env: bool = False, stream=0):
+        if taps is None:
+            L.call(self, "aoenv_set_lgs_spots", None, 0, 0, None, stream)
+            return
+        taps = np.ascontiguousarray(taps, dtype=np.float64)
+        box = np.ascontiguousarray(box, dtype=np.int32)
+        if box.shape != (4,):
+            raise ValueError("the box of an LGS tap table is [x0, y0, nx, ny]")
+        L.call(self, "aoenv_set_lgs_spots", taps, taps.nbytes, self.cfg.n_env if per_env else 0, box, stream)
+
+    def get_lgs_spots(self):
+        """(taps [n_env or 1][n_valid][n][n] as given, per_env, box [4])."""
+        per_env, box = np.zeros(1, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        L.call(self, "aoenv_get_lgs_spots", None, per_env, box)
+        n = 2 * (self.cfg.resolution // self.cfg.n_subap)
+        taps = np.zeros((self.cfg.n_env if per_env[0] else 1, self.cfg.n_valid_subap, n, n))
+        L.call(self, "aoenv_get_lgs_spots", taps, None, None)
+        return taps, bool(per_env[0]), box
 
     # dm.OPD [n_env][R*R] of the command held (dense-DM shards and shards with actuator pairs)
     def get_dm_surface(self, stream=0):
@@ -862,10 +935,45 @@ class _SourceProxy:
     ``set_magnitude_per_env``.  ``coordinates`` is ``[n_envs, 2]`` (zenith arcsec, azimuth deg; zeros while no direction is set);
     assigning one pair for every env or an ``[n_envs, 2]`` array is ``set_guide_direction``."""
     tag = "source"
-    type = "NGS"
 
     def __init__(self, env):
         object.__setattr__(self, "_e", env)
+
+    @property
+    def type(self):
+        """"LGS" on an env built with ``set_params(..., lgs=...)`` (OOPAO/Source.py:115-121), "NGS" otherwise."""
+        return "LGS" if self._e._lgs is not None else "NGS"
+
+    @property
+    def altitude(self):
+        """The Na-weighted altitude of an LGS (OOPAO/Source.py:120; ``[n_envs]`` once ``set_lgs_per_env`` is in force), inf for an NGS."""
+        e = self._e
+        if e._lgs is None:
+            return np.inf
+        if e._lgs_env is None:
+            return calib.lgs_altitude(e._lgs["Na_profile"])
+        return np.array([calib.lgs_altitude(prof) for prof in e._lgs_env["Na_profile"]])
+
+    @property
+    def Na_profile(self):
+        e = self._e
+        if e._lgs is None:
+            raise AttributeError("a natural guide star has no Na_profile (set_params(..., lgs=...))")
+        return (e._lgs if e._lgs_env is None else e._lgs_env)["Na_profile"].copy()
+
+    @property
+    def FWHM_spot_up(self):
+        e = self._e
+        if e._lgs is None:
+            raise AttributeError("a natural guide star has no FWHM_spot_up (set_params(..., lgs=...))")
+        return e._lgs["FWHM_spot_up"] if e._lgs_env is None else e._lgs_env["FWHM_spot_up"].copy()
+
+    @property
+    def laser_coordinates(self):
+        e = self._e
+        if e._lgs is None:
+            return np.zeros(2)
+        return (e._lgs if e._lgs_env is None else e._lgs_env)["laser_coordinates"].copy()
 
     @property
     def optBand(self):
@@ -972,6 +1080,29 @@ class _WfsProxy:
     def is_geometric(self, value):
         raise AttributeError("wfs.is_geometric cannot be assigned: the slope units, the interaction matrix and the reconstructor "
                              "depend on it -- build the env with set_params(..., is_geometric=...)")
+
+    @property
+    def is_LGS(self):
+        """True on an env built with ``set_params(..., lgs=...)``: the sensor convolves its spots (OOPAO/ShackHartmann.py:189-192)."""
+        return self._e._lgs is not None
+
+    @property
+    def elungation_factor(self):
+        """The reference's attribute, its spelling (OOPAO/ShackHartmann.py:492): the largest spot elongation over the lenslet's field,
+        of the calibrated star."""
+        if self._e._lgs is None:
+            raise AttributeError("wfs.elungation_factor belongs to an LGS sensor (set_params(..., lgs=...))")
+        return self._e._lgs_elongation
+
+    def lgs_kernels(self, per_env=False):
+        """The convolution kernels ``K = real(ifft2(wfs.C))``: ``[n_valid, n, n]`` of the calibrated star, or with ``per_env``
+        ``[n_envs, n_valid, n, n]`` as the loop shard applies them (``set_lgs_per_env``)."""
+        e = self._e
+        if e._lgs is None:
+            raise AttributeError("wfs.lgs_kernels belongs to an LGS sensor (set_params(..., lgs=...))")
+        if not per_env:
+            return e._lgs_K.copy()
+        return e._lgs_kernels_per_env(e._lgs_env) if e._lgs_env is not None else np.broadcast_to(e._lgs_K, (e.n_envs,) + e._lgs_K.shape).copy()
 
     @property
     def signal(self):
@@ -1104,6 +1235,7 @@ class BatchedAOEnv:
         self.atm = self.dm = self.tel = self.wfs = None
         self._shard = None
         self.is_geometric = False                                  # set_params(..., is_geometric=True): the gradient Shack-Hartmann
+        self._lgs = self._lgs_env = self._lgs_taps = None          # set_params(..., lgs=dict(...)): a laser guide star's elongated spots
         self._done = None
         self._wind_env = None                                      # (speed, direction) [n_envs, nLayer] once per-env winds are set
         self._per_env_clock = False
@@ -1180,6 +1312,15 @@ class BatchedAOEnv:
         of the unmasked phase summed per lenslet, over ``slopes_units``: no spots, no camera, no threshold, no reference slopes, no
         noise.  Units, interaction matrix and reconstructor are calibrated in that mode; the camera flavours are accepted and change
         nothing (``wfs.cam.frame`` is zeros); ``fused_step`` is False (a step is the phase kernel and one launch for the rest).
+        ``lgs=dict(Na_profile=[2, n_z], FWHM_spot_up=..., laser_coordinates=[x, y], threshold_convolution=0.05)`` (a keyword, or the
+        parameter-file key ``lgs``; diffractive Shack-Hartmann only): the sensor sits behind a laser guide star, the reference's
+        ``Source(..., Na_profile=..., FWHM_spot_up=..., laser_coordinates=...)`` of type "LGS", and convolves every lenslet's spot with
+        that lenslet's own image of the sodium column before binning, camera and centroid (OOPAO/ShackHartmann.py:396-503, 554-556;
+        ``calib.lgs_spot_kernels``).  Reference slopes, slope units, interaction matrix and reconstructor are calibrated on the
+        elongated spots, as the reference does by constructing the sensor behind the source; the interaction matrix keeps the loop's
+        spot convention (the reference's multi-wavefront branch drops the ``fftshift``, :641-642, which is not reproduced).  The shard
+        runs the batched kernels (``fused_step`` is False).  ``set_lgs_per_env`` then gives every env a star of its own.  A
+        ``UserWarning`` where the reference prints its wrap warning (elongation factor above 1).
         ``atm_AB``: the ring operators handed over instead of recomputed -- one pair (A, B) when the layers share a grid, a list
         with one pair per layer when they have grids of their own (``_atmosphere_tables``); a wrong form or shape is refused
         before anything of the env is touched."""
@@ -1196,6 +1337,11 @@ class BatchedAOEnv:
             raise ValueError(f"unknown wfs_type {wfs_type!r}")
         if p.is_geometric and self.wfs_type != "sh":
             raise ValueError("is_geometric is a mode of the Shack-Hartmann: there is no geometric Pyramid")
+        lgs = None
+        if p.lgs is not None:
+            if self.wfs_type != "sh" or p.is_geometric:
+                raise ValueError("lgs: spot elongation belongs to the diffractive Shack-Hartmann, not to a Pyramid or to is_geometric")
+            lgs = resolve_lgs(p.lgs)
         self.is_geometric = bool(p.is_geometric)
         torch = _torch()
         self.gainCL = gainCL
@@ -1219,6 +1365,15 @@ class BatchedAOEnv:
             self._pyr_tables = calib.PyramidTables(p, self.pupil, self.nPhoton, psf_centering=p.psfCentering,
                                                    n_pix_separation=p.n_pix_separation, post_processing=p.postProcessing)
             self.cam_res = self._pyr_tables.cam_res
+        self._lgs = self._lgs_env = self._lgs_taps = None
+        if lgs is not None:
+            # the sensor is built behind the LGS source: reference slopes, slope units, interaction matrix and reconstructor are all
+            # calibrated on elongated spots (every shard _make_shard makes from here on is handed the table)
+            self._lgs_K, self._lgs_elongation = calib.lgs_spot_kernels(p, sht, **lgs)
+            if self._lgs_elongation > 1:                             # where the reference prints its warning (ShackHartmann.py:494-497)
+                warnings.warn(f"The largest spot elongation is {round(self._lgs_elongation, 3)} times larger than a subaperture! "
+                              "Consider using a higher resolution", stacklevel=2)
+            self._lgs, self._lgs_taps = lgs, calib.lgs_binned_taps(self._lgs_K)
         self._xv_t = torch.as_tensor(self.xvalid, device=self.device)
         self._yv_t = torch.as_tensor(self.yvalid, device=self.device)
 
@@ -1315,6 +1470,8 @@ class BatchedAOEnv:
             sh.upload(L.C_PYR_MASK, self._pyr_tables.mask_pairs)
             if self._wfs_n_theta > 1:
                 sh.upload(L.C_PYR_TT, self._pyr_tt)
+        if self._lgs_taps is not None:                              # an LGS env: calibration shards and the loop shard alike
+            sh.set_lgs_spots(self._lgs_taps[0], self._lgs_taps[1], per_env=False)
         return sh
 
     def _calibrate_pyramid(self):
@@ -2187,6 +2344,59 @@ class BatchedAOEnv:
             return None
         wfs, science = self._shard.get_static_opd()
         return dict(wfs=wfs, science=science)
+
+    # -- laser guide star per env (aoenv_set_lgs_spots; OOPAO/ShackHartmann.py:396-503) ------------------------------------------------
+    def _require_lgs(self, who: str):
+        if self._lgs is None:
+            raise ValueError(f"{who}: the env was not built behind a laser guide star (set_params(..., lgs=dict(...)))")
+
+    def _lgs_held(self) -> dict:
+        """The guide star of every env as held: the per-env assignment, or the calibrated star broadcast."""
+        if self._lgs_env is not None:
+            return self._lgs_env
+        g, N = self._lgs, self.n_envs
+        return dict(Na_profile=np.broadcast_to(g["Na_profile"], (N,) + g["Na_profile"].shape).copy(),
+                    FWHM_spot_up=np.full(N, g["FWHM_spot_up"]), laser_coordinates=np.broadcast_to(g["laser_coordinates"], (N, 2)).copy())
+
+    def _lgs_kernels_per_env(self, held: dict) -> np.ndarray:
+        """``K [n_envs, n_valid, n, n]`` of a per-env assignment; envs with equal parameters share one evaluation."""
+        seen, out = {}, []
+        for prof, fwhm, launch in zip(held["Na_profile"], held["FWHM_spot_up"], held["laser_coordinates"]):
+            key = prof.tobytes() + np.float64(fwhm).tobytes() + launch.tobytes()
+            if key not in seen:
+                seen[key] = calib.lgs_spot_kernels(self.param, self._sh_tables, prof, fwhm, launch,
+                                                   self._lgs["threshold_convolution"])[0]
+            out.append(seen[key])
+        return np.stack(out)
+
+    def set_lgs_per_env(self, Na_profile=None, FWHM_spot_up=None, laser_coordinates=None, env_ids=None):
+        """Every env its own sodium column and launch geometry against the ONE calibration: ``Na_profile`` ``[2, n_z]`` or one per
+        (listed) env ``[k, 2, n_z]`` (``n_z`` as calibrated), ``FWHM_spot_up`` a scalar or ``[k]``, ``laser_coordinates`` ``[x, y]``
+        or ``[k, 2]``; an argument left out stays as held, envs not named keep their kernels (the calibrated ones if nothing was
+        set).  Each env's spots are then convolved with the kernels of its own star (``wfs.lgs_kernels(per_env=True)``), in every
+        loop; reference slopes, slope units and reconstructor stay the calibrated ones -- that is the experiment.  Needs an env
+        built with ``set_params(..., lgs=...)``.  Bad arguments raise before anything is touched.  Not part of ``get_state``."""
+        self._require_lgs("set_lgs_per_env")
+        held = resolve_lgs_per_env(Na_profile, FWHM_spot_up, laser_coordinates, env_ids, self.n_envs, self._lgs_held())
+        taps, box = calib.lgs_binned_taps(self._lgs_kernels_per_env(held))
+        self._shard.set_lgs_spots(taps, box, per_env=True, stream=self._stream())
+        self._lgs_env = held
+
+    def clear_lgs_per_env(self):
+        """Every env the calibrated star again: the one shared table, as set_params left it."""
+        self._require_lgs("clear_lgs_per_env")
+        self._shard.set_lgs_spots(self._lgs_taps[0], self._lgs_taps[1], per_env=False, stream=self._stream())
+        self._lgs_env = None
+
+    @property
+    def lgs(self):
+        """``dict(Na_profile [n_envs, 2, n_z], FWHM_spot_up [n_envs], laser_coordinates [n_envs, 2], threshold_convolution,
+        per_env)`` of the guide stars the loop shard applies; None on an env without a laser guide star."""
+        if self._lgs is None:
+            return None
+        held = {k: v.copy() for k, v in self._lgs_held().items()}
+        held.update(threshold_convolution=self._lgs["threshold_convolution"], per_env=self._lgs_env is not None)
+        return held
 
     def env_seeds(self, seed: int) -> np.ndarray:
         idx = np.arange(self.n_envs, dtype=np.int64) + self.env_index_offset

@@ -195,6 +195,16 @@ class TorchWrapper:
     def static_aberration(self):
         return self._env.static_aberration
 
+    def set_lgs_per_env(self, Na_profile=None, FWHM_spot_up=None, laser_coordinates=None, env_ids=None):
+        return self._env.set_lgs_per_env(Na_profile, FWHM_spot_up, laser_coordinates, env_ids)
+
+    def clear_lgs_per_env(self):
+        return self._env.clear_lgs_per_env()
+
+    @property
+    def lgs(self):
+        return self._env.lgs
+
     @property
     def src(self):
         return self._env.src
@@ -396,6 +406,16 @@ class TimeDelayEnv:
     def static_aberration(self):
         return self._env.static_aberration
 
+    def set_lgs_per_env(self, Na_profile=None, FWHM_spot_up=None, laser_coordinates=None, env_ids=None):
+        return self._env.set_lgs_per_env(Na_profile, FWHM_spot_up, laser_coordinates, env_ids)
+
+    def clear_lgs_per_env(self):
+        return self._env.clear_lgs_per_env()
+
+    @property
+    def lgs(self):
+        return self._env.lgs
+
     @property
     def src(self):
         return self._env.src
@@ -567,6 +587,16 @@ class HistoryEnv:
     @property
     def static_aberration(self):
         return self._env.static_aberration
+
+    def set_lgs_per_env(self, Na_profile=None, FWHM_spot_up=None, laser_coordinates=None, env_ids=None):
+        return self._env.set_lgs_per_env(Na_profile, FWHM_spot_up, laser_coordinates, env_ids)
+
+    def clear_lgs_per_env(self):
+        return self._env.clear_lgs_per_env()
+
+    @property
+    def lgs(self):
+        return self._env.lgs
 
     @property
     def src(self):
